@@ -27,9 +27,24 @@ region; the cartpole's rounds come ten to a launch: every ten) - one
 The timed region (W warm-up rounds, then exactly K rounds between barrier +
 synchronize pairs) is repeated --repeats times from the same nominal; the line
 reports the MEDIAN repetition (and the minimum and every repetition beside it).
-Two further repetitions of the same K rounds carry HIP events on the sweep's and
-the line search's dispatches: the per-kernel durations of `roofline` come from
-those (`ms_per_step_with_kernel_events` shows what the events cost).
+A plain run times the region once (--repeats 1) and prints the headline alone.
+
+    python bench.py --gpus N --steps K --warmup W --full
+
+adds what takes runs of its own: five repetitions by default, two further
+repetitions of the same K rounds with HIP events on the sweep's and the line
+search's dispatches (the per-kernel durations of `roofline` come from those;
+`ms_per_step_with_kernel_events` shows what the events cost), the extra
+roofline points, the CPU baseline and the short runs of the other configs
+(`secondary`).
+
+    python bench.py ... --dump-outputs DIR
+
+writes what the last timed repetition left behind - the nominal (Z, U), its
+costs, the last sweep's gains (k, K), the regularisation and the per-trajectory
+state - as DIR/<name>.npy (float32 / float64; above 64 MB a fixed sample of
+trajectories, their indices in rows.npy).  The inputs depend on the arguments
+only, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -1088,6 +1103,48 @@ def search_accept_bytes(B, N, n, m, A, S, itemsize, accepted_share=1.0,
     return itemsize * B * (per + accepted_share * per_acc)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, s):
+    """What the timed path leaves its caller after the last step - the
+    nominal (Z, U) and its costs, the last sweep's gains (k, K), the
+    regularisation and the per-trajectory state - as path/<name>.npy, in the
+    run's dtype (mu: float64, state: as float64).  Beyond DUMP_LIMIT_BYTES a
+    fixed sample of trajectories (seed 0), their indices in rows.npy."""
+    torch.cuda.synchronize(s.device)
+    k, K = s.gain_views()
+    arrays = {"Z": s.Z, "U": s.U, "J_opt": s.J_opt, "k": k, "K": K,
+              "mu": s.mu, "state": s.state}
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        host[name] = a
+    budget = DUMP_LIMIT_BYTES - 4096  # (room for the .npy headers)
+    per_row = sum(a.nbytes for a in host.values()) / s.B
+    if per_row * s.B > budget:
+        keep = int(budget // (per_row + 8))
+        rows = np.sort(np.random.RandomState(0).choice(s.B, keep,
+                                                       replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
+def emit_line(world, rank, out):
+    """Leaves the process group and prints the result line (rank 0)."""
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1124,6 +1181,14 @@ def main():
                          "rollout, nothing on a rank's path reads it; "
                          "--exchange-every 1 = per iteration, one round per "
                          "launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: five repetitions (unless "
+                         "--repeats), the per-kernel roofline, the extra "
+                         "roofline points, the CPU baseline and the other "
+                         "configs (`secondary`); cartpole workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy (cartpole workload)")
     ap.add_argument("--no-graph-replay", action="store_true",
                     help="double_cartpole_gp: skip the informational hipGraph "
                          "replay (rocprofv3 --pmc and stream capture do not "
@@ -1145,6 +1210,8 @@ def main():
                          "more than one rank the exchange needs the round "
                          "boundary: at most --exchange-every rounds per launch")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "cartpole":
+        ap.error("--dump-outputs: the cartpole workload only")
     exchange_default = args.exchange_every is None
     if exchange_default:
         args.exchange_every = 1
@@ -1175,15 +1242,16 @@ def main():
     n, m = s.n, s.m
     lib = _native.lib()
     K, W = args.steps, args.warmup
-    R = args.repeats or 5
+    R = args.repeats or (5 if args.full else 1)
     n_iter = 1 << 30  # the fit loop never runs out inside the benchmark
     seen = ranks_seen(world, device)
 
     # R repetitions give the headline; R_EV more repetitions of the SAME K rounds
-    # carry HIP events on the two dispatches for the per-kernel durations of
-    # the roofline (the events cost ~4.5 us per kernel - 0.1205 against 0.1116
-    # ms per round at B = 4096 - and are not part of the product's step)
-    R_EV = 2
+    # (--full) carry HIP events on the two dispatches for the per-kernel
+    # durations of the roofline (the events cost ~4.5 us per kernel - 0.1205
+    # against 0.1116 ms per round at B = 4096 - and are not part of the
+    # product's step)
+    R_EV = 2 if args.full else 0
     pool_sweep, pool_search = EventPool(lib), EventPool(lib)
     pool_round = EventPool(lib)
     reps, reps_ev = [], []
@@ -1210,7 +1278,8 @@ def main():
         # with events on them, then the same rounds as TWO launches (sweep,
         # search + accept - the same device code) with events on each: the
         # sweep's own duration for the roofline of SURVEY 8(d)
-        two_launch = rpl == 0 or not round_kernel_ok or rep == R + R_EV - 1
+        two_launch = rpl == 0 or not round_kernel_ok or \
+            (with_events and rep == R + R_EV - 1)
         s._one_launch = False if two_launch else None
         # every repetition times the same K rounds from the same nominal
         s.set_nominal(z0, U)
@@ -1292,14 +1361,74 @@ def main():
              "total_attempted": total_attempted, "live": [live0, liveK],
              "form": "two launches" if two_launch else
                      "%d rounds per launch" % chunk})
+        if rep == R - 1 and args.dump_outputs and rank == 0:
+            # (before the event repetitions and the points reuse the solver)
+            dump_outputs(args.dump_outputs, s)
     s._one_launch = None
 
     order = sorted(range(R), key=lambda i: reps[i]["elapsed"])
     med = reps[order[R // 2]]
     elapsed, total_attempted = med["elapsed"], med["total_attempted"]
+    timed_form = reps[0]["form"]
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "pddp_iterations_per_sec",
+            "value": total_attempted / elapsed,
+            "unit": "trajectory-iterations/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": elapsed / K * 1e3,
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "rccl_ranks_seen": seen,
+            "repeats": R,
+            "ms_per_step_min": reps[order[0]]["elapsed"] / K * 1e3,
+            "ms_per_step_all": [r["elapsed"] / K * 1e3 for r in reps],
+            "config": {
+                "workload": "BASELINE.json configs[1]: cartpole n=4 m=1, "
+                            "known-dynamics iLQR, horizon=%d, batch=%d "
+                            "trajectories per GPU, bounds +-10 (eig-clamp + "
+                            "BoxQP branch), 10 line-search alphas" % (N, B),
+                "batch_per_gpu": B, "horizon": N, "alphas": int(s.A),
+                "unit_definition": "one iLQR attempt of one trajectory: "
+                                   "derivative records when its nominal "
+                                   "changed + backward sweep + line search + "
+                                   "accept",
+                "value_definition": "median of %d repetitions of the timed "
+                                    "region (each: set_nominal, %d warm-up "
+                                    "rounds, %d timed rounds)" % (R, W, K),
+                # how the K timed rounds were issued
+                "launch_form": timed_form,
+                "rounds_per_launch": args.rounds_per_launch,
+                # (ranks > 1) the best rollout is all-gathered every so many
+                # rounds, between launches
+                "exchange_every_rounds": args.exchange_every if world > 1
+                else None,
+                "batched_iterations_per_s": K / elapsed,
+                "trajectory_timesteps_per_s": total_attempted * N / elapsed,
+                "live_trajectories_start_end": med["live"],
+                "backward_kernel_variant": args.kernel_variant,
+                # the timed kernels' f32 arithmetic: reciprocal by v_rcp_f32
+                # (1 ulp) where the reference divides, the BoxQP in its lean
+                # closed form (sign-bit predicates; QpClosed and the
+                # reference's loop behind it), own sincos; the IEEE-division
+                # twins are kernel variants 6 / 8 / 16 / 20 / 24
+                "arithmetic": "f32, v_rcp, lean BoxQP (fall-back: closed form "
+                              "+ the reference's loop), branch-free sincos",
+            },
+        }
+    if not args.full:
+        # a plain run: the headline alone (--full adds what takes runs
+        # of its own)
+        return emit_line(world, rank, out)
+
     # (the repetition with events on the separate sweep / search launches)
     attempted_all = reps_ev[-1]["attempted"]
-    timed_form = reps[0]["form"]
 
     itemsize = 4 if dtype == torch.float32 else 8
     per_traj = algorithmic_bytes_per_trajectory(N, n, m, itemsize, True)
@@ -1399,60 +1528,11 @@ def main():
     if round_obj is not None:
         round_obj["traffic"] = traffic_round
 
-    out = None
     if rank == 0:
-        out = {
-            "metric": "pddp_iterations_per_sec",
-            "value": total_attempted / elapsed,
-            "unit": "trajectory-iterations/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": W,
-            "ms_per_step": elapsed / K * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "rccl_ranks_seen": seen,
-            "repeats": R,
-            "ms_per_step_min": reps[order[0]]["elapsed"] / K * 1e3,
-            "ms_per_step_all": [r["elapsed"] / K * 1e3 for r in reps],
+        out.update({
             "ms_per_step_with_kernel_events": [
                 {"form": r["form"], "ms": r["elapsed"] / K * 1e3}
                 for r in reps_ev],
-            "config": {
-                "workload": "BASELINE.json configs[1]: cartpole n=4 m=1, "
-                            "known-dynamics iLQR, horizon=%d, batch=%d "
-                            "trajectories per GPU, bounds +-10 (eig-clamp + "
-                            "BoxQP branch), 10 line-search alphas" % (N, B),
-                "batch_per_gpu": B, "horizon": N, "alphas": int(s.A),
-                "unit_definition": "one iLQR attempt of one trajectory: "
-                                   "derivative records when its nominal "
-                                   "changed + backward sweep + line search + "
-                                   "accept",
-                "value_definition": "median of %d repetitions of the timed "
-                                    "region (each: set_nominal, %d warm-up "
-                                    "rounds, %d timed rounds)" % (R, W, K),
-                # how the K timed rounds were issued
-                "launch_form": timed_form,
-                "rounds_per_launch": args.rounds_per_launch,
-                # (ranks > 1) the best rollout is all-gathered every so many
-                # rounds, between launches
-                "exchange_every_rounds": args.exchange_every if world > 1
-                else None,
-                "batched_iterations_per_s": K / elapsed,
-                "trajectory_timesteps_per_s": total_attempted * N / elapsed,
-                "live_trajectories_start_end": med["live"],
-                "backward_kernel_variant": args.kernel_variant,
-                # the timed kernels' f32 arithmetic: reciprocal by v_rcp_f32
-                # (1 ulp) where the reference divides, the BoxQP in its lean
-                # closed form (sign-bit predicates; QpClosed and the
-                # reference's loop behind it), own sincos; the IEEE-division
-                # twins are kernel variants 6 / 8 / 16 / 20 / 24
-                "arithmetic": "f32, v_rcp, lean BoxQP (fall-back: closed form "
-                              "+ the reference's loop), branch-free sincos",
-            },
             "roofline": {
                 "bound": "hbm",
                 "kernel": ("backward Riccati sweep from the nominal "
@@ -1522,7 +1602,7 @@ def main():
                         if traffic_search else None),
                 }],
             },
-        }
+        })
         if round_obj is not None:
             # The timed region's dominant kernel is the round kernel: IT is
             # the `roofline` object (bytes = the two phases' agreed figures,
@@ -1623,11 +1703,7 @@ def main():
                     sec.append({"workload": wl, "error": repr(e)[:300]})
                 torch.cuda.empty_cache()
             out["secondary"] = sec
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(out))
+    emit_line(world, rank, out)
 
 
 if __name__ == "__main__":

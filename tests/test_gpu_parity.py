@@ -3224,11 +3224,63 @@ def test_bench_two_ranks_over_rccl():
     out = subprocess.run(
         [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
          "--steps", "5", "--warmup", "2", "--repeats", "2", "--batch", "512",
-         "--no-cpu-baseline", "--no-points"], env=env, capture_output=True,
-        text=True, timeout=900)
+         "--no-cpu-baseline", "--no-points", "--full"], env=env,
+        capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks_seen"] == 2
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps rounds once and prints the
+    headline alone; --dump-outputs writes the last timed round's nominal,
+    costs, gains, regularisation and state - the same arrays from run to run,
+    and the same under --full (whose repetitions each start from the same
+    nominal, the dump taken before its event repetitions)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    K, B = 7, 256
+    full = ["--full", "--repeats", "2", "--no-cpu-baseline"]
+    dumps, lines = {}, {}
+    for run, extra in (("a", []), ("b", []), ("full", full)):
+        out = subprocess.run(
+            [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+             "--steps", str(K), "--warmup", "2", "--batch", str(B),
+             "--dump-outputs", str(tmp_path / run)] + extra,
+            capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        lines[run] = json.loads(out.stdout.strip().splitlines()[-1])
+        dumps[run] = {f[:-4]: np.load(str(tmp_path / run / f))
+                      for f in os.listdir(str(tmp_path / run))}
+    for run in ("a", "b"):
+        line = lines[run]
+        assert line["steps"] == K and line["repeats"] == 1
+        assert len(line["ms_per_step_all"]) == 1 and line["ms_per_step"] > 0
+        assert line["config"]["launch_form"] == "10 rounds per launch"
+        # the attempts of the timed region: every trajectory is live in the
+        # first timed round, none makes more than one attempt per round
+        attempts = line["value"] * line["ms_per_step"] * K / 1e3
+        assert B - 0.5 <= attempts <= K * B + 0.5, attempts
+        for key in ("roofline", "cpu_baseline", "secondary",
+                    "ms_per_step_with_kernel_events"):
+            assert key not in line, key
+    line = lines["full"]
+    assert line["repeats"] == 2 and len(line["ms_per_step_all"]) == 2
+    assert len(line["ms_per_step_with_kernel_events"]) == 2
+    assert line["roofline"]["avg_launch_us"] > 0
+    shapes = {"Z": (B, 101, 4), "U": (B, 100, 1), "J_opt": (B,),
+              "k": (B, 100, 1), "K": (B, 100, 1, 4), "mu": (B,),
+              "state": (B,)}
+    a = dumps["a"]
+    assert {k: v.shape for k, v in a.items()} == shapes
+    for name, arr in a.items():
+        assert arr.dtype in (np.float32, np.float64), name
+        assert np.isfinite(arr).all(), name
+        assert np.array_equal(arr, dumps["b"][name]), name
+        assert np.array_equal(arr, dumps["full"][name]), name
 
 
 @pytest.mark.parametrize("workload,extra", [
@@ -3237,6 +3289,8 @@ def test_bench_two_ranks_over_rccl():
                   "--scaling", "strong"]),
     ("double_cartpole_bnn", ["--batch", "16", "--horizon", "6"]),
     ("double_cartpole_gp", ["--batch", "16", "--horizon", "6"]),
+    ("cartpole", ["--batch", "512", "--repeats", "2", "--no-points",
+                  "--full"]),
 ])
 def test_bench_two_ranks_rehearsal_on_one_gpu(workload, extra):
     """The whole multi-rank path of `bench.py --gpus 2` - the launcher, shard
@@ -3261,6 +3315,11 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(workload, extra):
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks_seen"] == 2
     assert line["value"] > 0 and line["steps"] == 3
+    if "--full" in extra:
+        # the event repetitions ran on both ranks (barrier and all_reduce
+        # inside them)
+        assert len(line["ms_per_step_with_kernel_events"]) == 2
+        assert line["roofline"]["avg_launch_us"] > 0
 
 
 def test_boxqp_many_dimensions_on_the_gpu():

@@ -304,6 +304,27 @@ def test_bench_gpus_flag_is_honoured():
         assert out.returncode == 2 and "device(s) visible" in out.stderr
 
 
+def test_bench_dump_outputs_refuses_other_workloads():
+    """`--dump-outputs` writes the cartpole's timed path only: another
+    workload exits non-zero before anything touches the GPU."""
+    bench = os.path.join(ROOT, "bench.py")
+    out = subprocess.run([sys.executable, bench, "--workload", "mpc_bnn",
+                          "--dump-outputs", "unused"], capture_output=True,
+                         text=True, timeout=300)
+    assert out.returncode == 2
+    assert "--dump-outputs: the cartpole workload only" in out.stderr
+    # the cartpole gets past that check: the next one (a torchrun
+    # environment of another world size) is what stops it, still before the GPU
+    env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
+    for workload in (["--workload", "cartpole"], []):
+        out = subprocess.run([sys.executable, bench, "--gpus", "2",
+                              "--dump-outputs", "unused"] + workload, env=env,
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 2 and "WORLD_SIZE" in out.stderr, out.stderr
+        assert "cartpole workload only" not in out.stderr
+    assert not os.path.exists("unused")
+
+
 def test_best_rollout_single_process():
     from pddp_amd.parallel import gather_best_rollout
     J = torch.tensor([3.0, float("inf"), 1.5])

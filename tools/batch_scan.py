@@ -11,9 +11,9 @@ rows = []
 for B in [int(v) for v in sys.argv[1:]] or [4096, 8192, 12288, 16384, 32768,
                                             65536]:
     out = subprocess.run(
-        [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B),
-         "--no-cpu-baseline", "--no-points", "--no-secondary", "--repeats",
-         "3"], capture_output=True, text=True, timeout=600)
+        [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch",
+         str(B), "--no-cpu-baseline", "--no-points", "--no-secondary",
+         "--repeats", "3"], capture_output=True, text=True, timeout=600)
     if out.returncode != 0:
         print(B, "FAILED", out.stderr[-500:])
         continue

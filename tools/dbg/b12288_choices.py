@@ -11,7 +11,7 @@ from pddp_amd import _native
 import bench
 _native.lib().pddp_sweep_nominal_kernel(int(sys.argv[2]))
 _native.lib().pddp_search_candidates(int(sys.argv[3]))
-sys.argv = ["bench.py", "--batch", sys.argv[1], "--no-cpu-baseline", "--no-points", "--no-secondary", "--repeats", "3"]
+sys.argv = ["bench.py", "--full", "--batch", sys.argv[1], "--no-cpu-baseline", "--no-points", "--no-secondary", "--repeats", "3"]
 bench.main()
 ''' % ROOT
 for B in (8192, 12288, 16384):

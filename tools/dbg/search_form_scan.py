@@ -8,7 +8,7 @@ sys.path.insert(0, %r)
 from pddp_amd import _native
 import bench
 _native.lib().pddp_search_form(int(sys.argv[2]))
-sys.argv = ["bench.py", "--batch", sys.argv[1], "--no-cpu-baseline", "--no-points", "--no-secondary", "--repeats", "3"]
+sys.argv = ["bench.py", "--full", "--batch", sys.argv[1], "--no-cpu-baseline", "--no-points", "--no-secondary", "--repeats", "3"]
 bench.main()
 ''' % ROOT
 for B in [int(v) for v in sys.argv[1:]] or (4096, 8192, 12288, 16384, 32768, 65536):

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
     --output-format csv -d $R/gpurun_out/${TAG}_pmc_sq -- \
-    python3 $R/bench.py --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-points "$@" > /dev/null 2>&1
+    python3 $R/bench.py --full --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-points "$@" > /dev/null 2>&1
 cd $R
 python3 - "$TAG" <<'PY'
 import collections, csv, glob, json, os, sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condenses gpurun_out/<tag>_* (tools/collect_profiles.sh) into profiles/."""
+"""Condenses profiles_raw/<tag>_* (tools/collect_profiles.sh) into profiles/."""
 import collections
 import csv
 import glob
@@ -14,12 +14,13 @@ def newest(pattern):
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 out = "profiles"
+raw = "profiles_raw"
 os.makedirs(out, exist_ok=True)
 
 def stats_and_traffic(suffix, workload, extra_args):
     """kernel-trace stats + the FETCH / WRITE passes of one bench command."""
     try:
-        src = newest("gpurun_out/%s_stats%s/*/*kernel_stats.csv" % (tag, suffix))
+        src = newest(raw + "/%s_stats%s/*/*kernel_stats.csv" % (tag, suffix))
     except ValueError:
         return
     name = "%s%s" % (tag, suffix)
@@ -32,7 +33,7 @@ def stats_and_traffic(suffix, workload, extra_args):
             w.writerow([r["Name"][:110]] + [r[c] for c in cols[1:]])
     traffic = {}
     for kind, ctr in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
-        f = newest("gpurun_out/%s_pmc_%s%s/*/*counter_collection.csv"
+        f = newest(raw + "/%s_pmc_%s%s/*/*counter_collection.csv"
                    % (tag, kind, suffix))
         acc = collections.defaultdict(list)
         for r in csv.DictReader(open(f)):
@@ -80,7 +81,7 @@ stats_and_traffic("_cpbnn_f64", "cartpole BNN (configs[2]) in float64: n=14 m=1 
                   "N=100 B=4096, [200,200] x 100 particles",
                   " --workload cartpole_bnn --dtype f64 --steps 1 --warmup 1")
 
-f = newest("gpurun_out/%s_pmc_sq/*/*counter_collection.csv" % tag)
+f = newest(raw + "/%s_pmc_sq/*/*counter_collection.csv" % tag)
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for r in csv.DictReader(open(f)):
     if "pddp" in r["Kernel_Name"]:
@@ -92,7 +93,7 @@ json.dump({"note": "averages per launch; SQ_WAVE_CYCLES / SQ_WAIT_* / "
           open(os.path.join(out, "%s_pmc_sq.json" % tag), "w"), indent=1)
 
 points = {}
-for p in sorted(glob.glob("gpurun_out/%s_bench*.json" % tag)):
+for p in sorted(glob.glob(raw + "/%s_bench*.json" % tag)):
     try:
         line = [l for l in open(p).read().splitlines() if l.startswith("{")][-1]
         points[os.path.basename(p)[len(tag) + 1:-5]] = json.loads(line)
