@@ -66,6 +66,20 @@ PDDP_DEV void control_law(const T* z, const T* zr, const T* gr, const T* us,
     un[r] = clamp_nan(v, umin[r], umax[r]);
   }
 }
+// The same for the round kernel's paired cartpole state (x, xd), (th, thd) and
+// nominal row: the four differences two at a time (v_pk_add_f32), the K dz
+// chain and the rest as above.  g01 = (k, K0), g23 = (K1, K2), g4u = (K3, u).
+PDDP_DEV float control_law_pk(f32x2 za, f32x2 zb, f32x2 zra, f32x2 zrb,
+                              f32x2 g01, f32x2 g23, f32x2 g4u, float alpha,
+                              float umin, float umax) {
+  const f32x2 da = pk_sub(za, zra), db = pk_sub(zb, zrb);
+  float s = n4::fma_(da.x, g01.y, 0.0f);
+  s = n4::fma_(da.y, g23.x, s);
+  s = n4::fma_(db.x, g23.y, s);
+  s = n4::fma_(db.y, g4u.x, s);
+  const float du = n4::fma_(alpha, g01.x, s);
+  return clamp_nan(g4u.y + du, umin, umax);
+}
 
 // Same line search with the trajectory's nominal data staged in LDS: 16 lanes
 // per trajectory (one per alpha, A <= 16), four trajectories per wavefront.
@@ -159,6 +173,11 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
   constexpr int GST = PRE ? GS + m : GS;
   constexpr int UST = PRE ? GS + m : m;
   constexpr int kTailRows = DENSE ? 8 : 4;  // rows per lane of the short tail
+  // the round kernel's cartpole step on register pairs (v_pk_*), for the
+  // CartpoleCost's live rows {x, sin, cos} - the configuration it is built for
+  constexpr bool kPaired = PRE && MODEL == PDDP_MODEL_CARTPOLE &&
+                           std::is_same<T, float>::value && GST == 6 &&
+                           QM == 0b11001u;
   __shared__ int sh_dec[WPB][4][2];  // H = 2: {amin_out, fresh} per trajectory
   const int lane = tid & (kWave - 1);
   const int wave_all = tid >> 6;
@@ -254,6 +273,47 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
   const bool store_uc = !(FUSED && n <= 6 && Lout == nullptr &&
                           rec != nullptr && N + 1 <= 16 * H * kTailRows);
   auto rollout = [&](T alpha, T* Zci, size_t zstep, T* Uci, size_t ustep) {
+    if constexpr (kPaired) {
+      // (the round kernel, cartpole, CartpoleCost: the step on register
+      // pairs - the state (x, xd | th, thd) as one quad, which is also the
+      // candidate row's 16-byte store; models.hpp, the paired forms)
+      typedef float V4_ __attribute__((ext_vector_type(4)));
+      V4_ z4 = {Zs[0], Zs[1], Zs[2], Zs[3]};  // Z_new[0] = Z[0]  (ilqr.py:690)
+      float J = 0.0f;
+      auto step = [&](const int t) {
+        const V4_ zr = *reinterpret_cast<const V4_*>(
+            __builtin_assume_aligned(Zs + t * 4, 16));
+        const f32x2* g2 = reinterpret_cast<const f32x2*>(
+            __builtin_assume_aligned(Gs + t * 6, 8));
+        const f32x2 g01 = g2[0], g23 = g2[1], g4u = g2[2];
+        const f32x2 sc = sincos_pk(z4.z);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        const float u = control_law_pk(z4.xy, z4.zw, zr.xy, zr.zw, g01, g23,
+                                       g4u, alpha, umin[0], umax[0]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Zci[(size_t)t * zstep + j] = z4[j];
+        J += cartpole_cost_pk(P, z4.xy, sc, u);
+        f32x2 na, nb;
+        cartpole_dynamics_pk(P, z4.xy, z4.zw, sc, u, na, nb);
+        z4 = V4_{na.x, na.y, nb.x, nb.y};
+      };
+      int t = 0;
+      for (; t + 3 < N; t += 4) {
+        step(t);
+        step(t + 1);
+        step(t + 2);
+        step(t + 3);
+      }
+#pragma unroll 1
+      for (; t < N; ++t) step(t);
+      T z[n] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+      for (int j = 0; j < n; ++j) Zci[(size_t)N * zstep + j] = z[j];
+      const T lf =
+          cost_value<T, MODEL>(P, z, nullptr, trig_of<T, MODEL>(z), true);
+      return J + lf;
+    }
     T z[n], zn[n], un[m];
 #pragma unroll
     for (int j = 0; j < n; ++j) z[j] = Zs[j];  // Z_new[0] = Z[0]  (ilqr.py:690)
@@ -496,6 +556,19 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
         for (int k = 0; k < KR; ++k) {
           const int t = t_first + 16 * H * k;
           const int tu = t < N ? t : 0;
+          if constexpr (kPaired) {
+            // (the rollout's paired control law, on the same pairs)
+            typedef float V4_ __attribute__((ext_vector_type(4)));
+            const V4_ zr = *reinterpret_cast<const V4_*>(
+                __builtin_assume_aligned(Zs + tu * 4, 16));
+            const f32x2* g2 = reinterpret_cast<const f32x2*>(
+                __builtin_assume_aligned(Gs + tu * 6, 8));
+            uu[k][0] = control_law_pk(f32x2{zz[k][0], zz[k][1]},
+                                      f32x2{zz[k][2], zz[k][3]}, zr.xy, zr.zw,
+                                      g2[0], g2[1], g2[2], alpha_w, umin[0],
+                                      umax[0]);
+            continue;
+          }
           T zr[n], gr[GS], us[m];
 #pragma unroll
           for (int j = 0; j < n; ++j) zr[j] = Zs[tu * n + j];

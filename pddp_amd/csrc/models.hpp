@@ -137,6 +137,61 @@ PDDP_DEV void sincos_(float x, float& s, float& c) {
 }
 PDDP_DEV void sincos_(double x, double& s, double& c) { sincos(x, &s, &c); }
 
+// ---- paired f32 forms (the round kernel's rollout step, line_search_lds.hpp)
+// A lone wavefront issues v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 at the
+// cost of one v_fma_f32 (5.4 cycles, tools/probe/packed_f32_probe.hip), and
+// each half is the IEEE f32 operation: two independent operations of the same
+// kind in one instruction, the same bits.  Only such pairs are packed, every
+// contraction written out as in the scalar forms it stands for.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+PDDP_DEV f32x2 splat2(float a) { return f32x2{a, a}; }
+PDDP_DEV f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
+  return __builtin_elementwise_fma(a, b, c);
+}
+// sincos_poly with the sine's and the cosine's polynomials side by side:
+// (s, c)
+PDDP_DEV f32x2 sincos_poly_pk(float r, int q) {
+  // (z, r): z = r r in the low half, which the splats read without a move
+  f32x2 zr = f32x2{r * r, r};
+  const f32x2 p = zr.yx * zr.xx;  // (r z, z z)
+  f32x2 w = pk_fma(zr.xx, f32x2{-1.9515295891e-4f, 2.443315711809948e-5f},
+                   f32x2{8.3321608736e-3f, -1.388731625493765e-3f});
+  w = pk_fma(zr.xx, w, f32x2{-1.6666654611e-1f, 4.166664568298827e-2f});
+  zr.x = __builtin_fmaf(zr.x, -0.5f, 1.0f);  // (1 - z / 2, r)
+  const f32x2 sc = pk_fma(p, w, zr.yx);
+  const bool swap = (q & 1) != 0;
+  const unsigned ss = ((unsigned)q & 2u) << 30;
+  const unsigned cs = (((unsigned)q + 1u) & 2u) << 30;
+  return f32x2{__uint_as_float(__float_as_uint(swap ? sc.y : sc.x) ^ ss),
+               __uint_as_float(__float_as_uint(swap ? sc.x : sc.y) ^ cs)};
+}
+// sincos_ on the paired polynomials: the same reduction, the same fall-back
+PDDP_DEV f32x2 sincos_pk(float x) {
+  const double xd = (double)x;
+  const double kd = __builtin_rint(xd * 0.63661977236758138243);  // 2 / pi
+  double rd = __builtin_fma(kd, -1.57079632679489655800e+00, xd);
+  rd = __builtin_fma(kd, -6.12323399573676603587e-17, rd);
+  const f32x2 sc = sincos_poly_pk((float)rd, (int)kd);
+  float s = sc.x, c = sc.y;
+  const bool big = fabsf(x) >= kTrigCoreLimit;
+  if (__builtin_expect(__any(big), 0)) {
+    float sl, cl;
+    sincosf(x, &sl, &cl);
+    s = big ? sl : s;
+    c = big ? cl : c;
+  }
+  return f32x2{s, c};
+}
+// a - b two at a time.  (Written out: of a vector subtraction whose halves are
+// only read one by one the compiler makes two v_sub_f32.)
+PDDP_DEV f32x2 pk_sub(f32x2 a, f32x2 b) {
+  f32x2 d;
+  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"
+      : "=v"(d)
+      : "v"(a), "v"(b));
+  return d;
+}
+
 // 1 / a: float through v_rcp_f32 and one Newton step (<= 1 ulp, 3
 // instructions instead of the 11 of an IEEE division); double divides.
 PDDP_DEV float inv_(float a) {
@@ -463,6 +518,61 @@ PDDP_DEV T cost_value(const ProblemT<T>& P, const T* z, const T* u,
     }
   }
   return cost;
+}
+
+// The cartpole's stage cost and dynamics on the paired state of the round
+// kernel's rollouts, za = (x, xd), zb = (th, thd), with sc = (sin th, cos th)
+// (sincos_pk) and the clamped action F: cost_value<float, CARTPOLE, 0b11001>
+// (CartpoleCost's live rows {x, sin, cos}) and dynamics<float, CARTPOLE,
+// false>, operation for operation - the pairs are the two live columns
+// j = 3, 4 of the quadratic form, (g s, 3 mp c), ((mc + mp) a1, 3 mp a1) and
+// the two accelerations' last products.
+PDDP_DEV float cartpole_cost_pk(const ProblemT<float>& P, f32x2 za, f32x2 sc,
+                                float F) {
+  constexpr int S = PDDP_MAX_AUG;
+  const float* Q = P.Q;
+  const float dx0 = za.x - P.goal[0];
+  const f32x2 dx34 = sc - f32x2{P.goal[3], P.goal[4]};
+  // dq_j = sum over the live rows i = 0, 3, 4 of dx_i Q[i][j], in that order
+  float dq0 = __builtin_fmaf(dx0, Q[0 * S + 0], 0.0f);
+  f32x2 dq = pk_fma(splat2(dx0), f32x2{Q[0 * S + 3], Q[0 * S + 4]}, splat2(0.0f));
+  dq0 = __builtin_fmaf(dx34.x, Q[3 * S + 0], dq0);
+  dq = pk_fma(splat2(dx34.x), f32x2{Q[3 * S + 3], Q[3 * S + 4]}, dq);
+  dq0 = __builtin_fmaf(dx34.y, Q[4 * S + 0], dq0);
+  dq = pk_fma(splat2(dx34.y), f32x2{Q[4 * S + 3], Q[4 * S + 4]}, dq);
+  float cost = __builtin_fmaf(dq0, dx0, 0.0f);
+  cost = __builtin_fmaf(dq.x, dx34.x, cost);
+  cost = __builtin_fmaf(dq.y, dx34.y, cost);
+  const float du = F - P.ugoal[0];
+  const float dr = __builtin_fmaf(du, P.R[0], 0.0f);
+  return __builtin_fmaf(dr, du, cost);
+}
+PDDP_DEV void cartpole_dynamics_pk(const ProblemT<float>& P, f32x2 za,
+                                   f32x2 zb, f32x2 sc, float F, f32x2& na,
+                                   f32x2& nb) {
+  const float mc = P.p[0], mp = P.p[1], l = P.p[2], mu = P.p[3], g = P.p[4];
+  const float dt = P.dt;
+  const float x = za.x, xd = za.y, th = zb.x, thd = zb.y, c = sc.y;
+  const float a0 = mp * l * thd * thd * sc.x;
+  const f32x2 ga = sc * f32x2{g, 3.0f * mp};  // (a1 = g s, 3 mp c)
+  const float a1 = ga.x;
+  const float a2 = __builtin_fmaf(-mu, xd, F);
+  const float a3 = __builtin_fmaf(-ga.y, c, 4.0f * (mc + mp));
+  const f32x2 m1 = f32x2{mc + mp, 3.0f * mp} * splat2(a1);
+  float num_t = __builtin_fmaf(a2, c, m1.x);
+  num_t = num_t + num_t;
+  num_t = __builtin_fmaf(a0, c, num_t);
+  const float ia3 = inv_(a3);
+  float num_x = m1.y * c;
+  num_x = __builtin_fmaf(2.0f, a0, num_x);
+  num_x = __builtin_fmaf(4.0f, a2, num_x);
+  const float il = 1.0f / l;
+  // (xdd, thdd) = (num_x ia3, (-3 num_t) (ia3 / l))
+  const f32x2 acc = f32x2{num_x, -3.0f * num_t} * f32x2{ia3, ia3 * il};
+  const float nxd = __builtin_fmaf(acc.x, dt, xd);
+  const float nthd = __builtin_fmaf(acc.y, dt, thd);
+  na = f32x2{__builtin_fmaf(nxd, dt, x), nxd};
+  nb = f32x2{__builtin_fmaf(nthd, dt, th), nthd};
 }
 
 // Cost with gradient and Hessian w.r.t. (z, u) (ilqr.py:464-465,471-473).
