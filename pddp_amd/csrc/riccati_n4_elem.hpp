@@ -168,37 +168,98 @@ struct Vec {
 //    is 2.9 us shorter.  The loop itself still runs behind QpClosed: on the
 //    records-path variants (exact=True), in float64, and for the irregular
 //    rows of the class test below.
+//
+// Paired (models.hpp, the paired forms): the gaps of the Newton point to the
+// box, and Q x + c and Q x / 2 + c at both iterates, are one v_pk_* each -
+// per half the operation the scalar form did, the same bits.  The pairs are
+// registers the operands already sit in ({lo, hi}: two words of one LDS read;
+// {Quu, Qu}: the step's paired sum, step_core) or are produced into ({xs,
+// x1}).  A lone operand is the low half of a pair whose high half is left
+// undefined (`lo_word`): every instruction that takes one reads only its low
+// half (op_sel_hi 0 for that operand).  A splat would cost a v_mov per use.
+PDDP_DEV f32x2 lo_word(float a) {  // (a, undefined): read through op_sel only
+  f32x2 r;
+  r.x = a;
+  return r;
+}
+// (lo - x, x - hi) for lh = (lo, hi): sign bits x > lo, x < hi
+PDDP_DEV f32x2 box_gaps(f32x2 lh, float x) {
+  f32x2 d;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[1,0]"
+      : "=v"(d)
+      : "v"(lh), "v"(lo_word(x)));
+  return d;
+}
+// a X + Qu at both iterates X = (xs, x1), qq = (Quu, Qu)
+PDDP_DEV f32x2 fma_at(float a, f32x2 X, f32x2 qq) {
+  return pk_fma(splat2(a), X, qq.yy);
+}
+// (-a.x b, a.y b): -s Quzc and Quzr Quzc of the step (never fused).  Half for
+// half the products the scalar code made - (-s) Quzc is -(s Quzc) bit for
+// bit, except that the sign of a NaN result is not pinned down.
+PDDP_DEV f32x2 quz_products(f32x2 a, float b) {
+  f32x2 r;  // (written out: the compiler negates a.x with a v_xor_b32 first)
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[1,0]"
+      : "=v"(r)
+      : "v"(a), "v"(lo_word(b)));
+  return r;
+}
 struct QpLean1 {
   float x, inv;
   int free_w;  // flag in the sign bit
-  PDDP_DEV void solve(float x0, float Q, float c, float lo, float hi) {
-    const float d_lo = lo - x0, d_hi = x0 - hi;  // sign: x0 > lo, x0 < hi
-    const float xs = __builtin_amdgcn_fmed3f(x0, lo, hi);
+  float Q, d_lo, d_hi, xs;
+  // Q = (Quu < 0 ? 1e-12 : Quu) + reg (ilqr.py:633-634), the warm start's
+  // gaps to the box and its clamp, issued in this order: the paired sum
+  // {Quu, Qu} and the hand-issued sign-bit operations (splat, bsel) each need
+  // one instruction between their result and its first reader, and the
+  // warm start's three operations are the independent work that fills those
+  // slots (left to the scheduler, they became s_nop)
+  PDDP_DEV void head(float x0, float Quu, float reg, f32x2 lh) {
+    d_lo = lh.x - x0;
+    __builtin_amdgcn_sched_barrier(0);
+    const int neg = splat(sgn(Quu));
+    __builtin_amdgcn_sched_barrier(0);
+    d_hi = x0 - lh.y;
+    __builtin_amdgcn_sched_barrier(0);
+    const float q = bsel(neg, 1e-12f, Quu);
+    __builtin_amdgcn_sched_barrier(0);
+    xs = __builtin_amdgcn_fmed3f(x0, lh.x, lh.y);
+    __builtin_amdgcn_sched_barrier(0);
+    Q = q + reg;
+  }
+  // after head(): c = qq.y (Qu), lh = (lo, hi)
+  PDDP_DEV void solve(f32x2 qq, f32x2 lh) {
+    const float c = qq.y, lo = lh.x, hi = lh.y;
+    f32x2 X;  // (xs, x1)
+    X.x = xs;
     const float hQ = 0.5f * Q;
     inv = __builtin_amdgcn_rcpf(Q);
     // ---- iteration 0                                        (:191-239)
-    const float g0 = fma_(Q, xs, c);
+    const float s0 = fma_(c, -inv, -xs);  // newton - xs
+    const float xa = xs + s0;
+    X.y = __builtin_amdgcn_fmed3f(xa, lo, hi);
+    const float x1 = X.y;
+    const f32x2 d1 = box_gaps(lh, xa);  // x1 == lo <=> xa <= lo
+    const f32x2 g = fma_at(Q, X, qq);   // (g0, g1)
+    const f32x2 h = fma_at(hQ, X, qq);  // Q x / 2 + c at xs, x1
+    const float g0 = g.x, g1 = g.y;
     const int ncl0 = (sgn(d_hi) & ~sgn(d_lo) & ~sgn(g0)) | (~sgn(d_hi) & sgn(g0));
     const int small0 = sgn(__builtin_fabsf(g0) - 1e-8f);
     const int done0 = ncl0 | small0;
-    const float s0 = fma_(c, -inv, -xs);  // newton - xs
-    const float xa = xs + s0;
-    const float x1 = __builtin_amdgcn_fmed3f(xa, lo, hi);
-    const float d1_lo = lo - xa, d1_hi = xa - hi;  // x1 == lo <=> xa <= lo
-    const float f0 = xs * fma_(hQ, xs, c);
-    const float num = fma_(x1, fma_(hQ, x1, c), -f0);  // f1 - f0
+    const float f0 = xs * h.x;
+    const float num = fma_(x1, h.y, -f0);  // f1 - f0
     // ---- iteration 1: exit tests
     const int conv = sgn(fma_(-1e-8f, __builtin_fabsf(f0), -num));
-    const float g1 = fma_(Q, x1, c);
-    const int ncl1 = (sgn(d1_hi) & ~sgn(d1_lo) & ~sgn(g1)) | (~sgn(d1_hi) & sgn(g1));
+    const int ncl1 = (sgn(d1.y) & ~sgn(d1.x) & ~sgn(g1)) | (~sgn(d1.y) & sgn(g1));
     x = bsel(splat(done0), xs, x1);
     // free = (done0 & !ncl0) | (!done0 & (conv | !ncl1)), done0 = ncl0 | small0
     free_w = ~ncl0 & (small0 | conv | ~ncl1);
   }
 };
 
-// The products and reductions of one step, hand-scheduled: 27 instructions,
-// every DPP read at least two instructions behind the write of its source (the
+// The products and reductions of one step, hand-scheduled: 25 instructions
+// and, float, one v_pk_add_f32 for Luu + .. and Lu + .. (27 scalar), every DPP
+// read at least two instructions behind the write of its source (the
 // compiler has to pad a dependent DPP chain with s_nop - nine per step when
 // these were seven separate statements; it also folds a DPP move into v_mul /
 // v_add but not into v_fmac, riccati_n4_quad.hpp).  Lane (i, j) of a row:
@@ -247,7 +308,10 @@ PDDP_DEV StepCore step_core(float V, float vc, float fr, float fc, f32x4 Fs,
                             f32x4 Fq, float Lzz, float Lzc, float Luzr,
                             float Luu, float Lu) {
   StepCore o;
-  float A;
+  float A, p1, p2;
+  // (Luu + p1 and Lu + p2 are one v_pk_add_f32 after the statement: {Luu, Lu}
+  // are two words of one LDS read; the product of A and fc moved up so that
+  // the last DPP read of q1 is still two instructions behind its write)
 #define PDDP_RM " row_mask:0xf bank_mask:0xf\n\t"
   asm("v_mul_f32 %[p1], %[fr], %[V]\n\t"
       "v_mul_f32 %[p2], %[fc], %[vc]\n\t"
@@ -265,25 +329,25 @@ PDDP_DEV StepCore step_core(float V, float vc, float fr, float fc, f32x4 Fs,
       "v_fmac_f32_dpp %[Qzc], %[vc], %[Fq1] quad_perm:[1,2,3,0]" PDDP_RM
       "v_fma_f32 %[Qzz], %[A], %[Fq0], %[Lzz]\n\t"
       "v_add_f32_dpp %[p1], %[p1], %[p1] quad_perm:[1,0,3,2]" PDDP_RM
+      "v_mul_f32 %[q1], %[A], %[fc]\n\t"
       "v_fmac_f32_dpp %[Qzz], %[A], %[Fq1] quad_perm:[1,2,3,0]" PDDP_RM
       "v_fmac_f32_dpp %[Qzc], %[vc], %[Fq2] quad_perm:[2,3,0,1]" PDDP_RM
-      "v_mul_f32 %[q1], %[A], %[fc]\n\t"
+      "v_add_f32_dpp %[q1], %[q1], %[q1] quad_perm:[2,3,0,1]" PDDP_RM
       "v_fmac_f32_dpp %[Qzz], %[A], %[Fq2] quad_perm:[2,3,0,1]" PDDP_RM
       "v_fmac_f32_dpp %[Qzc], %[vc], %[Fq3] quad_perm:[3,0,1,2]" PDDP_RM
-      "v_add_f32_dpp %[q1], %[q1], %[q1] quad_perm:[2,3,0,1]" PDDP_RM
-      "v_fmac_f32_dpp %[Qzz], %[A], %[Fq3] quad_perm:[3,0,1,2]" PDDP_RM
-      "v_add_f32 %[p1], %[Luu], %[p1]\n\t"
       "v_add_f32_dpp %[q1], %[q1], %[q1] quad_perm:[1,0,3,2]" PDDP_RM
-      "v_add_f32 %[p2], %[Lu], %[p2]\n\t"
+      "v_fmac_f32_dpp %[Qzz], %[A], %[Fq3] quad_perm:[3,0,1,2]" PDDP_RM
       "v_add_f32 %[q1], %[Luzr], %[q1]\n\t"
-      : [p1] "=&v"(o.Quu), [p2] "=&v"(o.Qu), [q1] "=&v"(o.Quzr),
+      : [p1] "=&v"(p1), [p2] "=&v"(p2), [q1] "=&v"(o.Quzr),
         [Qzz] "=&v"(o.Qzz), [Qzc] "=&v"(o.Qzc), [A] "=&v"(A)
       : [V] "v"(V), [vc] "v"(vc), [fr] "v"(fr), [fc] "v"(fc),
         [Fs0] "v"(Fs[0]), [Fs1] "v"(Fs[1]), [Fs2] "v"(Fs[2]), [Fs3] "v"(Fs[3]),
         [Fq0] "v"(Fq[0]), [Fq1] "v"(Fq[1]), [Fq2] "v"(Fq[2]), [Fq3] "v"(Fq[3]),
-        [Lzz] "v"(Lzz), [Lzc] "v"(Lzc), [Luzr] "v"(Luzr), [Luu] "v"(Luu),
-        [Lu] "v"(Lu));
+        [Lzz] "v"(Lzz), [Lzc] "v"(Lzc), [Luzr] "v"(Luzr));
 #undef PDDP_RM
+  const f32x2 q = f32x2{Luu, Lu} + f32x2{p1, p2};
+  o.Quu = q.x;
+  o.Qu = q.y;
   return o;
 }
 
@@ -311,9 +375,10 @@ PDDP_DEV ElemGains<T> elem_gains(T kprev, T Quu, T Qu, T reg, T lo_b, T hi_b,
   T qp_Q, kt = T(0), sK = T(0), c = T(0), wv = T(0);
   unsigned long long oddm;
   if constexpr (F32) {
-    qp_Q = bsel(splat(sgn(Quu)), 1e-12f, Quu) + reg;
     QpLean1 ql;
-    ql.solve(kprev, qp_Q, Qu, lo_b, hi_b);
+    ql.head(kprev, Quu, reg, f32x2{lo_b, hi_b});
+    qp_Q = ql.Q;
+    ql.solve(f32x2{Quu, Qu}, f32x2{lo_b, hi_b});
     kt = ql.x;
     sK = __int_as_float(splat(ql.free_w) & __float_as_int(ql.inv));
     n4q::rank_one_coeffs(kt, sK, Quu, Qu, c, wv);
@@ -751,14 +816,24 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
     const ElemGains<T> g_ = elem_gains<T>(kprev, Quu, Qu, reg, w.Sc[2], w.Sc[3],
                                           lane, status, alive_m);
     const T kt = g_.kt, sK = g_.sK, c = g_.c, wv = g_.wv;
+    // the two products by Quzc: -s Quzc (the gains) and Quzr Quzc (the value
+    // update) - float: one v_pk_mul_f32 of the pair {s, Quzr}
+    T Ks, QQ;
+    if constexpr (F32) {
+      const f32x2 m = quz_products(f32x2{sK, q.Quzr}, Quzc);
+      Ks = m.x;
+      QQ = m.y;
+    } else {
+      Ks = -(sK * Quzc);
+      QQ = mul_nc(q.Quzr, Quzc);
+    }
     // ---- gains out: K = -s Quz (column form in lanes (0, j)), k elsewhere
-    ib[s * kImg + ostage] = (l < 4) ? -(sK * Quzc) : kt;
+    ib[s * kImg + ostage] = (l < 4) ? Ks : kt;
     kprev = kt;
     // ---- value update (ilqr.py:664-672 with K = -s Quz):
     // V' = sym(Qzz) + c Quz Quz^T,  V_z' = Qz + w Quz
     // (every term symmetric in (i, j) bit for bit: a + b == b + a)
-    V = fma_(T(0.5), n4::opaque(q.Qzz + QzzT),
-             mul_nc(c, mul_nc(q.Quzr, Quzc)));
+    V = fma_(T(0.5), n4::opaque(q.Qzz + QzzT), mul_nc(c, QQ));
     vc = fma_(wv, Quzc, q.Qzc);
   };
 
