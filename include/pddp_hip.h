@@ -306,8 +306,13 @@ int pddp_pack_best_f64(int B, int nz, int nu, const double* J, const double* Z,
  * J_opt[b] = sum_t L[b][t] in t order (ilqr.py:289 L.sum()) and fresh[b] is
  * cleared.  Z [B][N+1][n], U [B][N] un-clamped nominal actions.  Under
  * IGNORE_UNCERTAINTY:
- *   cartpole          f32, bounded (u_min, u_max non-NULL), PDDP_BRANCH_EIG
- *                     (csrc/riccati_n4_elem.hpp);
+ *   cartpole          f32 and f64, both branches, bounded (u_min, u_max
+ *                     non-NULL) or not (both NULL) (csrc/riccati_n4_elem.hpp;
+ *                     every combination but bounded PDDP_BRANCH_EIG in the
+ *                     kernels of csrc/cartpole_branches.hip.  Gains of
+ *                     trajectories with active[b] == 0 are left alone there;
+ *                     the bounded PDDP_BRANCH_EIG f32 kernels may overwrite
+ *                     them);
  *   pendulum, double cartpole   f32 and f64, both branches, bounded or not
  *                     (csrc/riccati_mfma16_nominal.hpp: the 16 x 16
  *                     matrix-core sweep, its records generated block by block
@@ -400,9 +405,11 @@ int pddp_search_accept_f64(const pddp_problem* problem, int B, int N, int A,
  * winner's actions are its control law at its states, re-evaluated.)
  * `mu` is both the sweep's `reg` and the schedule's state; `scratch` as `rec`
  * of pddp_search_accept_* with L == NULL (B (N+1) n scalars).  Cartpole under
- * IGNORE_UNCERTAINTY, f32, bounded, PDDP_BRANCH_EIG, A <= 16, N <= 127 and at
- * most 4096 trajectories (one workgroup of 16 per CU); PDDP_E_UNSUPPORTED
- * otherwise (make the two calls then).
+ * IGNORE_UNCERTAINTY, f32, both branches, bounded or not (u_min and u_max both
+ * NULL: the search clamps to +-inf), A <= 16, N <= 127 (every branch: the LDS
+ * image of a step is the same 52 words) and at most 4096 trajectories (one
+ * workgroup of 16 per CU); PDDP_E_UNSUPPORTED otherwise (make the two calls
+ * then).
  * `rounds` >= 1: that many attempts of every trajectory in the one launch,
  * exactly as `rounds` calls with rounds = 1 (trajectories are independent and
  * a workgroup owns its sixteen for the whole launch; one that has left the fit

@@ -154,10 +154,10 @@ class ILQRSolver(object):
                 self.kernel_variant == 0):
             return False
         if self.problem.model == 1:  # cartpole: csrc/riccati_n4_elem.hpp
-            # (f32, and - round 5 - the same mapping in f64)
+            # (f32, and - round 5 - the same mapping in f64; all four gain
+            # branches: eig-clamp / V_zz-regularised, bounded or not)
             return (self.n == 4 and
-                    self.u_min is not None and self.u_max is not None and
-                    self.branch == BRANCH_EIG)
+                    (self.u_min is None) == (self.u_max is None))
         # pendulum (3), double cartpole (2): csrc/riccati_mfma16_nominal.hpp -
         # f32 and f64, both branches, bounded or not
         return self.problem.model in (2, 3) and \
@@ -166,7 +166,10 @@ class ILQRSolver(object):
     def _nominal_sweep_pays(self):
         """Where round() takes the sweep from the nominal by itself (measured,
         tools/nominal_round_time.py, 4096 trajectories): cartpole f32 1.37x
-        the round on records, pendulum f32 1.04x; pendulum f64 0.95x and the
+        the round on records (bounded eig-clamp; the other gain branches,
+        tools/cartpole_branch_round_time.py: two launches 1.48x - 1.61x f32,
+        1.25x - 1.54x f64, the one-launch round 1.8x - 2.0x),
+        pendulum f32 1.04x; pendulum f64 0.95x and the
         double cartpole 0.65x (f32) / 0.74x (f64) - its record is ~1500
         instructions against a step of ~150, and a block of them in LDS leaves
         one workgroup per CU.  `sweep_nominal()` itself works wherever
@@ -365,7 +368,7 @@ class ILQRSolver(object):
         attempts).  False when it does not apply (the caller then makes the two
         calls)."""
         if self.dtype != torch.float32 or self.plugin is not None or \
-                self.u_min is None or self.u_max is None:
+                (self.u_min is None) != (self.u_max is None):
             self._one_launch = False
             return False
         if events is not None:

@@ -1,7 +1,12 @@
-// riccati_n4_elem.hpp - the n = 4, m = 1 bounded eig-clamp sweep (branch B,
-// ilqr.py:629-672) from the nominal trajectory, ONE wavefront per four
-// trajectories and nothing shared between wavefronts: no roles, no phase
-// barrier, no exchange buffers.
+// riccati_n4_elem.hpp - the n = 4, m = 1 sweep from the nominal trajectory,
+// ONE wavefront per four trajectories and nothing shared between wavefronts:
+// no roles, no phase barrier, no exchange buffers.  Written for - and, in the
+// instantiation BR = kBrEigBox, unchanged from - the bounded eig-clamp branch
+// (ilqr.py:629-672); the other three gain branches of the reference's
+// `backward` (eig-clamp without bounds, V_zz-regularised with and without,
+// ilqr.py:584-643) are the same mapping, images and generator with another
+// gain step and value update (branch_gains below), in kernels
+// of their own (cartpole_branches.hip).
 //
 // Why: at B = 4096 every n = 4 sweep is a chain of N
 // dependent steps on wavefronts that have a SIMD to themselves, and a lone
@@ -433,6 +438,105 @@ PDDP_DEV ElemGains<T> elem_gains(T kprev, T Quu, T Qu, T reg, T lo_b, T hi_b,
   return ElemGains<T>{kt, sK, c, wv};
 }
 
+// ---- the other gain branches of ilqr.py `backward`.  BR is a
+// template parameter of the sweep: every instantiation carries its own step
+// only, and kBrEigBox is the code above, untouched.
+constexpr int kBrEigBox = 0;   // eig-clamp, bounded      (ilqr.py:644-662)
+constexpr int kBrEig = 1;      // eig-clamp, unbounded    (ilqr.py:635-643)
+constexpr int kBrChol = 2;     // V_zz-regularised, unbounded      (:594-599)
+constexpr int kBrCholBox = 3;  // V_zz-regularised, bounded        (:600-617)
+constexpr bool br_bounded(int br) { return br == kBrEigBox || br == kBrCholBox; }
+constexpr bool br_chol(int br) { return br == kBrChol || br == kBrCholBox; }
+
+// The gains of one step of those branches for the four trajectories of a
+// wavefront: kt = k, sK = s with K = -s Quz_reg (0: K zeroed by the BoxQP), and
+// the step's PDDP_BWD_* code (the same in the 16 lanes of a row).  `Quug`:
+// Quu_reg of the V_zz-regularised branches (Quu + reg f.f).  Plain statements,
+// the arithmetic of the sweeps on records (riccati_n4_quad.hpp): one
+// reciprocal (float: v_rcp_f32, float64: IEEE division), and for the bounded
+// form the BoxQP of the bounded eig-clamp step on Quu_reg - float: QpLean1,
+// the closed form of riccati_n4.hpp and the reference's loop behind one class
+// test; float64: the closed form and the loop.
+template <typename T, int BR>
+PDDP_DEV int branch_gains(T kprev, T Quu, T Qu, T Quug, T reg, T lo_b, T hi_b,
+                          bool alive, int lane, T& kt, T& sK) {
+  int st = PDDP_BWD_OK;
+  if constexpr (BR == kBrEig) {
+    if (!is_finite(Quu)) st = PDDP_BWD_NAN;      // eig raises (ilqr.py:631)
+    const T e = (Quu < T(0) ? T(1e-12) : Quu) + reg;  // ilqr.py:633-634
+    sK = n4::div_<true>(T(1), e);                // (E / e) E^T
+    kt = -(sK * Qu);
+    if (kt != kt) st = PDDP_BWD_NAN;             // ilqr.py:639-640 (k; K: caller)
+  } else if constexpr (BR == kBrChol) {
+    // potrf of the 1 x 1 Quu_reg (ilqr.py:595)
+    if (!(Quug > T(0)) || !is_finite(Quug)) st = PDDP_BWD_NOT_PD;
+    sK = n4::div_<true>(T(1), Quug);             // potrs (ilqr.py:597)
+    kt = -(sK * Qu);
+  } else {
+    static_assert(BR == kBrCholBox, "");
+    constexpr bool F32 = std::is_same<T, float>::value;
+    const int l = lane & 15;
+    const unsigned long long lane_bit = 1ull << lane;
+    const unsigned long long alive_m = __ballot(alive);
+    unsigned long long oddm;
+    kt = T(0);
+    sK = T(0);
+    if constexpr (F32) {
+      // the lean BoxQP of the benched sweep on Q = Quu_reg (no back-tracking:
+      // for one action it cannot change the answer, see QpLean1), and behind
+      // ONE class test the closed form for what it does not cover - a Quu_reg
+      // that is not positive and finite, a non-finite Qu
+      QpLean1 ql;
+      ql.d_lo = lo_b - kprev;
+      ql.d_hi = kprev - hi_b;
+      ql.xs = __builtin_amdgcn_fmed3f(kprev, lo_b, hi_b);
+      ql.Q = Quug;
+      ql.solve(f32x2{Quug, Qu}, f32x2{lo_b, hi_b});
+      kt = ql.x;
+      sK = __int_as_float(splat(ql.free_w) & __float_as_int(ql.inv));
+      const T chk = fma_(Qu, T(0), Quug);
+      unsigned long long regular;
+      asm("v_cmp_class_f32 %0, %1, %2" : "=s"(regular) : "v"(chk), "v"(0x180));
+      oddm = ~regular & alive_m;
+    } else {
+      oddm = alive_m;  // float64: the closed form (IEEE division) for every row
+    }
+    bool fail = false;
+    if (__builtin_expect(oddm != 0, F32 ? 0 : 1)) {
+      const bool take = (oddm & lane_bit) != 0;
+      // the other rows get a trivial QP: their closed form never asks for
+      // the loop
+      n4::QpClosed<T, true> qc;
+      qc.solve(take ? kprev : T(0), take ? Quug : T(1), take ? Qu : T(0), lo_b,
+               hi_b);
+      T kx = qc.x;
+      bool Kzero = !qc.free_;
+      fail = qc.fail & take;
+      const bool slow = qc.slow & take;
+      if (__builtin_expect(__any(slow), 0)) {
+        // rare: the reference's loop, one slow trajectory at a time on the
+        // whole wavefront
+        unsigned long long todo = __ballot(slow && l == 0);
+        while (todo != 0) {
+          const int src = __builtin_ctzll(todo);
+          todo &= todo - 1;
+          const n4::SlowQpOut<T> o = n4q::boxqp1_wave<T, true>(
+              __shfl(kprev, src), __shfl(Quug, src), __shfl(Qu, src),
+              __shfl(lo_b, src), __shfl(hi_b, src), ls_table<T>(), lane);
+          const bool mine = (lane >> 4) == (src >> 4);
+          kx = mine ? o.x : kx;
+          Kzero = mine ? ((o.result_free & 1) == 0) : Kzero;
+          fail = mine ? (o.result_free < 2) : fail;
+        }
+      }
+      kt = take ? kx : kt;
+      sK = take ? (Kzero ? T(0) : qc.inv) : sK;
+    }
+    if (fail) st = PDDP_BWD_BOXQP_FAILED;        // ilqr.py:608-610
+  }
+  return st;
+}
+
 #ifdef PDDP_ELEM_MARKS
 // time marks of wavefront 0 of workgroup 0: begin, first step, last step done,
 // end (tools/elem_sweep_marks.py)
@@ -515,7 +619,7 @@ constexpr int kCarryF = kTrajW * kCarryRows * kCarryW;  // 340 floats
 constexpr int kGainL = kGain + 1;
 constexpr int round_gains_floats(int N) { return (kTrajW * N * kGainL + 3) & ~3; }
 
-template <typename T, unsigned QM, bool OVL, bool ROUND>
+template <typename T, unsigned QM, bool OVL, bool ROUND, int BR = kBrEigBox>
 PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
                               const ProblemT<T>& prob, unsigned char* smem_raw,
                               RoundOut& ro,
@@ -533,6 +637,9 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
   using V2 = typename Vec<T>::v2;
   constexpr int MODEL = PDDP_MODEL_CARTPOLE;
   constexpr RecLayout lay(4, 1);
+  // (unbounded: no clamp of the nominal action in the records, and the image
+  // words {u_min - U, u_max - U} are zeros nobody reads)
+  constexpr bool BOUNDED = br_bounded(BR), CHOL = br_chol(BR);
   const int kPairLds = OVL ? kPairLdsOvl + (ROUND ? round_gains_floats(a.N) +
                                                         (carry >= 0 ? kCarryF : 0)
                                                   : 0)
@@ -564,7 +671,8 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
   PDDP_EM_MARK(0);
   PDDP_TL(0);
   PDDP_TL_HW(10);
-  const T umin = a.u_min[0], umax = a.u_max[0];
+  T umin = T(0), umax = T(0);
+  if constexpr (BOUNDED) { umin = a.u_min[0]; umax = a.u_max[0]; }
   const int rbase = row * kRowStride;
 
   // =============================================================== generator
@@ -635,7 +743,7 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
     if (jb + 1 < nblk) request(jb + 1);
     const int tau = N - 1 - kBlk * jb - l;
     T w[lay.stride];
-    const T lc = record_of<T, MODEL, QM>(prob, z, &u, false, true, a.u_min,
+    const T lc = record_of<T, MODEL, QM>(prob, z, &u, false, BOUNDED, a.u_min,
                                          a.u_max, w);
     T* dst = buf + rbase + l * kImg;
 #pragma unroll
@@ -660,7 +768,8 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
           V4{w[lay.oLzz + 4 * r], w[lay.oLzz + 4 * r + 1],
                 w[lay.oLzz + 4 * r + 2], w[lay.oLzz + 4 * r + 3]};
     *reinterpret_cast<V4*>(dst + 48) =
-        V4{w[lay.oLuu], w[lay.oLu], umin - w[lay.oU], umax - w[lay.oU]};
+        V4{w[lay.oLuu], w[lay.oLu], BOUNDED ? umin - w[lay.oU] : T(0),
+           BOUNDED ? umax - w[lay.oU] : T(0)};
     if (tau >= 0) {
       if (counted) gen.L[(size_t)bc * (size_t)(N + 1) + tau] = lc;
       Jacc += lc;
@@ -691,7 +800,9 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
     const T* sg = ib + l * kImg + rbase;
     const V4 Kv = *reinterpret_cast<const V4*>(sg);
     const T kv = sg[4];
-    if (exists && l < cnt) {
+    // (the branches of cartpole_branches.hip leave a masked trajectory's gains
+    // alone; the bounded eig-clamp kernels store what its lanes computed)
+    if ((BR == kBrEigBox ? exists : counted) && l < cnt) {
       T* g = a.gains + ((size_t)bc * (size_t)N + (size_t)(t_top - l)) * kGain;
       g[0] = kv; g[1] = Kv[0]; g[2] = Kv[1]; g[3] = Kv[2]; g[4] = Kv[3];
       if constexpr (ROUND) {
@@ -811,6 +922,60 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
     // the BoxQP (left to itself the scheduler sinks them to their use)
     const T QzzT = bperm(tr_addr, q.Qzz);
     const T Quzc = bperm(tr_addr, q.Quzr);
+    if constexpr (BR != kBrEigBox) {
+      // ---- the other gain branches (branch_gains above)
+      T Quug = Quu, Rr = q.Quzr, Rc = Quzc;
+      if constexpr (CHOL) {
+        // the second Q() with V + reg I (ilqr.py:590-592): Quu_reg = Quu +
+        // reg f.f, Quz_reg = Quz + reg F^T f.  f.f and F^T f are the record's
+        // alone - formed here, off the chain through V, from words the lane
+        // holds anyway (Fs[d] = F[(i+d)%4][i], f by row and by column): seven
+        // instructions, and the image stays 52 words (N <= 127 still fits)
+        const T fr = w.Ti[0], fc = w.Tj[0];
+        const T ff = n4::dot_cols(fc, fc);
+        T g = fr * w.Fs[0];
+        g = fma_(n4::from_row_plus<1>(fr), w.Fs[1], g);
+        g = fma_(n4::from_row_plus<2>(fr), w.Fs[2], g);
+        g = fma_(n4::from_row_plus<3>(fr), w.Fs[3], g);
+        Quug = fma_(reg, ff, Quu);
+        Rr = fma_(reg, g, q.Quzr);
+        Rc = bperm(tr_addr, Rr);
+      }
+      const bool alive = counted & (status == PDDP_BWD_OK);
+      T kt, sK;
+      int st = branch_gains<T, BR>(kprev, Quu, Qu, Quug, reg, w.Sc[2], w.Sc[3],
+                                   alive, lane, kt, sK);
+      const T Ks = -(sK * Rc);  // K[j] in lane (i, j)
+      if constexpr (BR == kBrEig) {
+        // NaN anywhere in K raises too (ilqr.py:639-640)
+        const bool nanK = n4::sum_cols((Ks != Ks) ? T(1) : T(0)) != T(0);
+        if (nanK && st == PDDP_BWD_OK) st = PDDP_BWD_NAN;
+      }
+      status = (alive & (st != PDDP_BWD_OK)) ? st : status;
+      ib[s * kImg + ostage] = (l < 4) ? Ks : kt;
+      kprev = kt;
+      // ---- value update with the UNregularised Quu, Quz (ilqr.py:619-625,
+      // :664-672) and K = -s r, r = Quz_reg, q = Quz:
+      //   V'   = sym(Qzz) + s^2 Quu r r^T - s (r q^T + q r^T)
+      //   V_z' = Qz - s (Qu + Quu k) r + k q
+      // (r == q without V_zz regularisation: the rank-one form.)  Every
+      // product rounded on its own, sums of commuting pairs: lane (i, j) and
+      // lane (j, i) form the same bits
+      const T sym = n4::opaque(q.Qzz + QzzT);
+      if constexpr (CHOL) {
+        const T wr = -(sK * fma_(Quu, kt, Qu));
+        const T c2 = mul_nc(mul_nc(sK, sK), Quu);
+        const T X = mul_nc(Rr, Quzc) + mul_nc(q.Quzr, Rc);
+        V = fma_(T(0.5), sym, fma_(c2, mul_nc(Rr, Rc), -mul_nc(sK, X)));
+        vc = fma_(kt, Quzc, fma_(wr, Rc, q.Qzc));
+      } else {
+        T c, wv;
+        n4q::rank_one_coeffs(kt, sK, Quu, Qu, c, wv);
+        V = fma_(T(0.5), sym, mul_nc(c, mul_nc(q.Quzr, Quzc)));
+        vc = fma_(wv, Quzc, q.Qzc);
+      }
+      return;
+    }
     __builtin_amdgcn_sched_barrier(0);
     // ---- gains: the scalar BoxQP of the step (elem_gains above)
     const ElemGains<T> g_ = elem_gains<T>(kprev, Quu, Qu, reg, w.Sc[2], w.Sc[3],
@@ -908,7 +1073,7 @@ riccati_n4_elem_kernel(RiccatiArgs<float> a, GenArgs<float> gen,
   RoundOut ro;
   elem_sweep_body<float, QM, OVL, false>(a, gen, prob, smem_raw, ro);
 }
-// float64 (cartpole, bounded eig-clamp branch): the inline form
+// float64 (cartpole): the inline form
 template <unsigned QM>
 __global__ __launch_bounds__(kWaves * kWave) void riccati_n4_elem_f64_kernel(
     RiccatiArgs<double> a, GenArgs<double> gen, ProblemT<double> prob) {
@@ -927,12 +1092,31 @@ inline int& nominal_kernel_choice() {
   return choice;
 }
 
+// The gain branch of a sweep's arguments (n4e::kBr*), -1: not served (one
+// bound without the other).
+inline int n4_branch_of(const void* u_min, const void* u_max, int branch) {
+  if ((u_min == nullptr) != (u_max == nullptr)) return -1;
+  const bool bounded = u_min != nullptr;
+  if (branch == PDDP_BRANCH_EIG) return bounded ? n4e::kBrEigBox : n4e::kBrEig;
+  if (branch == PDDP_BRANCH_CHOLESKY)
+    return bounded ? n4e::kBrCholBox : n4e::kBrChol;
+  return -1;
+}
+// cartpole_branches.hip: the kernels of every branch but kBrEigBox (a
+// translation unit of their own; the benched kernels stay as they are)
+int launch_n4_branches(const pddp_problem& p, const RiccatiArgs<float>& a,
+                       const n4d::GenArgs<float>& gen, hipStream_t st,
+                       bool ovl, int br);
+int launch_n4_branches_f64(const pddp_problem& p, const RiccatiArgs<double>& a,
+                           const n4d::GenArgs<double>& gen, hipStream_t st,
+                           int br);
+
 static int launch_n4_elem(const pddp_problem& p, const RiccatiArgs<float>& a,
                           const n4d::GenArgs<float>& gen, hipStream_t st,
                           int overlap = -1) {
+  const int br = n4_branch_of(a.u_min, a.u_max, a.branch);
   if (p.model != PDDP_MODEL_CARTPOLE ||
-      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || a.u_min == nullptr ||
-      a.u_max == nullptr || a.branch != PDDP_BRANCH_EIG || a.N < 1)
+      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || br < 0 || a.N < 1)
     return PDDP_E_UNSUPPORTED;
   const ProblemT<float> P = convert_problem<float>(p);
   constexpr int kPer = n4e::kWaves * n4e::kTrajW;  // trajectories / workgroup
@@ -941,6 +1125,7 @@ static int launch_n4_elem(const pddp_problem& p, const RiccatiArgs<float>& a,
   // the batch; beyond that the SIMDs have other wavefronts to issue from and
   // the smaller LDS footprint (more workgroups per CU) counts
   const bool ovl = overlap < 0 ? grid.x <= 256u : overlap != 0;
+  if (br != n4e::kBrEigBox) return launch_n4_branches(p, a, gen, st, ovl, br);
   constexpr unsigned kSparse = 0b11001u;  // CartpoleCost: {x, sin, cos}
   const bool sparse =
       (live_mask(p.Q, ModelDims<PDDP_MODEL_CARTPOLE>::na) & ~kSparse) == 0;
@@ -966,10 +1151,11 @@ static int launch_n4_elem(const pddp_problem& p, const RiccatiArgs<float>& a,
 static int launch_n4_elem_f64(const pddp_problem& p,
                               const RiccatiArgs<double>& a,
                               const n4d::GenArgs<double>& gen, hipStream_t st) {
+  const int br = n4_branch_of(a.u_min, a.u_max, a.branch);
   if (p.model != PDDP_MODEL_CARTPOLE ||
-      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || a.u_min == nullptr ||
-      a.u_max == nullptr || a.branch != PDDP_BRANCH_EIG || a.N < 1)
+      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || br < 0 || a.N < 1)
     return PDDP_E_UNSUPPORTED;
+  if (br != n4e::kBrEigBox) return launch_n4_branches_f64(p, a, gen, st, br);
   const ProblemT<double> P = convert_problem<double>(p);
   constexpr int kPer = n4e::kWaves * n4e::kTrajW;
   const dim3 grid((a.B + kPer - 1) / kPer);

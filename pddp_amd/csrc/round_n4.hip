@@ -1,5 +1,8 @@
 // round_n4.hip - ONE launch for a whole round of the cartpole f32 path
-// (BASELINE.json configs[1]): the backward sweep from the nominal
+// (BASELINE.json configs[1]; this file: the kernels of the bounded eig-clamp
+// branch and the entry point - the other three gain branches run the same
+// body, round_n4_body.hpp, in the kernels of cartpole_branches.hip): the
+// backward sweep from the nominal
 // (riccati_n4_elem.hpp; ilqr.py:489-674 with the records of :393-486 evaluated
 // in place) and then, in the SAME wavefronts for the same four trajectories,
 // the batched line search, argmin, accept / regularisation schedule and the
@@ -31,8 +34,7 @@
 // three places, each an A/B-measured cut: the nominal row is
 // read with one 16-byte and three 8-byte LDS reads, one LDS wait per step, and
 // between the rounds of a launch the nominal's last rows stay in LDS.
-#include "riccati_n4_elem.hpp"
-#include "line_search_lds.hpp"
+#include "round_n4_body.hpp"
 
 namespace pddp {
 
@@ -41,66 +43,8 @@ __global__ __launch_bounds__(2 * n4e::kWaves * kWave) void round_n4_kernel(
     RiccatiArgs<float> a, n4d::GenArgs<float> gen, ProblemT<float> prob,
     LineSearchArgs<float> ls, AcceptArgs<float> ac, float* scratch,
     int rounds, long long* phase_ticks, int use_carry) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  // (bench.py's roofline leg: what share of the launch is sweep - rocprofv3
-  // sees one kernel.  Wavefront 0 of the workgroup reads the chip's 100 MHz
-  // clock around its phases and adds the differences up; NULL: nothing)
-  const bool timed = phase_ticks != nullptr && threadIdx.x == 0;
-  long long t_sweep = 0, t_search = 0;
-  // `rounds` attempts of every trajectory, back to back: trajectories are
-  // independent (ilqr.py:298-314 is a loop over ONE trajectory's attempts), a
-  // workgroup owns its sixteen for the whole launch, and everything a round
-  // hands to the next - nominal, regularisation state, masks, costs - was
-  // written by this workgroup: a workgroup-scope fence and a barrier, no
-  // launch boundary.  (A trajectory that has left the fit is skipped, as by
-  // the next launch.)
-  for (int r = 0;; ++r) {
-    // (a zero the compiler cannot see through, added to the horizon: address
-    // arithmetic and everything else that depends on it stays INSIDE the
-    // round - hoisted out of this loop, both phases' invariants live across
-    // both phases: 255 VGPRs and 53 spilled against 102)
-    int z = 0;
-    unsigned tid = threadIdx.x;
-    if constexpr (MULTI) {
-      asm volatile("s_mov_b32 %0, 0" : "=s"(z));
-      asm volatile("" : "+v"(tid));  // (likewise: what the lane id feeds)
-    }
-    RiccatiArgs<float> a_r = a;
-    a_r.N += z;
-    LineSearchArgs<float> ls_r = ls;
-    ls_r.N += z;
-    AcceptArgs<float> ac_r = ac;
-    ac_r.N += z;
-    n4e::RoundOut ro;
-    const long long t0 = timed ? wall_clock64() : 0;
-    // (a pair without a live trajectory leaves here, both wavefronts alike -
-    // it has none in any later round either; s_barrier does not wait for
-    // wavefronts that have ended)
-    // (several rounds per launch: the nominal's last rows ride in LDS)
-    const int carry = MULTI && use_carry ? (r == 0 ? 1 : 0) : -1;
-    if (!n4e::elem_sweep_body<float, QM, true, true>(a_r, gen, prob, smem_raw,
-                                                     ro, tid, carry))
-      break;
-    const long long t1 = timed ? wall_clock64() : 0;
-    const PreStaged<float> pre{ro.Zs, ro.Us,      ro.Gs,
-                               ro.status, ro.J_opt, ro.carry_rows};
-    line_search_lds_body<float, PDDP_MODEL_CARTPOLE, true, n4e::kWaves, 2, QM,
-                         false, true>(prob, ls_r, ac_r, scratch, nullptr,
-                                      smem_raw, pre, tid);
-    if (timed) {
-      t_sweep += t1 - t0;
-      t_search += wall_clock64() - t1;
-    }
-    if (!MULTI || r + 1 >= rounds) break;
-    // the round's writes (global: nominal, mu, delta, J_opt, masks; LDS: read
-    // to the end by the tail) before the next round's reads and LDS writes
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __syncthreads();
-  }
-  if (timed) {
-    phase_ticks[2 * blockIdx.x] += t_sweep;
-    phase_ticks[2 * blockIdx.x + 1] += t_search;
-  }
+  round_n4_body<QM, MULTI, n4e::kBrEigBox>(a, gen, prob, ls, ac, scratch,
+                                           rounds, phase_ticks, use_carry);
 }
 
 static int launch_round_n4(const pddp_problem& p, const RiccatiArgs<float>& a,
@@ -109,11 +53,15 @@ static int launch_round_n4(const pddp_problem& p, const RiccatiArgs<float>& a,
                            const AcceptArgs<float>& ac, float* scratch,
                            int rounds, long long* phase_ticks,
                            hipStream_t st) {
+  const int br = n4_branch_of(a.u_min, a.u_max, a.branch);
   if (p.model != PDDP_MODEL_CARTPOLE ||
-      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || a.u_min == nullptr ||
-      a.u_max == nullptr || a.branch != PDDP_BRANCH_EIG || a.N < 1 ||
+      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || br < 0 || a.N < 1 ||
       a.N + 1 > 128 || ls.A > 16 || rounds < 1)
     return PDDP_E_UNSUPPORTED;
+  // (the other gain branches: kernels of their own, cartpole_branches.hip)
+  if (br != n4e::kBrEigBox)
+    return launch_round_n4_branches(p, a, gen, ls, ac, scratch, rounds,
+                                    phase_ticks, st, br);
   constexpr int kPer = n4e::kWaves * n4e::kTrajW;  // trajectories / workgroup
   const dim3 grid((a.B + kPer - 1) / kPer);
   // one workgroup per CU (142 KB of LDS at N = 100): beyond 256 workgroups
@@ -121,12 +69,9 @@ static int launch_round_n4(const pddp_problem& p, const RiccatiArgs<float>& a,
   // faster round
   if (grid.x > 256u) return PDDP_E_UNSUPPORTED;
   // (several rounds per launch: the carried rows, where they fit - N <= 123)
-  const size_t lds0 = (size_t)n4e::kWaves * sizeof(float) *
-                      (n4e::kPairLdsOvl + n4e::round_gains_floats(a.N));
-  const size_t lds1 = lds0 + (size_t)n4e::kWaves * sizeof(float) * n4e::kCarryF;
-  const int use_carry = rounds > 1 && lds1 <= 159 * 1024;
-  const size_t lds = use_carry ? lds1 : lds0;
-  if (lds > 159 * 1024) return PDDP_E_UNSUPPORTED;
+  int use_carry;
+  const size_t lds = round_n4_lds(a.N, rounds, use_carry);
+  if (lds == 0) return PDDP_E_UNSUPPORTED;
   const ProblemT<float> P = convert_problem<float>(p);
   constexpr unsigned kSparse = 0b11001u;  // CartpoleCost: {x, sin, cos}
   constexpr unsigned kFull = kFullMask<PDDP_MODEL_CARTPOLE>;
