@@ -781,10 +781,16 @@ int pddp_qr_cost_derivs_f64(const pddp_qr_cost_f64* cost, void* stream);
  * encoding: StateEncoding 1 (upper-triangular Cholesky, n = E + E(E+1)/2), 2
  * (variance), 3 (standard deviation), 4 (mean only); 0 (full covariance):
  * PDDP_E_UNSUPPORTED.  Built for (state_size, features + actions) = (2, 4),
- * (4, 6), (6, 9) - pendulum, cartpole, double cartpole; n + m <= 64; the
- * training set must fit the workgroup's 160 KB of LDS next to the inverses
- * (double cartpole: M <= 1278 in f32 / 596 in f64 without the Jacobian, 318 /
- * 74 with; the smaller systems several times that; PDDP_E_UNSUPPORTED beyond).
+ * (4, 6), (6, 9) - pendulum, cartpole, double cartpole; n + m <= 64.  Any
+ * number of training points M, in one of two forms chosen by the entry points
+ * themselves: RESIDENT while every per-point table of a row fits the
+ * workgroup's 160 KB of LDS next to the inverses (double cartpole: M <= 1278
+ * in f32 / 596 in f64 without the Jacobian, 890 / 208 with; the smaller
+ * systems several times that), CHUNKED beyond - the per-point tables hold a
+ * chunk of C points, the rows go out in consecutive launches on the stream
+ * (each sized to a fraction of a second by a cost model proportional to M^2;
+ * stream-ordered and capturable like one launch, same outputs).
+ * PDDP_E_UNSUPPORTED: an unbuilt (state_size, d), encoding 0, n + m > 64.
  * All arrays on the device. */
 typedef struct pddp_gp_model {
   int state_size;        /* E: one GP per state increment */
@@ -811,6 +817,26 @@ typedef struct pddp_gp_model {
  * (state_size, d) pair is not built.  Host function. */
 long long pddp_gp_step_lds_bytes(int state_size, int d, int M, int inputs, int jacobian,
                                  int element_size);
+/* The form pddp_gp_step_* / _masked_* / (jacobian = 0) pddp_gp_rollout_* use for
+ * these sizes: 0 resident (pddp_gp_step_lds_bytes <= 160 KB), 1 chunked, -1
+ * not covered; and the points per chunk C of that launch (M for the resident
+ * form, -1 when not covered).  pddp_gp_step_chunked_lds_bytes: the chunked
+ * form's LDS at chunk C (-1: pair not built).  Host functions; they reflect
+ * pddp_gp_step_force_chunk. */
+int pddp_gp_step_form(int state_size, int d, int M, int inputs, int jacobian, int element_size);
+int pddp_gp_step_chunk(int state_size, int d, int M, int inputs, int jacobian, int element_size);
+long long pddp_gp_step_chunked_lds_bytes(int state_size, int d, int C, int inputs, int jacobian,
+                                         int element_size);
+/* For tests: C > 0 makes every later launch of this process use the chunked
+ * form with chunks of (at most) C points (rounded up to an even number, and
+ * never more than the LDS or M allow) also where the resident form fits; 0:
+ * automatic.  pddp_gp_step_force_rows_per_launch: rows > 0 replaces the cost
+ * model's rows per launch of the chunked form; 0: automatic.  Both return the
+ * previous value (>= 0, never an error code; negative arguments count as 0).
+ * Process-wide, not synchronised with launches in flight on other threads; a
+ * hipGraph captured before a change keeps the form it was captured with. */
+int pddp_gp_step_force_chunk(int C);
+int pddp_gp_step_force_rows_per_launch(int rows);
 int pddp_gp_step_f32(const pddp_gp_model* gp, int R, const float* z, const float* u,
                      float* z_next, float* Fz, float* Fu, void* stream);
 int pddp_gp_step_f64(const pddp_gp_model* gp, int R, const double* z, const double* u,

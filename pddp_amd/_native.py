@@ -110,6 +110,11 @@ _SIGS = {
     "pddp_gp_step": [_P, c_int, _P, _P, _P, _P, _P, _P],
     "pddp_gp_step_masked": [_P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P],
     "pddp_gp_step_lds_bytes": [c_int] * 6,
+    "pddp_gp_step_form": [c_int] * 6,
+    "pddp_gp_step_chunk": [c_int] * 6,
+    "pddp_gp_step_chunked_lds_bytes": [c_int] * 6,
+    "pddp_gp_step_force_chunk": [c_int],
+    "pddp_gp_step_force_rows_per_launch": [c_int],
     "pddp_gp_rollout": [_P, _P, _P],
     "pddp_event_create": [_P],
     "pddp_event_record": [_P, _P],
@@ -160,6 +165,7 @@ def lib():
                 fn.restype = c_int
         l.pddp_hip_arch.restype = ctypes.c_char_p
         l.pddp_gp_step_lds_bytes.restype = ctypes.c_longlong
+        l.pddp_gp_step_chunked_lds_bytes.restype = ctypes.c_longlong
         _lib = l
     return _lib
 

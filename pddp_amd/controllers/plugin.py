@@ -199,11 +199,13 @@ class TorchProblem(object):
     # -- GP plugin: csrc/gp_step.hip ----------------------------------------------
     def _gp_native_ok(self, s):
         mo = self.model
-        if not (hasattr(mo, "native_step") and hasattr(mo, "native_ok")):
+        if not (hasattr(mo, "native_step") and hasattr(mo, "native_form")):
             return False
         if not getattr(self, "use_native_gp", True) or self.model_opts:
             return False
-        return bool(mo.native_ok(s.Z[:, 0], self.encoding, jacobian=True))
+        # (either form of the kernel: resident or chunked)
+        return mo.native_form(s.Z[:, 0], self.encoding,
+                              jacobian=True) is not None
 
     @torch.no_grad()
     def _dyn_derivs_gp(self, s, F_z, F_u, mask=None):

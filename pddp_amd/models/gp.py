@@ -32,8 +32,11 @@ cov[x, sin a_k] = S_x[:, k] E[cos a_k]).  The module below is batched torch
 (einsum / solve / det) and differentiable: the definition, and the checker of
 the HIP kernel `pddp_gp_step_f32 / _f64` (csrc/gp_step.hip),
 which computes the same step and its Jacobian with respect to (z, u) in one
-launch for any number of rows.  `forward` goes through the kernel whenever
-nobody can ask autograd for gradients (`native_ok`, `native_step`); the
+launch for any number of rows and any number of training points: with every
+per-point table of a row resident in the workgroup's LDS while that fits, in
+chunks of the training set beyond (`native_form`).  `forward` goes through the
+kernel whenever nobody can ask autograd for gradients (`native_form`,
+`native_step`); the
 controllers' plugin path takes F_z, F_u of a whole nominal from one launch
 (controllers/plugin.py `_dyn_derivs_gp`) and runs the line search on it
 (`_line_search_gp`).
@@ -47,6 +50,34 @@ from ..utils.angular import augment_moments, augment_state
 from ..utils.classproperty import classproperty
 from ..utils.encoding import StateEncoding, decode_covar, decode_mean, encode
 from ..utils.linalg import cholesky_solve
+
+
+class _SolveSymmetric(torch.autograd.Function):
+    """`torch.linalg.solve(A, B)` for symmetric A (broadcast over leading
+    dimensions) with the backward pass written out: g_B = A^-1 g_X as a solve
+    on contiguous operands, g_A = -g_B X^T.  The forward pass is the library's
+    own, bit for bit.  Why: autograd's own backward of linalg.solve (a solve
+    with the adjoint VIEW of A) ends in "HIP error: unspecified launch failure"
+    on the device for the cartpole's shapes (E = 4, d = 6) from M = 300
+    right-hand sides on (PyTorch 2.10 / ROCm 7: the third defect of that
+    library path, see `condition`), which took the autograd path of the
+    derivative rollout down at the data-set sizes the outer loop produces.
+    Differentiable again (the backward pass is torch ops)."""
+
+    @staticmethod
+    def forward(ctx, A, B):
+        X = torch.linalg.solve(A, B)
+        ctx.save_for_backward(A, X)
+        ctx.b_shape = B.shape
+        return X
+
+    @staticmethod
+    def backward(ctx, gX):
+        A, X = ctx.saved_tensors
+        # (A is symmetric: A^-T = A^-1)
+        gB = _SolveSymmetric.apply(A.contiguous(), gX.contiguous())
+        gA = -(gB @ X.transpose(-1, -2))
+        return gA.sum_to_size(A.shape), gB.sum_to_size(ctx.b_shape)
 
 
 def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
@@ -217,7 +248,7 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
             # ---- mean and input-output covariance
             SL = S.unsqueeze(-3) + torch.diag_embed(ell2)     # [..., E, d, d]
             # (S + L)^-1 nu^T  -> [..., E, d, M]
-            sol = torch.linalg.solve(SL, nu.transpose(-1, -2).unsqueeze(-3))
+            sol = _SolveSymmetric.apply(SL, nu.transpose(-1, -2).unsqueeze(-3))
             quad = (nu.transpose(-1, -2).unsqueeze(-3) * sol).sum(-2)  # [.., E, M]
             det = torch.linalg.det(S.unsqueeze(-3) / ell2.unsqueeze(-2) + eye)
             q = sf2.unsqueeze(-1) * det.unsqueeze(-1).rsqrt() * \
@@ -265,29 +296,54 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
         # -- the HIP kernel (csrc/gp_step.hip) ------------------------------------
         use_native = True
 
-        def native_ok(self, z, encoding, jacobian=False):
-            """True when `pddp_gp_step_*` covers this call: device tensors of
-            f32 / f64, an encoding other than the full covariance matrix, one of
-            the built (state_size, feature + action size) pairs, a training set
-            that fits the workgroup's LDS."""
+        def _native_inputs(self, z, encoding):
+            """n + m when `pddp_gp_step_*` takes this call whatever the size
+            of the training set (device tensors of f32 / f64, an encoding
+            other than the full covariance matrix), else None."""
             if not (self.use_native and self.fitted and z.is_cuda):
-                return False
+                return None
             if z.dtype not in (torch.float32, torch.float64):
-                return False
+                return None
             if int(encoding) not in (1, 2, 3, 4):
-                return False
+                return None
             if len(ai) > 4 or len(ni) > 8:
-                return False
+                return None
             E = state_size
             n = {1: E + E * (E + 1) // 2, 2: 2 * E, 3: 2 * E, 4: E}[
                 int(encoding)]
             if n + action_size > 64:
+                return None
+            return n + action_size
+
+        def native_ok(self, z, encoding, jacobian=False):
+            """True when the RESIDENT form of `pddp_gp_step_*` covers this
+            call: device tensors of f32 / f64, an encoding other than the full
+            covariance matrix, one of the built (state_size, feature + action
+            size) pairs, a training set whose per-point tables fit the
+            workgroup's LDS.  Whether the kernel covers the call at all:
+            `native_form`."""
+            inputs = self._native_inputs(z, encoding)
+            if inputs is None:
                 return False
             from .. import _native
             fn = _native.lib().pddp_gp_step_lds_bytes
-            need = fn(E, d_in, int(self.Xt.shape[0]), n + action_size,
+            need = fn(state_size, d_in, int(self.Xt.shape[0]), inputs,
                       int(bool(jacobian)), z.element_size())
             return 0 <= need <= 160 * 1024
+
+        def native_form(self, z, encoding, jacobian=False):
+            """The form of `pddp_gp_step_*` this call runs on: "resident"
+            (every per-point table of a row in LDS), "chunked" (the training
+            set in chunks: any size) or None (the kernel does not cover it:
+            `native_ok`'s preconditions without the one on the size)."""
+            inputs = self._native_inputs(z, encoding)
+            if inputs is None:
+                return None
+            from .. import _native
+            form = _native.lib().pddp_gp_step_form(
+                state_size, d_in, int(self.Xt.shape[0]), inputs,
+                int(bool(jacobian)), z.element_size())
+            return {0: "resident", 1: "chunked"}.get(form)
 
         def _native_model(self, dtype, device, encoding):
             """The kernel's view of the conditioned GPs (cached per dtype; the
@@ -396,7 +452,7 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
             # nobody can ask autograd to differentiate this call: the kernel
             if z.dim() == 2 and not (torch.is_grad_enabled() and (
                     z.requires_grad or u.requires_grad)) and \
-                    self.native_ok(z, encoding):
+                    self.native_form(z, encoding) is not None:
                 out = self.native_step(z, u, encoding)
                 return out[0] if single else out
             D = state_size

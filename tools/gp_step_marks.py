@@ -1,5 +1,7 @@
 """Phase times of pddp_gp_step_* from a debug build (-DPDDP_GP_MARKS: rebuilds
-csrc/gp_step.hip into a private library): s_memtime of wavefront 0 at the phase
+csrc/gp_step.hip and gp_step_chunked.hip into a private library; the marks
+read here are the resident form's, the chunked unit keeps its own behind
+pddp_debug_gp_marks_chunked): s_memtime of wavefront 0 at the phase
 boundaries A0 | A1 | A2 | B | C | A3 | end, rows 0-7 of a launch."""
 import ctypes
 import os
@@ -16,7 +18,8 @@ out = "/tmp/libpddp_gp_marks.so"
 subprocess.check_call(
     ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
      "-fPIC", "-shared", "-ffp-contract=fast", "-fno-fast-math",
-     "-DPDDP_GP_MARKS", os.path.join(src, "gp_step.hip"), "-o", out])
+     "-DPDDP_GP_MARKS", os.path.join(src, "gp_step.hip"),
+     os.path.join(src, "gp_step_chunked.hip"), "-o", out])
 from pddp_amd import _native  # noqa: E402
 from pddp_amd import StateEncoding  # noqa: E402
 from gp_native_check import make, rows  # noqa: E402
@@ -32,7 +35,7 @@ for dtype in (torch.float32, torch.float64):
     z, u = rows("double_cartpole", 2048, enc, dtype)
     g = model._native_model(dtype, z.device, enc)
     for jac in (False, True):
-        if not model.native_ok(z, enc, jac):
+        if model.native_form(z, enc, jac) is None:
             continue
         o = torch.empty_like(z)
         Fz = torch.empty(2048, 27, 27, dtype=dtype, device="cuda") if jac else None

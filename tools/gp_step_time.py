@@ -18,7 +18,7 @@ for dtype in (torch.float32, torch.float64):
         enc = StateEncoding.DEFAULT
         for jac in (False, True):
             z, u = rows("double_cartpole", R, enc, dtype)
-            if not model.native_ok(z, enc, jac):
+            if model.native_form(z, enc, jac) is None:
                 print("M=%d %s jac=%s: not covered" % (M, dtype, jac))
                 continue
             for _ in range(20):  # (the clocks come down while the host
