@@ -13,8 +13,36 @@ trajectory at once:
 
 with per-trajectory masks instead of Python control flow, so a round is a
 fixed launch sequence with no host synchronisation.
+
+The launches of a round are decided in one place: `ILQRSolver._plan()` names
+the sequence a round tries FIRST, round() demotes it when an entry point
+answers PDDP_E_UNSUPPORTED, and the `_*_done()` helpers note what a
+launch did in the plan's inputs, the tri-states `_one_launch`, `_nominal_sweep`
+(None at first only where that sweep applies and pays) and `_fused`: None
+untried / allowed, False forbidden or found unsupported, True has applied.
+Assign one between two rounds to force a path.  "nominal" below: the variant
+is 0 and neither `_nominal_sweep` nor `_fused` is False.
+
+    sequence          launches                        tried first when
+    ----------------  ------------------------------  ------------------------
+    one_launch        pddp_round_nominal_f32          nominal, `_one_launch`
+                                                      is not False, no
+                                                      search_events
+    nominal+fused     pddp_sweep_nominal,             nominal (and what a
+                      pddp_search_accept, L = NULL    refused one_launch
+                                                      becomes)
+    nominal+separate  pddp_sweep_nominal,             never: a nominal+fused
+                      line_search, accept; records    whose search was refused
+                      by derivs from then on          (> 16 step sizes)
+    records+fused     [sync_records] [derivs]         not nominal (or sweep
+                      backward, pddp_search_accept    refused); no plugin,
+                                                      `_fused` is not False
+    records+separate  derivs, backward, line_search,  plugin, `_fused` is
+                      accept                          False, or search refused
 """
 import ctypes
+import functools
+import types
 
 import torch
 
@@ -22,13 +50,13 @@ from .. import _native
 from ..utils.encoding import StateEncoding
 
 BRANCH_EIG, BRANCH_CHOLESKY = 0, 1
+ONE_LAUNCH, NOMINAL_FUSED, RECORDS_FUSED, RECORDS_SEPARATE = (
+    "one_launch", "nominal+fused", "records+fused", "records+separate")
 
 
 def _on_device(fn):
     """The C ABI takes a stream handle and launches on the CURRENT device: a
     solver that lives on another GPU makes its device current for the call."""
-    import functools
-
     @functools.wraps(fn)
     def wrapped(self, *args, **kwargs):
         if torch.cuda.current_device() == self.device.index:
@@ -117,13 +145,13 @@ class ILQRSolver(object):
         self.n_live = torch.zeros(256, **i32)
         self._graph = None  # (key, graph of a round [, round without derivs])
         self._rollout_graph = None
-        self._model_gen = None  # model generation the plugin graphs captured
+        self._graph_nominal = False  # the captured round writes no records
+        self._model_gen = self._cost_gen = None  # the plugin graphs' own
         self.graph_rollout = False  # nominal rollout of a plugin as a hipGraph
-        self._fused = None  # None: untried, True / False: fused kernel applies
-        # the whole round in one launch (round_nominal): None untried, True /
-        # False applies / does not (set False to force the two launches)
-        self._one_launch = None
-        self._round_args = None
+        self._fused = self._one_launch = None  # _plan()'s inputs (docstring)
+        self._round_args = None  # _buffers()'s cache
+        self._jscr = torch.zeros_like(self.J_opt)  # sync_records()'s J_opt
+        self.last_search_timed = None
         # int64 [ceil(B / 16)][2] or None: pddp_round_nominal_f32's phase clock
         self.phase_ticks = None
         # False after a search launch that dropped the candidates (large
@@ -133,10 +161,8 @@ class ILQRSolver(object):
         # the winner's actions are re-evaluated, include/pddp_hip.h)
         self.candidates_kept = True
         self._derivs_due = True
-        # The sweep that evaluates the derivative records itself, from the
-        # nominal (pddp_sweep_nominal_f32): None untried, then True / False.
-        # With it `rec` is not kept up to date by round(); `sync_records()`
-        # brings it up to date for whoever reads it.
+        # (with the sweep from the nominal `rec` is not kept up to date by
+        # round(); `sync_records()` brings it up to date for whoever reads it)
         self._nominal_sweep = None if (self._nominal_sweep_possible() and
                                        self._nominal_sweep_pays()) else False
         self._rec_stale = False
@@ -189,17 +215,15 @@ class ILQRSolver(object):
         """Brings `rec` / `L` up to date with the nominal when round() left
         them behind (the sweep from the nominal writes no records)."""
         if self._rec_stale:
-            p = _native.ptr
-            _native.call("pddp_derivs", self.dtype, self._pp, self.B, self.N,
-                         p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
-                         None, p(self._rec), p(self.L), p(self._J_scratch()),
-                         None, self._s())
+            self._derivs(None, self._jscr, None)
             self._rec_stale = False
 
-    def _J_scratch(self):
-        if getattr(self, "_jscr", None) is None:
-            self._jscr = torch.zeros_like(self.J_opt)
-        return self._jscr
+    def _derivs(self, mask, J, state):
+        p = _native.ptr
+        _native.call("pddp_derivs", self.dtype, self._pp, self.B, self.N,
+                     p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
+                     p(mask), p(self._rec), p(self.L), p(J), p(state),
+                     self._s())
 
     # -- views in the reference's tensor layout -----------------------------
     def record_views(self):
@@ -270,7 +294,7 @@ class ILQRSolver(object):
         # (and the cost's tensors where launches read converted copies of
         # them: the GP line search, plugin.cost_generation)
         cg = getattr(self.plugin, "cost_generation", lambda: None)()
-        if gen != self._model_gen or cg != getattr(self, "_cost_gen", cg):
+        if gen != self._model_gen or cg != self._cost_gen:
             self._graph = None
             self._rollout_graph = None
             self._model_gen = gen
@@ -305,11 +329,7 @@ class ILQRSolver(object):
         if mask is not None:
             self.sync_records()  # (the rows outside the mask)
         self._rec_stale = False
-        p = _native.ptr
-        _native.call("pddp_derivs", self.dtype, self._pp, self.B, self.N,
-                     p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
-                     p(mask), p(self._rec), p(self.L), p(self.J_opt),
-                     p(self.state) if set_state else None, self._s())
+        self._derivs(mask, self.J_opt, self.state if set_state else None)
 
     @_on_device
     def backward(self, active=None, reg=None, branch=None, bounded=True,
@@ -333,28 +353,104 @@ class ILQRSolver(object):
             _native.call("pddp_riccati_backward_timed", self.dtype, *args,
                          events[0], events[1])
 
+    # -- the round's launch plan ----------------------------------------------
+    def _plan(self, variant, search_events=None):
+        """The sequence a round tries first (module docstring)."""
+        if variant == 0 and self._nominal_sweep is not False and \
+                self._fused is not False:
+            one = self._one_launch is not False and search_events is None
+            return ONE_LAUNCH if one else NOMINAL_FUSED
+        return RECORDS_FUSED if self._fused_allowed() else RECORDS_SEPARATE
+
+    def _fused_allowed(self):
+        return self.plugin is None and self._fused is not False
+
+    def _one_launch_applied(self):
+        return self._one_launch is True
+
+    def _nominal_sweep_applied(self):
+        return self._nominal_sweep is True
+
+    def _records_due(self, always):
+        # (the fused search writes the records of the nominals it accepts)
+        return self._derivs_due or always or self._fused is not True
+
+    def _round_nominal_done(self, ok):  # (ok False: PDDP_E_UNSUPPORTED)
+        self._one_launch = ok
+        if ok:
+            self._nominal_sweep = self._fused = self._rec_stale = True
+            self._derivs_due = False
+        return ok
+
+    def _sweep_nominal_done(self, ok):
+        self._nominal_sweep = ok
+        self._rec_stale |= ok  # (the sweep writes no records)
+        return ok
+
+    def _search_accept_done(self, ok, records=True):
+        self._fused = ok
+        if ok:
+            # (pddp_search_candidates: without records the candidates are
+            # dropped beyond 200 MB - Zc / Uc are scratch after such a launch,
+            # only Jc and the nominal are results)
+            mode = _native.lib().pddp_search_candidates(-1)
+            nbytes = float(self.B) * self.A * (
+                (self.N + 1) * self.n + self.N * self.m) * \
+                self.Z.element_size()
+            self.candidates_kept = records or self._rec is None or not (
+                mode == 2 or (mode == 0 and nbytes > 200e6))
+        return ok
+
+    def _launch(self, events, fn, *args):
+        """fn(*args) with `events`, a (start, stop) pair or None, attached to
+        its launch - detached again if it made none (PDDP_E_UNSUPPORTED)."""
+        if events is None:
+            return fn(*args)
+        attach = _native.lib().pddp_attach_events
+        attach(*events)
+        rc = fn(*args)
+        if rc == _native.E_UNSUPPORTED:
+            attach(None, None)
+        return rc
+
+    def _buffers(self):
+        """Addresses of the round's buffers (the solver's own for its lifetime:
+        looked up once - a launch of pddp_round_nominal_f32 is the whole host
+        side of a round, and 27 data_ptr() calls were a third of it).  After
+        replacing one other than u_min, u_max, alphas: `_round_args = None`."""
+        key = (self._rec.data_ptr(), self.Z.data_ptr(), self.U.data_ptr(),
+               self.gains.data_ptr(), int(self.branch), id(self.u_min),
+               id(self.u_max), id(self.alphas))
+        b = self._round_args
+        if b is None or b.key != key:
+            b = self._round_args = types.SimpleNamespace(
+                key=key, keep=(self.u_min, self.u_max, self.alphas),  # (ids)
+                branch=key[4], **{
+                    k.lstrip("_"): _native.ptr(getattr(self, k)) for k in (
+                        "Z", "U", "alphas", "u_min", "u_max", "active",
+                        "fresh", "gains", "bwd_status", "L", "J_opt", "Zc",
+                        "Uc", "Jc", "gains_acc", "mu", "delta", "state",
+                        "iter", "n_live", "_rec")})
+            # pddp_round_nominal_f32's around (tol, max_reg, n_iterations)
+            b.head = (self._pp, self.B, self.N, self.A, b.Z, b.U, b.alphas,
+                      b.u_min, b.u_max, b.branch, b.active, b.fresh, b.gains,
+                      b.bwd_status, b.L, b.J_opt, b.Zc, b.Uc, b.Jc)
+            b.tail = (b.gains_acc, b.mu, b.delta, b.state, b.iter, b.n_live,
+                      b.rec)
+        return b
+
     @_on_device
     def sweep_nominal(self, events=None):
         """Backward sweep straight from the nominal (pddp_sweep_nominal_f32):
         derivative records evaluated in the workgroups, stage costs to `L`,
         J_opt of the fresh nominals.  False when it does not apply."""
-        p = _native.ptr
-        if events is not None:
-            _native.lib().pddp_attach_events(*events)
-        rc = _native.call_rc(
-            "pddp_sweep_nominal", self.dtype, self._pp, self.B, self.N,
-            p(self.Z), p(self.U), p(self.u_min), p(self.u_max), p(self.mu),
-            int(self.branch), p(self.active), p(self.fresh), p(self.gains),
-            p(self.bwd_status), p(self.L), p(self.J_opt), self._s())
-        if rc == _native.E_UNSUPPORTED:
-            if events is not None:
-                _native.lib().pddp_attach_events(None, None)
-            self._nominal_sweep = False
-            return False
-        _native.check(rc, "pddp_sweep_nominal")
-        self._nominal_sweep = True
-        self._rec_stale = True
-        return True
+        b = self._buffers()
+        rc = self._launch(
+            events, _native.call_rc, "pddp_sweep_nominal", self.dtype,
+            self._pp, self.B, self.N, b.Z, b.U, b.u_min, b.u_max, b.mu,
+            b.branch, b.active, b.fresh, b.gains, b.bwd_status, b.L, b.J_opt,
+            self._s())
+        return self._sweep_nominal_done(rc == 0)
 
     @_on_device
     def round_nominal(self, tol, max_reg, n_iterations, events=None,
@@ -369,63 +465,34 @@ class ILQRSolver(object):
         calls)."""
         if self.dtype != torch.float32 or self.plugin is not None or \
                 (self.u_min is None) != (self.u_max is None):
-            self._one_launch = False
-            return False
-        if events is not None:
-            _native.lib().pddp_attach_events(*events)
-        # (the buffers are the solver's own for its lifetime: their addresses
-        # are looked up once - a launch of this entry point is the whole host
-        # side of a round, and 27 data_ptr() calls were a third of it)
-        key = (self._rec.data_ptr(), self.Z.data_ptr(), self.U.data_ptr(),
-               self.gains.data_ptr(), int(self.branch))
-        if self._round_args is None or self._round_args[0] != key:
-            p = _native.ptr
-            self._round_args = (key, (
-                self._pp, self.B, self.N, self.A, p(self.Z), p(self.U),
-                p(self.alphas), p(self.u_min), p(self.u_max), int(self.branch),
-                p(self.active), p(self.fresh), p(self.gains),
-                p(self.bwd_status), p(self.L), p(self.J_opt), p(self.Zc),
-                p(self.Uc), p(self.Jc)), (
-                p(self.gains_acc), p(self.mu), p(self.delta), p(self.state),
-                p(self.iter), p(self.n_live), p(self._rec)))
-        _, head, tail = self._round_args
-        rc = _native.lib().pddp_round_nominal_f32(
-            *head, float(tol), float(max_reg), int(n_iterations), *tail,
-            int(rounds), _native.ptr(self.phase_ticks), self._s())
-        if rc == _native.E_UNSUPPORTED:
-            if events is not None:
-                _native.lib().pddp_attach_events(None, None)
-            self._one_launch = False
-            return False
-        _native.check(rc, "pddp_round_nominal_f32")
-        self._one_launch = True
-        self._nominal_sweep = True
-        self._fused = True
-        self._rec_stale = True
-        self._derivs_due = False
-        return True
+            return self._round_nominal_done(False)
+        b = self._buffers()
+        rc = self._launch(
+            events, _native.lib().pddp_round_nominal_f32, *b.head, float(tol),
+            float(max_reg), int(n_iterations), *b.tail, int(rounds),
+            _native.ptr(self.phase_ticks), self._s())
+        if rc != _native.E_UNSUPPORTED:
+            _native.check(rc, "pddp_round_nominal_f32")
+        return self._round_nominal_done(rc == 0)
 
     @_on_device
     def line_search(self, active=None, use_status=True):
         if self.plugin is not None:
             return self.plugin.line_search(self, active, use_status)
-        p = _native.ptr
+        b = self._buffers()
         _native.call("pddp_line_search", self.dtype, self._pp, self.B, self.N,
-                     self.A, p(self.Z), p(self.U), p(self.gains),
-                     p(self.alphas), p(self.u_min), p(self.u_max), p(active),
-                     p(self.bwd_status) if use_status else None, p(self.Zc),
-                     p(self.Uc), p(self.Jc), self._s())
+                     self.A, b.Z, b.U, b.gains, b.alphas, b.u_min, b.u_max,
+                     _native.ptr(active), b.bwd_status if use_status else None,
+                     b.Zc, b.Uc, b.Jc, self._s())
 
     @_on_device
     def accept(self, tol, max_reg, n_iterations):
-        p = _native.ptr
+        b = self._buffers()
         _native.call("pddp_accept", self.dtype, self.B, self.N, self.n, self.m,
-                     self.A, p(self.Zc), p(self.Uc), p(self.Jc), p(self.gains),
-                     p(self.bwd_status), float(tol), float(max_reg),
-                     int(n_iterations), p(self.Z), p(self.U),
-                     p(self.gains_acc), p(self.J_opt), p(self.mu),
-                     p(self.delta), p(self.state), p(self.iter),
-                     p(self.active), p(self.fresh), p(self.n_live), self._s())
+                     self.A, b.Zc, b.Uc, b.Jc, b.gains, b.bwd_status,
+                     float(tol), float(max_reg), int(n_iterations), b.Z, b.U,
+                     b.gains_acc, b.J_opt, b.mu, b.delta, b.state, b.iter,
+                     b.active, b.fresh, b.n_live, self._s())
 
     @_on_device
     def search_accept(self, tol, max_reg, n_iterations, events=None,
@@ -437,46 +504,26 @@ class ILQRSolver(object):
         kernel does not apply nothing is attached and `last_search_timed` says
         so."""
         self.last_search_timed = None
-        if self.plugin is not None or self._fused is False:
+        if not self._fused_allowed():
             return False
-        p = _native.ptr
-        if events is not None:
-            _native.lib().pddp_attach_events(*events)
+        b = self._buffers()
+        rc = self._launch(
+            events, _native.call_rc, "pddp_search_accept", self.dtype,
+            self._pp, self.B, self.N, self.A, b.Z, b.U, b.gains, b.alphas,
+            b.u_min, b.u_max, b.active, b.bwd_status, b.Zc, b.Uc, b.Jc,
+            float(tol), float(max_reg), int(n_iterations), b.gains_acc,
+            b.J_opt, b.mu, b.delta, b.state, b.iter, b.fresh, b.n_live, b.rec,
+            b.L if records else None, self._s())
+        if rc == 0 and events is not None:
             self.last_search_timed = "search_accept"
-        rc = _native.call_rc(
-            "pddp_search_accept", self.dtype, self._pp, self.B, self.N, self.A,
-            p(self.Z), p(self.U), p(self.gains), p(self.alphas), p(self.u_min),
-            p(self.u_max), p(self.active), p(self.bwd_status), p(self.Zc),
-            p(self.Uc), p(self.Jc), float(tol), float(max_reg),
-            int(n_iterations), p(self.gains_acc), p(self.J_opt), p(self.mu),
-            p(self.delta), p(self.state), p(self.iter), p(self.fresh),
-            p(self.n_live), p(self._rec), p(self.L) if records else None,
-            self._s())
-        self._fused = rc == 0
-        if self._fused:
-            # (pddp_search_candidates: without records the candidates are
-            # dropped beyond 200 MB - Zc / Uc are scratch after such a launch,
-            # only Jc and the nominal are results)
-            mode = _native.lib().pddp_search_candidates(-1)
-            nbytes = float(self.B) * self.A * (
-                (self.N + 1) * self.n + self.N * self.m) * \
-                self.Z.element_size()
-            self.candidates_kept = records or self._rec is None or not (
-                mode == 2 or (mode == 0 and nbytes > 200e6))
-        if not self._fused and events is not None:
-            _native.lib().pddp_attach_events(None, None)  # nothing launched
-            self.last_search_timed = None
-        return self._fused
+        return self._search_accept_done(rc == 0, records)
 
     def rounds(self, count, tol=5e-6, max_reg=1e10, n_iterations=50,
                events=None):
         """`count` rounds; in one launch where pddp_round_nominal_f32 applies
         (`events` are then attached to that launch), `count` calls of round()
         otherwise."""
-        if count > 1 and self._one_launch is not False and \
-                self.kernel_variant == 0 and \
-                self._nominal_sweep is not False and \
-                self._fused is not False and \
+        if count > 1 and self._plan(self.kernel_variant) == ONE_LAUNCH and \
                 self.round_nominal(tol, max_reg, n_iterations, events=events,
                                    rounds=count):
             return
@@ -492,44 +539,34 @@ class ILQRSolver(object):
         nominals (so the first call is a no-op from the second round on)."""
         if variant is None:
             variant = self.kernel_variant
-        if self._one_launch is not False and variant == 0 and \
-                self._nominal_sweep is not False and \
-                self._fused is not False and search_events is None and \
-                self.round_nominal(tol, max_reg, n_iterations,
-                                   events=backward_events):
+        plan = self._plan(variant, search_events)
+        if plan == ONE_LAUNCH and self.round_nominal(
+                tol, max_reg, n_iterations, events=backward_events):
             return
-        if self._nominal_sweep is not False and variant == 0 and \
-                self._fused is not False and \
-                self.sweep_nominal(events=backward_events):
-            # records evaluated inside the sweep; the fused launch then writes
-            # none (`fresh` stays set until the next sweep has summed the
-            # stage costs of the new nominal into J_opt)
-            self._derivs_due = False
-            if self.search_accept(tol, max_reg, n_iterations,
-                                  events=search_events, records=False):
-                return
-            # (the fused launch does not apply: > 16 step sizes) the separate
-            # calls; records by the masked derivs launch from now on
-            self._nominal_sweep = False
-            self.line_search(active=self.active)
-            self.accept(tol, max_reg, n_iterations)
-            self._derivs_due = True
+        nominal = plan in (ONE_LAUNCH, NOMINAL_FUSED) and \
+            self.sweep_nominal(events=backward_events)
+        if not nominal:  # on records (derivs() / backward() sync stale ones)
+            if self._records_due(always_derivs):
+                self.derivs(mask=self.fresh)
+            self.backward(active=self.active, variant=variant,
+                          events=backward_events)
+        # (records evaluated inside the sweep: the fused launch then writes
+        # none, and `fresh` stays set until the next sweep has summed the stage
+        # costs of the new nominal into J_opt)
+        self._derivs_due = False
+        if self.search_accept(tol, max_reg, n_iterations, events=search_events,
+                              records=not nominal):
             return
-        if self._rec_stale:
-            self.sync_records()
-        if self._derivs_due or not self._fused or always_derivs:
-            self.derivs(mask=self.fresh)
-            self._derivs_due = False
-        self.backward(active=self.active, variant=variant,
-                      events=backward_events)
-        if not self.search_accept(tol, max_reg, n_iterations,
-                                  events=search_events):
-            if search_events is not None and self.plugin is None:
-                # the separate line search is what gets timed then
-                _native.lib().pddp_attach_events(*search_events)
-                self.last_search_timed = "line_search"
-            self.line_search(active=self.active)
-            self.accept(tol, max_reg, n_iterations)
+        ev = None
+        if nominal:
+            # nominal+separate (> 16 step sizes); records by derivs from now on
+            self._sweep_nominal_done(False)
+        elif self.plugin is None and search_events is not None:
+            # the separate line search is what gets timed then
+            ev, self.last_search_timed = search_events, "line_search"
+        self._launch(ev, self.line_search, self.active)
+        self.accept(tol, max_reg, n_iterations)
+        self._derivs_due = nominal
 
     def graph_ok(self):
         """A round can be captured: native sample problem, or a plugin whose
@@ -571,7 +608,7 @@ class ILQRSolver(object):
                 # set_nominal() must not sweep the previous nominal's records
                 self.round(tol, max_reg, n_iterations, always_derivs=True)
             self._graph = (key, graph, None)
-            self._graph_nominal = self._nominal_sweep is True
+            self._graph_nominal = self._nominal_sweep_applied()
             return graph
         # warm-up outside the capture (noise caches, masks, per-kernel
         # attributes, allocator) on a snapshot of the solver's state
@@ -600,8 +637,7 @@ class ILQRSolver(object):
     def replay_round(self, with_derivs=True):
         g = self._graph[1] if (with_derivs or self._graph[2] is None) \
             else self._graph[2]
-        if getattr(self, "_graph_nominal", False):
-            self._rec_stale = True  # the captured sweep writes no records
+        self._rec_stale |= self._graph_nominal  # (its sweep: no records)
         g.replay()
 
     def fit(self, n_iterations=50, tol=5e-6, max_reg=1e10, on_round=None,
@@ -626,10 +662,9 @@ class ILQRSolver(object):
         while True:
             if graph:
                 self.replay_round(need_derivs)
-            elif rpl > 1 and self._one_launch is True:
-                # (only where the one-launch round has applied: elsewhere
-                # rounds() is a loop of round() calls that would run past the
-                # last live trajectory)
+            elif rpl > 1 and self._one_launch_applied():
+                # (only once the one-launch round has applied: a rounds()
+                # that loops over round() would run past the last live one)
                 c = rpl if max_rounds is None else min(rpl, max_rounds - rounds)
                 self.rounds(c, tol, max_reg, n_iterations)
                 rounds += c - 1
@@ -640,7 +675,7 @@ class ILQRSolver(object):
                 on_round(rounds, self)
             if max_rounds is not None and rounds >= max_rounds:
                 break
-            if not (rpl > 1 and self._one_launch is True) and \
+            if not (rpl > 1 and self._one_launch_applied()) and \
                     rounds % rounds_per_sync:
                 continue
             # the one host sync: live trajectories, and (plugin graphs) whether
