@@ -743,10 +743,57 @@ def capture_round3():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def capture_accept_schedule():
+    """tests/golden/accept_schedule.npz: the reference controller's own
+    `_reset_reg` / `_increase_reg(max_reg)` / `_decrease_reg` (ilqr.py:364-390)
+    driven through seeded random call sequences - 200 calls each, for every
+    pair of increase probability {0.3, 0.5, 0.7} and max_reg {1e-3, 1, 1e10},
+    a reset at the start and after every `_increase_reg` that returned False.
+    Stored per sequence: the calls (0 reset, 1 increase, 2 decrease), `_mu`
+    and `_delta` after each call (doubles) and what the call returned (1 True,
+    0 False, -1 None)."""
+    n_calls = 200
+    calls, mus, deltas, rets, p_incs, max_regs = [], [], [], [], [], []
+    for si, (p_inc, max_reg) in enumerate(
+            (p, r) for p in (0.3, 0.5, 0.7) for r in (1e-3, 1.0, 1e10)):
+        rng = np.random.RandomState(100 + si)
+        ctrl = iLQRController(None, None, None)
+        seq, mu, delta, ret = [], [], [], []
+        reset_due = True
+        for _ in range(n_calls):
+            if reset_due:
+                call, r = 0, ctrl._reset_reg()
+                reset_due = False
+            elif rng.rand() < p_inc:
+                call, r = 1, ctrl._increase_reg(max_reg)
+                reset_due = r is False
+            else:
+                call, r = 2, ctrl._decrease_reg()
+            seq.append(call)
+            mu.append(float(ctrl._mu))
+            delta.append(float(ctrl._delta))
+            ret.append(-1 if r is None else int(bool(r)))
+        calls.append(seq); mus.append(mu); deltas.append(delta); rets.append(ret)
+        p_incs.append(p_inc); max_regs.append(max_reg)
+    store = {"calls": np.array(calls, np.int8),
+             "mu": np.array(mus, np.float64),
+             "delta": np.array(deltas, np.float64),
+             "ret": np.array(rets, np.int8),
+             "p_increase": np.array(p_incs, np.float64),
+             "max_reg": np.array(max_regs, np.float64)}
+    path = os.path.join(OUT, "accept_schedule.npz")
+    np.savez_compressed(path, **store)
+    print("wrote", path, os.path.getsize(path), "bytes;",
+          "max_reg reached %d times" % int((store["ret"] == 0).sum()))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
     np.random.seed(0)
+    if "--accept-schedule" in sys.argv:
+        capture_accept_schedule()
+        return
     if "--round3" in sys.argv:
         capture_round3()
         return
