@@ -248,6 +248,61 @@ int pddp_line_search_f64(const pddp_problem* problem, int B, int N, int A,
                          const int32_t* bwd_status, double* Zc, double* Uc,
                          double* Jc, void* stream);
 
+/* ---- the same three operations with a PER-TRAJECTORY problem -------------
+ * (csrc/batch_problem.hip).  `table` [B][PDDP_BATCH_ROW], device memory of the
+ * run's dtype: row b holds trajectory b's model parameters and goals,
+ *   [PDDP_BATCH_PARAMS .. +7]  params  (pddp_problem.params order: dt first,
+ *                                       then the model's constants)
+ *   [PDDP_BATCH_X_GOAL .. +7]  x_goal  (augmented coordinates, PDDP_MAX_AUG)
+ *   [PDDP_BATCH_U_GOAL .. +3]  u_goal  (PDDP_MAX_ACTION)
+ * Entries beyond the model's sizes are ignored.  Q, Q_term, R, the model, the
+ * encoding and the action bounds are shared: those of `problem`, whose own
+ * params / x_goal / u_goal are not read by the kernels.  An f32 row is 80
+ * bytes, an f64 row 160: rows are 16-byte aligned when the base is.
+ * Every other argument is its uniform namesake's.  Domain: the four sample
+ * models under PDDP_ENC_IGNORE_UNCERTAINTY (PDDP_E_UNSUPPORTED for any other
+ * encoding); table == NULL: PDDP_E_BADARG.  The line search takes any A. */
+#define PDDP_BATCH_ROW 20
+#define PDDP_BATCH_PARAMS 0
+#define PDDP_BATCH_X_GOAL 8
+#define PDDP_BATCH_U_GOAL 16
+int pddp_nominal_rollout_batch_f32(const pddp_problem* problem,
+                                   const float* table, int B, int N,
+                                   const float* z0, const float* U,
+                                   const float* u_min, const float* u_max,
+                                   const uint8_t* mask, float* Z, void* stream);
+int pddp_nominal_rollout_batch_f64(const pddp_problem* problem,
+                                   const double* table, int B, int N,
+                                   const double* z0, const double* U,
+                                   const double* u_min, const double* u_max,
+                                   const uint8_t* mask, double* Z,
+                                   void* stream);
+int pddp_derivs_batch_f32(const pddp_problem* problem, const float* table,
+                          int B, int N, const float* Z, const float* U,
+                          const float* u_min, const float* u_max,
+                          const uint8_t* mask, float* rec, float* L, float* J,
+                          int32_t* state, void* stream);
+int pddp_derivs_batch_f64(const pddp_problem* problem, const double* table,
+                          int B, int N, const double* Z, const double* U,
+                          const double* u_min, const double* u_max,
+                          const uint8_t* mask, double* rec, double* L,
+                          double* J, int32_t* state, void* stream);
+int pddp_line_search_batch_f32(const pddp_problem* problem, const float* table,
+                               int B, int N, int A, const float* Z,
+                               const float* U, const float* gains,
+                               const float* alphas, const float* u_min,
+                               const float* u_max, const uint8_t* active,
+                               const int32_t* bwd_status, float* Zc, float* Uc,
+                               float* Jc, void* stream);
+int pddp_line_search_batch_f64(const pddp_problem* problem,
+                               const double* table, int B, int N, int A,
+                               const double* Z, const double* U,
+                               const double* gains, const double* alphas,
+                               const double* u_min, const double* u_max,
+                               const uint8_t* active,
+                               const int32_t* bwd_status, double* Zc,
+                               double* Uc, double* Jc, void* stream);
+
 /* ---- ilqr.py:102-181 _step() accept / reject, :364-390 mu schedule and the
  * fit() loop bookkeeping (:298-314), per trajectory, device resident -------- */
 /* Controller state arrays (all [B]):

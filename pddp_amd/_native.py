@@ -18,6 +18,9 @@ LIB_PATH = os.environ.get("PDDP_HIP_LIB") or os.path.join(
 CSRC = os.path.join(_HERE, "csrc")
 
 MAX_AUG, MAX_ACTION, MAX_PARAMS = 8, 4, 8
+# the per-trajectory table of the pddp_*_batch_* entry points: one row per
+# trajectory (PDDP_BATCH_* of include/pddp_hip.h)
+BATCH_ROW, BATCH_PARAMS, BATCH_X_GOAL, BATCH_U_GOAL = 20, 0, 8, 16
 
 c_int, c_double, c_void_p = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 
@@ -72,6 +75,9 @@ _SIGS = {
     "pddp_nominal_rollout": [_P, c_int, c_int] + [_P] * 7,
     "pddp_derivs": [_P, c_int, c_int] + [_P] * 10,
     "pddp_line_search": [_P, c_int, c_int, c_int] + [_P] * 12,
+    "pddp_nominal_rollout_batch": [_P, _P, c_int, c_int] + [_P] * 7,
+    "pddp_derivs_batch": [_P, _P, c_int, c_int] + [_P] * 10,
+    "pddp_line_search_batch": [_P, _P, c_int, c_int, c_int] + [_P] * 12,
     "pddp_search_accept": [_P, c_int, c_int, c_int] + [_P] * 11 +
                           [c_double, c_double, c_int] +
                           [_P] * 11,
@@ -128,6 +134,8 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_nominal_rollout",
           "pddp_derivs",
           "pddp_line_search", "pddp_search_accept", "pddp_accept",
+          "pddp_nominal_rollout_batch", "pddp_derivs_batch",
+          "pddp_line_search_batch",
           "pddp_pack_best", "pddp_sweep_nominal", "pddp_gp_step",
           "pddp_gp_step_masked",
           "pddp_gp_rollout")

@@ -38,7 +38,12 @@ is 0 and neither `_nominal_sweep` nor `_fused` is False.
                       backward, pddp_search_accept    refused); no plugin,
                                                       `_fused` is not False
     records+separate  derivs, backward, line_search,  plugin, `_fused` is
-                      accept                          False, or search refused
+                      accept                          False, search refused, or
+                                                      a per-trajectory problem
+
+`set_batch_problem()` gives every trajectory its own model parameters and
+goals (`batch_table`): derivs, nominal rollout and line search are then the
+pddp_*_batch_* entry points, and every round is records+separate.
 """
 import ctypes
 import functools
@@ -167,6 +172,9 @@ class ILQRSolver(object):
                                        self._nominal_sweep_pays()) else False
         self._rec_stale = False
         self._pp = None if problem is None else ctypes.addressof(problem)
+        # [B][_native.BATCH_ROW] per-trajectory parameters and goals, or None:
+        # set_batch_problem()
+        self.batch_table = None
 
     def _nominal_sweep_possible(self):
         """pddp_sweep_nominal_*'s domain (include/pddp_hip.h).  At every
@@ -204,6 +212,96 @@ class ILQRSolver(object):
         return self.problem.model == 1 or (self.problem.model == 3 and
                                            self.dtype == torch.float32)
 
+    # parameters of each sample model, dt included (include/pddp_problem.h)
+    _PARAM_COUNT = {1: 6, 2: 8, 3: 5, 4: 3}
+
+    def _batch_problem_possible(self):
+        """The domain of the pddp_*_batch_* entry points (check_problem() of
+        csrc/problem_args.hpp): a sample model under IGNORE_UNCERTAINTY."""
+        return (self.plugin is None and self.problem is not None and
+                self.problem.encoding == 4 and
+                self.problem.model in self._PARAM_COUNT)
+
+    @_on_device
+    def set_batch_problem(self, params=None, x_goal=None, u_goal=None):
+        """Per-trajectory model parameters and goals: `params` [B][P] (P: the
+        model's parameter count, dt first, in `native_problem`'s order),
+        `x_goal` [B][na] in augmented coordinates, `u_goal` [B][m]; a block
+        not given stays the shared problem's.  Q, Q_term, R, the model, the
+        encoding and the action bounds stay shared.
+
+        Builds `batch_table` ([B][20], include/pddp_hip.h); from then on the
+        nominal rollout, the derivative records and the line search read
+        trajectory b's row, and every round is derivs, backward, line_search,
+        accept (`records+separate`): the sweep from the nominal, the
+        one-launch round and the fused search take one problem for the batch.
+        The current nominal `Z` is NOT rolled out again: call
+        `nominal_rollout()` / `set_nominal()` after changing the table."""
+        if not self._batch_problem_possible():
+            raise _native.NativeError(
+                "set_batch_problem needs a sample problem under "
+                "IGNORE_UNCERTAINTY on the native path (no plugin, no "
+                "Gaussian encoding)")
+        N_ = _native
+        prob = self.problem
+        P, na, m = self._PARAM_COUNT[prob.model], prob.aug_size, self.m
+        # the shared row: double -> T as convert_problem (csrc/models.hpp)
+        row = torch.zeros(N_.BATCH_ROW, dtype=torch.float64)
+        row[N_.BATCH_PARAMS:N_.BATCH_PARAMS + N_.MAX_PARAMS] = \
+            torch.tensor(list(prob.params), dtype=torch.float64)
+        row[N_.BATCH_X_GOAL:N_.BATCH_X_GOAL + N_.MAX_AUG] = \
+            torch.tensor(list(prob.x_goal), dtype=torch.float64)
+        row[N_.BATCH_U_GOAL:N_.BATCH_U_GOAL + N_.MAX_ACTION] = \
+            torch.tensor(list(prob.u_goal), dtype=torch.float64)
+        table = row.to(self.dtype).to(self.device).repeat(self.B, 1)
+        for name, block, off, width in (
+                ("params", params, N_.BATCH_PARAMS, P),
+                ("x_goal", x_goal, N_.BATCH_X_GOAL, na),
+                ("u_goal", u_goal, N_.BATCH_U_GOAL, m)):
+            if block is None:
+                continue
+            block = torch.as_tensor(block)
+            if tuple(block.shape) != (self.B, width):
+                raise _native.NativeError(
+                    "set_batch_problem: %s has shape %s, expected (%d, %d)" % (
+                        name, tuple(block.shape), self.B, width))
+            table[:, off:off + width] = block.to(dtype=self.dtype,
+                                                 device=self.device)
+        self.batch_table = table.contiguous()
+        self._one_launch = self._nominal_sweep = self._fused = False
+        self._derivs_due = True
+        self._rec_stale = True  # (the records in `_rec`: another problem's)
+        self._graph = None
+
+    def clear_batch_problem(self):
+        """Back to one problem for the whole batch: the plan's inputs as the
+        constructor leaves them.  (Nothing to do without a table.)"""
+        if self.batch_table is None:
+            return
+        self.batch_table = None
+        self._fused = self._one_launch = None
+        self._nominal_sweep = None if (self._nominal_sweep_possible() and
+                                       self._nominal_sweep_pays()) else False
+        self._derivs_due = True
+        self._rec_stale = True
+        self._graph = None
+
+    def _one_problem(self, what):
+        if self.batch_table is not None:
+            raise _native.NativeError(
+                "%s evaluates ONE problem for the whole batch; with "
+                "set_batch_problem() a round is derivs, backward, line_search, "
+                "accept" % what)
+
+    def _problem_call(self, name, *args):
+        """A problem kernel's entry point: the `_batch` one, with the table
+        (its address looked up at the call: the tensor may be replaced between
+        two calls), while a table is set."""
+        if self.batch_table is None:
+            return _native.call(name, self.dtype, self._pp, *args)
+        return _native.call(name + "_batch", self.dtype, self._pp,
+                            _native.ptr(self.batch_table), *args)
+
     @property
     def rec(self):
         """The derivative records [B][N+1][S] of the nominal, up to date."""
@@ -220,10 +318,10 @@ class ILQRSolver(object):
 
     def _derivs(self, mask, J, state):
         p = _native.ptr
-        _native.call("pddp_derivs", self.dtype, self._pp, self.B, self.N,
-                     p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
-                     p(mask), p(self._rec), p(self.L), p(J), p(state),
-                     self._s())
+        self._problem_call("pddp_derivs", self.B, self.N,
+                           p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
+                           p(mask), p(self._rec), p(self.L), p(J), p(state),
+                           self._s())
 
     # -- views in the reference's tensor layout -----------------------------
     def record_views(self):
@@ -318,9 +416,9 @@ class ILQRSolver(object):
                 return
             return self.plugin.rollout(self)
         p = _native.ptr
-        _native.call("pddp_nominal_rollout", self.dtype, self._pp, self.B,
-                     self.N, p(self.z0), p(self.U), p(self.u_min),
-                     p(self.u_max), p(mask), p(self.Z), self._s())
+        self._problem_call("pddp_nominal_rollout", self.B,
+                           self.N, p(self.z0), p(self.U), p(self.u_min),
+                           p(self.u_max), p(mask), p(self.Z), self._s())
 
     @_on_device
     def derivs(self, mask=None, set_state=True, in_graph=False):
@@ -356,6 +454,9 @@ class ILQRSolver(object):
     # -- the round's launch plan ----------------------------------------------
     def _plan(self, variant, search_events=None):
         """The sequence a round tries first (module docstring)."""
+        if self.batch_table is not None:
+            # (the other sequences' kernels take one problem for the batch)
+            return RECORDS_SEPARATE
         if variant == 0 and self._nominal_sweep is not False and \
                 self._fused is not False:
             one = self._one_launch is not False and search_events is None
@@ -363,7 +464,8 @@ class ILQRSolver(object):
         return RECORDS_FUSED if self._fused_allowed() else RECORDS_SEPARATE
 
     def _fused_allowed(self):
-        return self.plugin is None and self._fused is not False
+        return self.plugin is None and self._fused is not False and \
+            self.batch_table is None
 
     def _one_launch_applied(self):
         return self._one_launch is True
@@ -444,6 +546,7 @@ class ILQRSolver(object):
         """Backward sweep straight from the nominal (pddp_sweep_nominal_f32):
         derivative records evaluated in the workgroups, stage costs to `L`,
         J_opt of the fresh nominals.  False when it does not apply."""
+        self._one_problem("sweep_nominal")
         b = self._buffers()
         rc = self._launch(
             events, _native.call_rc, "pddp_sweep_nominal", self.dtype,
@@ -463,6 +566,7 @@ class ILQRSolver(object):
         workgroup owns its trajectories; no launch boundary between their
         attempts).  False when it does not apply (the caller then makes the two
         calls)."""
+        self._one_problem("round_nominal")
         if self.dtype != torch.float32 or self.plugin is not None or \
                 (self.u_min is None) != (self.u_max is None):
             return self._round_nominal_done(False)
@@ -480,10 +584,11 @@ class ILQRSolver(object):
         if self.plugin is not None:
             return self.plugin.line_search(self, active, use_status)
         b = self._buffers()
-        _native.call("pddp_line_search", self.dtype, self._pp, self.B, self.N,
-                     self.A, b.Z, b.U, b.gains, b.alphas, b.u_min, b.u_max,
-                     _native.ptr(active), b.bwd_status if use_status else None,
-                     b.Zc, b.Uc, b.Jc, self._s())
+        self._problem_call(
+            "pddp_line_search", self.B, self.N,
+            self.A, b.Z, b.U, b.gains, b.alphas, b.u_min, b.u_max,
+            _native.ptr(active), b.bwd_status if use_status else None,
+            b.Zc, b.Uc, b.Jc, self._s())
 
     @_on_device
     def accept(self, tol, max_reg, n_iterations):
@@ -599,6 +704,8 @@ class ILQRSolver(object):
                self.kernel_variant)
         if self._graph is not None and self._graph[0] == key:
             return self._graph[1]
+        if self.batch_table is not None:
+            self.sync_records()  # (a launch that belongs to no round)
         torch.cuda.synchronize(self.device)
         if self.plugin is None:
             graph = torch.cuda.CUDAGraph()

@@ -63,4 +63,31 @@ struct LineSearchArgs {
   int drop_candidates = 0;
 };
 
+// The domain of the IGNORE_UNCERTAINTY problem kernels (problem_kernels.hip,
+// batch_problem.hip) and their dispatch on the model.
+inline int check_problem(const pddp_problem* p) {
+  if (p == nullptr) return PDDP_E_BADARG;
+  if (p->encoding != PDDP_ENC_IGNORE_UNCERTAINTY) return PDDP_E_UNSUPPORTED;
+  switch (p->model) {
+    case PDDP_MODEL_CARTPOLE:
+    case PDDP_MODEL_DOUBLE_CARTPOLE:
+    case PDDP_MODEL_PENDULUM:
+    case PDDP_MODEL_RENDEZVOUS:
+      return 0;
+  }
+  return PDDP_E_UNSUPPORTED;
+}
+
+#define PDDP_DISPATCH_MODEL(FN, T, p, args, st)                                \
+  switch ((p)->model) {                                                        \
+    case PDDP_MODEL_CARTPOLE:                                                  \
+      return FN<T, PDDP_MODEL_CARTPOLE>(*(p), args, st);                       \
+    case PDDP_MODEL_DOUBLE_CARTPOLE:                                           \
+      return FN<T, PDDP_MODEL_DOUBLE_CARTPOLE>(*(p), args, st);                \
+    case PDDP_MODEL_PENDULUM:                                                  \
+      return FN<T, PDDP_MODEL_PENDULUM>(*(p), args, st);                       \
+    default:                                                                   \
+      return FN<T, PDDP_MODEL_RENDEZVOUS>(*(p), args, st);                     \
+  }
+
 }  // namespace pddp

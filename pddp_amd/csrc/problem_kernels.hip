@@ -361,30 +361,7 @@ static bool is_default_encoding(const pddp_problem* p) {
                           p->encoding == PDDP_ENC_FULL_COVARIANCE_MATRIX);
 }
 
-static int check_problem(const pddp_problem* p) {
-  if (p == nullptr) return PDDP_E_BADARG;
-  if (p->encoding != PDDP_ENC_IGNORE_UNCERTAINTY) return PDDP_E_UNSUPPORTED;
-  switch (p->model) {
-    case PDDP_MODEL_CARTPOLE:
-    case PDDP_MODEL_DOUBLE_CARTPOLE:
-    case PDDP_MODEL_PENDULUM:
-    case PDDP_MODEL_RENDEZVOUS:
-      return 0;
-  }
-  return PDDP_E_UNSUPPORTED;
-}
-
-#define PDDP_DISPATCH_MODEL(FN, T, p, args, st)                                \
-  switch ((p)->model) {                                                        \
-    case PDDP_MODEL_CARTPOLE:                                                  \
-      return FN<T, PDDP_MODEL_CARTPOLE>(*(p), args, st);                       \
-    case PDDP_MODEL_DOUBLE_CARTPOLE:                                           \
-      return FN<T, PDDP_MODEL_DOUBLE_CARTPOLE>(*(p), args, st);                \
-    case PDDP_MODEL_PENDULUM:                                                  \
-      return FN<T, PDDP_MODEL_PENDULUM>(*(p), args, st);                       \
-    default:                                                                   \
-      return FN<T, PDDP_MODEL_RENDEZVOUS>(*(p), args, st);                     \
-  }
+// (check_problem, PDDP_DISPATCH_MODEL: problem_args.hpp)
 
 template <typename T>
 static int nominal_rollout_impl(const pddp_problem* p, int B, int N,
