@@ -272,7 +272,9 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
   // tail's short form re-evaluates the winner's)
   const bool store_uc = !(FUSED && n <= 6 && Lout == nullptr &&
                           rec != nullptr && N + 1 <= 16 * H * kTailRows);
-  auto rollout = [&](T alpha, T* Zci, size_t zstep, T* Uci, size_t ustep) {
+  // (`cost`: std::true_type where the caller uses the returned cost)
+  auto rollout = [&](T alpha, T* Zci, size_t zstep, T* Uci, size_t ustep,
+                     auto cost) {
     if constexpr (kPaired) {
       // (the round kernel, cartpole, CartpoleCost: the step on register
       // pairs - the state (x, xd | th, thd) as one quad, which is also the
@@ -294,6 +296,15 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
 #pragma unroll
         for (int j = 0; j < 4; ++j) Zci[(size_t)t * zstep + j] = z4[j];
         J += cartpole_cost_pk(P, z4.xy, sc, u);
+        // The stage cost is evaluated HERE, before the state moves on.  Left
+        // alone the compiler sinks the costs of a trip's four steps to the
+        // trip's end; the old x then outlives its update, the new state
+        // lands in fresh registers and every candidate row's quad is put
+        // together by three moves.  With J opaque at this point the Euler
+        // updates run in place on the quad the store reads: no move, and no
+        // wait state either (87.0 -> 84.75 instructions per step, DESIGN.md
+        // 3.5b round 9).  Not where the cost is unused (the retry rollout).
+        if constexpr (decltype(cost)::value) asm("" : "+v"(J));
         f32x2 na, nb;
         cartpole_dynamics_pk(P, z4.xy, z4.zw, sc, u, na, nb);
         z4 = V4_{na.x, na.y, nb.x, nb.y};
@@ -415,7 +426,7 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
     // candidates dropped: every other step size overwrites ONE row of its own
     const size_t zstep = compact0 ? (size_t)n : (nocand ? 0 : zstep_c);
     const size_t ustep = nocand ? 0 : ustep_c;
-    Jmine = rollout(alpha, Zci, zstep, Uci, ustep);
+    Jmine = rollout(alpha, Zci, zstep, Uci, ustep, std::true_type{});
     a.Jc[idx] = Jmine;
   }
   PDDP_TLS(2);
@@ -457,7 +468,7 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
       if (nocand && hid == 0 && __any(amin_out > 0)) {
         if (amin_out > 0 && ai == amin_out)
           rollout(a.alphas[ai], rec + (size_t)b * (N + 1) * n, (size_t)n,
-                  a.Uc + ((size_t)b * N * a.A + ai) * m, 0);
+                  a.Uc + ((size_t)b * N * a.A + ai) * m, 0, std::false_type{});
       }
     }
     if constexpr (H == 1) {
