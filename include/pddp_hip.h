@@ -249,8 +249,9 @@ int pddp_line_search_f64(const pddp_problem* problem, int B, int N, int A,
                          double* Jc, void* stream);
 
 /* ---- the same three operations with a PER-TRAJECTORY problem -------------
- * (csrc/batch_problem.hip).  `table` [B][PDDP_BATCH_ROW], device memory of the
- * run's dtype: row b holds trajectory b's model parameters and goals,
+ * (the batch_* kernels of csrc/problem_kernels.hip).  `table`
+ * [B][PDDP_BATCH_ROW], device memory of the run's dtype: row b holds
+ * trajectory b's model parameters and goals,
  *   [PDDP_BATCH_PARAMS .. +7]  params  (pddp_problem.params order: dt first,
  *                                       then the model's constants)
  *   [PDDP_BATCH_X_GOAL .. +7]  x_goal  (augmented coordinates, PDDP_MAX_AUG)

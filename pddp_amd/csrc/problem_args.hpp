@@ -64,7 +64,7 @@ struct LineSearchArgs {
 };
 
 // The domain of the IGNORE_UNCERTAINTY problem kernels (problem_kernels.hip,
-// batch_problem.hip) and their dispatch on the model.
+// both forms) and their dispatch on the model.
 inline int check_problem(const pddp_problem* p) {
   if (p == nullptr) return PDDP_E_BADARG;
   if (p->encoding != PDDP_ENC_IGNORE_UNCERTAINTY) return PDDP_E_UNSUPPORTED;

@@ -14,51 +14,84 @@
 
 namespace pddp {
 
+// Each operation's loop is written ONCE, as a text (*_body.inc) that the
+// kernels of the two forms include: the uniform kernels read the problem from
+// their kernel argument `P`; the batch_* kernels (a problem PER TRAJECTORY: the
+// pddp_*_batch_* entry points, ILQRSolver.set_batch_problem) declare `P` at
+// PDDP_PROBLEM_OF_B as the shared problem with row b of `table`
+// [B][PDDP_BATCH_ROW] written over it (include/pddp_hip.h: params, x_goal,
+// u_goal).  The __global__ functions are that and nothing else; launchers,
+// argument checks and the dispatch on the model are shared too.
+//
+// An included text and not a device function: as a forceinline function
+// <T, MODEL> (arguments by value or by reference, the problem handed in or
+// asked for through a callable - all were built) the same statements reach the
+// optimiser with some commutative operands the other way round, `a * b + c * d`
+// is then contracted into the other FMA, and rollouts, records and candidates
+// differ from the separate kernels' in their last bits
+// (tests/test_problem_kernels_golden.py).  Included, every kernel is the
+// instruction sequence it was.
+//
+// Q, Q_term, R, the model, the encoding and the action bounds stay those of the
+// pddp_problem passed by value.  The row is read ONCE ahead of the time loop,
+// by each lane (rollout, line search) or workgroup (records); the overwritten
+// fields live in vector registers from then on (27 words for the double
+// cartpole, 12 for the cartpole); Q, Qt and R are never written and stay scalar
+// operands of the kernel argument.
+//
+// The backward sweep and the accept kernel never see the problem, so a round
+// with a table is derivs(batch), backward, line_search(batch), accept.
+
+// parameters of each model, dt included (include/pddp_problem.h)
+template <int MODEL>
+constexpr int kParamCount = MODEL == PDDP_MODEL_CARTPOLE          ? 6
+                            : MODEL == PDDP_MODEL_DOUBLE_CARTPOLE ? 8
+                            : MODEL == PDDP_MODEL_PENDULUM        ? 5
+                                                                  : 3;
+
+// The shared problem with trajectory b's row written over it.  Entries of the
+// row beyond the model's sizes are not read.
+template <typename T, int MODEL>
+PDDP_DEV ProblemT<T> problem_of_row(const ProblemT<T>& shared, const T* table,
+                                    int b) {
+  using D = ModelDims<MODEL>;
+  const T* row = table + (size_t)b * PDDP_BATCH_ROW;
+  ProblemT<T> P = shared;
+  P.dt = row[PDDP_BATCH_PARAMS];
+#pragma unroll
+  for (int i = 0; i < kParamCount<MODEL> - 1; ++i)
+    P.p[i] = row[PDDP_BATCH_PARAMS + 1 + i];
+#pragma unroll
+  for (int i = 0; i < D::na; ++i) P.goal[i] = row[PDDP_BATCH_X_GOAL + i];
+#pragma unroll
+  for (int i = 0; i < D::m; ++i) P.ugoal[i] = row[PDDP_BATCH_U_GOAL + i];
+  return P;
+}
+
 // --------------------------------------------------------------------------
-// nominal rollout: one lane per trajectory
+// nominal rollout: one lane per trajectory (rollout_body.inc)
 // --------------------------------------------------------------------------
 
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kWave) void nominal_rollout_kernel(
     ProblemT<T> P, RolloutArgs<T> a) {
-  using D = ModelDims<MODEL>;
-  constexpr int n = D::n, m = D::m;
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.B) return;
-  if (a.mask != nullptr && a.mask[b] == 0) return;
-  const bool bounded = a.u_min != nullptr && a.u_max != nullptr;
-  T z[n], zn[n], u[m], umin[m], umax[m];
-#pragma unroll
-  for (int r = 0; r < m; ++r) {
-    umin[r] = bounded ? a.u_min[r] : T(0);
-    umax[r] = bounded ? a.u_max[r] : T(0);
-  }
-  T* Zb = a.Z + (size_t)b * (a.N + 1) * n;
-  const T* Ub = a.U + (size_t)b * a.N * m;
-#pragma unroll
-  for (int j = 0; j < n; ++j) {
-    z[j] = a.z0[(size_t)b * n + j];
-    Zb[j] = z[j];
-  }
-  for (int t = 0; t < a.N; ++t) {
-#pragma unroll
-    for (int j = 0; j < m; ++j) {
-      u[j] = Ub[t * m + j];
-      if (bounded) u[j] = clamp1(u[j], umin[j], umax[j]);
-    }
-    const Trig<T, MODEL> tr = trig_of<T, MODEL>(z);
-    dynamics<T, MODEL, false>(P, z, u, tr, zn, nullptr, nullptr);
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      z[j] = zn[j];
-      Zb[(t + 1) * n + j] = z[j];
-    }
-  }
+#define PDDP_PROBLEM_OF_B
+#include "rollout_body.inc"
+#undef PDDP_PROBLEM_OF_B
+}
+
+template <typename T, int MODEL>
+__global__ __launch_bounds__(kWave) void batch_rollout_kernel(
+    ProblemT<T> shared, RolloutArgs<T> a, const T* table) {
+#define PDDP_PROBLEM_OF_B const ProblemT<T> P = problem_of_row<T, MODEL>(shared, table, b);
+#include "rollout_body.inc"
+#undef PDDP_PROBLEM_OF_B
 }
 
 // --------------------------------------------------------------------------
-// derivative records: one workgroup per trajectory, one lane per time step;
-// records are staged through LDS so the HBM writes are fully coalesced.
+// derivative records: one workgroup per trajectory (the row index is the
+// workgroup's), one lane per time step; records are staged through LDS so the
+// HBM writes are fully coalesced (derivs_body.inc).
 // --------------------------------------------------------------------------
 // (group_copy, store4: line_search_lds.hpp)
 // (record_of: models.hpp)
@@ -68,149 +101,50 @@ constexpr int kDerivThreads = 64;
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kDerivThreads) void derivs_kernel(
     ProblemT<T> P, DerivArgs<T> a) {
-  using D = ModelDims<MODEL>;
-  constexpr int n = D::n, m = D::m;
-  constexpr RecLayout lay(n, m);
-  constexpr int S = lay.stride;
-  constexpr int LD = kDerivThreads + 1;  // +1: conflict-free transposed reads
-  __shared__ T stage[S * LD];
-  __shared__ T Lsum[kDerivThreads];
+#define PDDP_PROBLEM_OF_B
+#define PDDP_SPLIT_TERMINAL 0
+#include "derivs_body.inc"
+#undef PDDP_SPLIT_TERMINAL
+#undef PDDP_PROBLEM_OF_B
+}
 
-  const int b = blockIdx.x;
-  const int tid = threadIdx.x;
-  if (a.mask != nullptr && a.mask[b] == 0) return;
-  const bool bounded = a.u_min != nullptr && a.u_max != nullptr;
-  const int N = a.N;
-  const T* Zb = a.Z + (size_t)b * (N + 1) * n;
-  const T* Ub = a.U + (size_t)b * N * m;
-  T* rec_b = a.rec + (size_t)b * (N + 1) * S;
-  T Jacc = T(0);  // only meaningful in lane 0
-
-  for (int t0 = 0; t0 <= N; t0 += kDerivThreads) {
-    const int t = t0 + tid;
-    T l = T(0);
-    if (t <= N) {
-      T z[n], un[m], w[S];
-#pragma unroll
-      for (int j = 0; j < n; ++j) z[j] = Zb[t * n + j];
-      const bool terminal = (t == N);
-#pragma unroll
-      for (int j = 0; j < m; ++j) un[j] = terminal ? T(0) : Ub[t * m + j];
-      l = record_of<T, MODEL>(P, z, un, terminal, bounded, a.u_min, a.u_max, w);
-      T* col = stage + tid;
-#pragma unroll
-      for (int j = 0; j < S; ++j) col[j * LD] = w[j];
-      a.L[(size_t)b * (N + 1) + t] = l;
-    }
-    Lsum[tid] = l;
-    __syncthreads();
-    // coalesced write-out of this chunk's records
-    const int nrec = min(kDerivThreads, N + 1 - t0);
-    T* dst = rec_b + (size_t)t0 * S;
-    for (int o = tid; o < nrec * S; o += kDerivThreads) {
-      const int r = o / S, w = o - r * S;
-      dst[o] = stage[w * LD + r];
-    }
-    if (tid == 0)
-      for (int r = 0; r < nrec; ++r) Jacc += Lsum[r];  // L.sum(), in t order
-    __syncthreads();
-  }
-  if (tid == 0) {
-    a.J[b] = Jacc;
-    if (a.state != nullptr) a.state[b] = PDDP_STATE_UNDEFINED;
-  }
+// `terminal` as a constant in each call of record_of: the cost picks its
+// matrix by `terminal ? P.Qt : P.Q`, and a run-time choice between two members
+// of this per-workgroup COPY would put the whole copy into scratch memory
+// (1344 B in f64, 680 B in f32).  The uniform kernel indexes the kernel
+// argument itself and keeps the run-time flag: its code object is the one it
+// was before the two forms shared their text.
+template <typename T, int MODEL>
+__global__ __launch_bounds__(kDerivThreads) void batch_derivs_kernel(
+    ProblemT<T> shared, DerivArgs<T> a, const T* table) {
+#define PDDP_PROBLEM_OF_B const ProblemT<T> P = problem_of_row<T, MODEL>(shared, table, b);
+#define PDDP_SPLIT_TERMINAL 1
+#include "derivs_body.inc"
+#undef PDDP_SPLIT_TERMINAL
+#undef PDDP_PROBLEM_OF_B
 }
 
 // --------------------------------------------------------------------------
-// line search: one lane per (trajectory, alpha) candidate
+// line search: one lane per (trajectory, alpha) candidate, any A; the next
+// step's nominal row and gains are requested ahead of the dependent chain
+// (with a table, the lanes of a trajectory read the same row: one broadcast
+// read each ahead of the loop) (line_search_body.inc)
 // --------------------------------------------------------------------------
 
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kWave) void line_search_kernel(
     ProblemT<T> P, LineSearchArgs<T> a) {
-  using D = ModelDims<MODEL>;
-  constexpr int n = D::n, m = D::m;
-  constexpr int GS = m + m * n;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const int total = a.B * a.A;
-  if (idx >= total) return;
-  const int b = idx / a.A, ai = idx - b * a.A;
-  if (a.active != nullptr && a.active[b] == 0) return;
-  if (a.bwd_status != nullptr && a.bwd_status[b] != 0) return;
-  const bool bounded = a.u_min != nullptr && a.u_max != nullptr;
-  T umin[m], umax[m];
-#pragma unroll
-  for (int r = 0; r < m; ++r) {
-    umin[r] = bounded ? a.u_min[r] : T(0);
-    umax[r] = bounded ? a.u_max[r] : T(0);
-  }
-  const int N = a.N;
-  const T alpha = a.alphas[ai];
-  const T* Zb = a.Z + (size_t)b * (N + 1) * n;
-  const T* Ub = a.U + (size_t)b * N * m;
-  const T* Gb = a.gains + (size_t)b * N * GS;
+#define PDDP_PROBLEM_OF_B
+#include "line_search_body.inc"
+#undef PDDP_PROBLEM_OF_B
+}
 
-  T z[n], zn[n], un[m];
-  T zr[n], ur[m], gr[GS];  // this step's nominal z, u and gains
-#pragma unroll
-  for (int j = 0; j < n; ++j) {
-    zr[j] = Zb[j];
-    z[j] = zr[j];  // Z_new[0] = Z[0]                             (ilqr.py:690)
-  }
-#pragma unroll
-  for (int j = 0; j < m; ++j) ur[j] = Ub[j];
-#pragma unroll
-  for (int j = 0; j < GS; ++j) gr[j] = Gb[j];
-
-  // time-major output [b][t][alpha][.]: at every step the A lanes of a
-  // trajectory write one contiguous A*n-word segment (see the note at
-  // LineSearchArgs)
-  T* Zci = a.Zc + ((size_t)b * (N + 1) * a.A + ai) * n;
-  T* Uci = a.Uc + ((size_t)b * N * a.A + ai) * m;
-  const size_t zstep = (size_t)a.A * n, ustep = (size_t)a.A * m;
-  T J = T(0);
-  for (int t = 0; t < N; ++t) {
-    // prefetch the next step's nominal data before the dependent chain
-    T zr2[n], ur2[m], gr2[GS];
-    const int tn = (t + 1 < N) ? t + 1 : t;
-#pragma unroll
-    for (int j = 0; j < n; ++j) zr2[j] = Zb[tn * n + j];
-#pragma unroll
-    for (int j = 0; j < m; ++j) ur2[j] = Ub[tn * m + j];
-#pragma unroll
-    for (int j = 0; j < GS; ++j) gr2[j] = Gb[tn * GS + j];
-
-#pragma unroll
-    for (int r = 0; r < m; ++r) {
-      T du = alpha * gr[r];  // alpha * k[i]                      (ilqr.py:708)
-      T s = T(0);
-#pragma unroll
-      for (int c = 0; c < n; ++c) s += (z[c] - zr[c]) * gr[m + r * n + c];
-      du = du + s;  // + dz K^T                                   (ilqr.py:710)
-      T v = ur[r] + du;
-      un[r] = bounded ? clamp_nan(v, umin[r], umax[r]) : v;
-    }
-#pragma unroll
-    for (int j = 0; j < n; ++j) Zci[(size_t)t * zstep + j] = z[j];
-#pragma unroll
-    for (int j = 0; j < m; ++j) Uci[(size_t)t * ustep + j] = un[j];
-    const Trig<T, MODEL> tr = trig_of<T, MODEL>(z);
-    J += cost_value<T, MODEL>(P, z, un, tr, false);
-    dynamics<T, MODEL, false>(P, z, un, tr, zn, nullptr, nullptr);
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      z[j] = zn[j];
-      zr[j] = zr2[j];
-    }
-#pragma unroll
-    for (int j = 0; j < m; ++j) ur[j] = ur2[j];
-#pragma unroll
-    for (int j = 0; j < GS; ++j) gr[j] = gr2[j];
-  }
-#pragma unroll
-  for (int j = 0; j < n; ++j) Zci[(size_t)N * zstep + j] = z[j];
-  const T lf = cost_value<T, MODEL>(P, z, nullptr, trig_of<T, MODEL>(z), true);
-  a.Jc[idx] = J + lf;  // L.sum(0) + l_f                           (ilqr.py:789)
+template <typename T, int MODEL>
+__global__ __launch_bounds__(kWave) void batch_line_search_kernel(
+    ProblemT<T> shared, LineSearchArgs<T> a, const T* table) {
+#define PDDP_PROBLEM_OF_B const ProblemT<T> P = problem_of_row<T, MODEL>(shared, table, b);
+#include "line_search_body.inc"
+#undef PDDP_PROBLEM_OF_B
 }
 
 // --------------------------------------------------------------------------
@@ -228,26 +162,50 @@ static bool stage_cost_on(const pddp_problem& p) {
   if (QM == kFullMask<MODEL>) return false;
   return (live_mask(p.Q, ModelDims<MODEL>::na) & ~QM) == 0;
 }
+// an argument block and the per-trajectory table of the batch entry points,
+// nullptr from the uniform ones
+template <typename Args, typename T>
+struct WithTable {
+  Args a;
+  const T* table;
+};
 template <typename T, int MODEL>
-static int launch_rollout(const pddp_problem& p, RolloutArgs<T> a,
-                          hipStream_t st) {
+static int launch_rollout(const pddp_problem& p,
+                          WithTable<RolloutArgs<T>, T> w, hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  const int blocks = (a.B + kWave - 1) / kWave;
-  PDDP_LAUNCH((nominal_rollout_kernel<T, MODEL>), dim3(blocks),
-                     dim3(kWave), 0, st, P, a);
+  const dim3 blocks((w.a.B + kWave - 1) / kWave);
+  if (w.table != nullptr)
+    PDDP_LAUNCH((batch_rollout_kernel<T, MODEL>), blocks, dim3(kWave), 0, st,
+                P, w.a, w.table);
+  else
+    PDDP_LAUNCH((nominal_rollout_kernel<T, MODEL>), blocks, dim3(kWave), 0, st,
+                P, w.a);
   return launch_status();
 }
 template <typename T, int MODEL>
-static int launch_derivs(const pddp_problem& p, DerivArgs<T> a, hipStream_t st) {
+static int launch_derivs(const pddp_problem& p, WithTable<DerivArgs<T>, T> w,
+                         hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  PDDP_LAUNCH((derivs_kernel<T, MODEL>), dim3(a.B), dim3(kDerivThreads),
-                     0, st, P, a);
+  if (w.table != nullptr)
+    PDDP_LAUNCH((batch_derivs_kernel<T, MODEL>), dim3(w.a.B),
+                dim3(kDerivThreads), 0, st, P, w.a, w.table);
+  else
+    PDDP_LAUNCH((derivs_kernel<T, MODEL>), dim3(w.a.B), dim3(kDerivThreads), 0,
+                st, P, w.a);
   return launch_status();
 }
 template <typename T, int MODEL>
-static int launch_line_search(const pddp_problem& p, LineSearchArgs<T> a,
+static int launch_line_search(const pddp_problem& p,
+                              WithTable<LineSearchArgs<T>, T> w,
                               hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
+  const LineSearchArgs<T>& a = w.a;
+  const dim3 lanes((unsigned)(((long long)a.B * a.A + kWave - 1) / kWave));
+  if (w.table != nullptr) {  // (the LDS kernels take one problem)
+    PDDP_LAUNCH((batch_line_search_kernel<T, MODEL>), lanes, dim3(kWave), 0,
+                st, P, a, w.table);
+    return launch_status();
+  }
   using D = ModelDims<MODEL>;
   const size_t per = (size_t)(a.N + 1) * D::n + (size_t)a.N * D::m +
                      (size_t)a.N * (D::m + D::m * D::n);
@@ -269,10 +227,8 @@ static int launch_line_search(const pddp_problem& p, LineSearchArgs<T> a,
                          AcceptArgs<T>{}, (T*)nullptr, (T*)nullptr);
     return launch_status();
   }
-  const int total = a.B * a.A;
-  const int blocks = (total + kWave - 1) / kWave;
-  PDDP_LAUNCH((line_search_kernel<T, MODEL>), dim3(blocks), dim3(kWave),
-                     0, st, P, a);
+  PDDP_LAUNCH((line_search_kernel<T, MODEL>), lanes, dim3(kWave), 0, st, P,
+              a);
   return launch_status();
 }
 
@@ -363,47 +319,58 @@ static bool is_default_encoding(const pddp_problem* p) {
 
 // (check_problem, PDDP_DISPATCH_MODEL: problem_args.hpp)
 
+// The three entry points in both forms.  `batch`: a pddp_*_batch_* entry
+// point - it needs its table and takes check_problem()'s domain only, the four
+// sample models under IGNORE_UNCERTAINTY; the uniform ones (table == nullptr)
+// route the Gaussian encodings to default_kernels.hip.
 template <typename T>
-static int nominal_rollout_impl(const pddp_problem* p, int B, int N,
-                                const T* z0, const T* U, const T* u_min,
-                                const T* u_max, const uint8_t* mask, T* Z,
-                                void* stream) {
-  if (B <= 0 || N <= 0 || !z0 || !U || !Z) return PDDP_E_BADARG;
-  RolloutArgs<T> a{B, N, z0, U, u_min, u_max, mask, Z};
-  if (is_default_encoding(p))
-    return default_rollout<T>(*p, a, (hipStream_t)stream);
-  if (int rc = check_problem(p)) return rc;
-  PDDP_DISPATCH_MODEL(launch_rollout, T, p, a, (hipStream_t)stream)
-}
-
-template <typename T>
-static int derivs_impl(const pddp_problem* p, int B, int N, const T* Z,
-                       const T* U, const T* u_min, const T* u_max,
-                       const uint8_t* mask, T* rec, T* L, T* J, int32_t* state,
-                       void* stream) {
-  if (B <= 0 || N <= 0 || !Z || !U || !rec || !L || !J) return PDDP_E_BADARG;
-  DerivArgs<T> a{B, N, Z, U, u_min, u_max, mask, rec, L, J, state};
-  if (is_default_encoding(p))
-    return default_derivs<T>(*p, a, (hipStream_t)stream);
-  if (int rc = check_problem(p)) return rc;
-  PDDP_DISPATCH_MODEL(launch_derivs, T, p, a, (hipStream_t)stream)
-}
-
-template <typename T>
-static int line_search_impl(const pddp_problem* p, int B, int N, int A,
-                            const T* Z, const T* U, const T* gains,
-                            const T* alphas, const T* u_min, const T* u_max,
-                            const uint8_t* active, const int32_t* bwd_status,
-                            T* Zc, T* Uc, T* Jc, void* stream) {
-  if (B <= 0 || N <= 0 || A <= 0 || !Z || !U || !gains || !alphas || !Zc ||
-      !Uc || !Jc)
+static int nominal_rollout_impl(const pddp_problem* p, bool batch,
+                                const T* table, int B, int N, const T* z0,
+                                const T* U, const T* u_min, const T* u_max,
+                                const uint8_t* mask, T* Z, void* stream) {
+  if (B <= 0 || N <= 0 || (batch && !table) || !z0 || !U || !Z)
     return PDDP_E_BADARG;
-  LineSearchArgs<T> a{B, N, A, Z, U, gains, alphas, u_min, u_max, active,
-                      bwd_status, Zc, Uc, Jc};
-  if (is_default_encoding(p))
-    return default_line_search<T>(*p, a, (hipStream_t)stream);
+  WithTable<RolloutArgs<T>, T> w{{B, N, z0, U, u_min, u_max, mask, Z}, table};
+  if (!batch && is_default_encoding(p))
+    return default_rollout<T>(*p, w.a, (hipStream_t)stream);
   if (int rc = check_problem(p)) return rc;
-  PDDP_DISPATCH_MODEL(launch_line_search, T, p, a, (hipStream_t)stream)
+  PDDP_DISPATCH_MODEL(launch_rollout, T, p, w, (hipStream_t)stream)
+}
+
+template <typename T>
+static int derivs_impl(const pddp_problem* p, bool batch, const T* table,
+                       int B, int N, const T* Z, const T* U, const T* u_min,
+                       const T* u_max, const uint8_t* mask, T* rec, T* L, T* J,
+                       int32_t* state, void* stream) {
+  if (B <= 0 || N <= 0 || (batch && !table) || !Z || !U || !rec || !L || !J)
+    return PDDP_E_BADARG;
+  WithTable<DerivArgs<T>, T> w{
+      {B, N, Z, U, u_min, u_max, mask, rec, L, J, state}, table};
+  if (!batch && is_default_encoding(p))
+    return default_derivs<T>(*p, w.a, (hipStream_t)stream);
+  if (int rc = check_problem(p)) return rc;
+  PDDP_DISPATCH_MODEL(launch_derivs, T, p, w, (hipStream_t)stream)
+}
+
+template <typename T>
+static int line_search_impl(const pddp_problem* p, bool batch, const T* table,
+                            int B, int N, int A, const T* Z, const T* U,
+                            const T* gains, const T* alphas, const T* u_min,
+                            const T* u_max, const uint8_t* active,
+                            const int32_t* bwd_status, T* Zc, T* Uc, T* Jc,
+                            void* stream) {
+  if (B <= 0 || N <= 0 || A <= 0 || (batch && !table) || !Z || !U || !gains ||
+      !alphas || !Zc || !Uc || !Jc)
+    return PDDP_E_BADARG;
+  // (the batch kernel's int lane index; the uniform entry points never checked)
+  if (batch && (long long)B * A > 0x7fffffffLL) return PDDP_E_BADARG;
+  WithTable<LineSearchArgs<T>, T> w{{B, N, A, Z, U, gains, alphas, u_min,
+                                     u_max, active, bwd_status, Zc, Uc, Jc},
+                                    table};
+  if (!batch && is_default_encoding(p))
+    return default_line_search<T>(*p, w.a, (hipStream_t)stream);
+  if (int rc = check_problem(p)) return rc;
+  PDDP_DISPATCH_MODEL(launch_line_search, T, p, w, (hipStream_t)stream)
 }
 
 // 0 auto (by the size of the candidates), 1 keep them, 2 drop them
@@ -507,29 +474,29 @@ int pddp_nominal_rollout_f32(const pddp_problem* p, int B, int N,
                              const float* z0, const float* U,
                              const float* u_min, const float* u_max,
                              const uint8_t* mask, float* Z, void* stream) {
-  return pddp::nominal_rollout_impl<float>(p, B, N, z0, U, u_min, u_max, mask,
-                                           Z, stream);
+  return pddp::nominal_rollout_impl<float>(p, false, nullptr, B, N, z0, U,
+                                           u_min, u_max, mask, Z, stream);
 }
 int pddp_nominal_rollout_f64(const pddp_problem* p, int B, int N,
                              const double* z0, const double* U,
                              const double* u_min, const double* u_max,
                              const uint8_t* mask, double* Z, void* stream) {
-  return pddp::nominal_rollout_impl<double>(p, B, N, z0, U, u_min, u_max, mask,
-                                            Z, stream);
+  return pddp::nominal_rollout_impl<double>(p, false, nullptr, B, N, z0, U,
+                                            u_min, u_max, mask, Z, stream);
 }
 int pddp_derivs_f32(const pddp_problem* p, int B, int N, const float* Z,
                     const float* U, const float* u_min, const float* u_max,
                     const uint8_t* mask, float* rec, float* L, float* J,
                     int32_t* state, void* stream) {
-  return pddp::derivs_impl<float>(p, B, N, Z, U, u_min, u_max, mask, rec, L, J,
-                                  state, stream);
+  return pddp::derivs_impl<float>(p, false, nullptr, B, N, Z, U, u_min, u_max,
+                                  mask, rec, L, J, state, stream);
 }
 int pddp_derivs_f64(const pddp_problem* p, int B, int N, const double* Z,
                     const double* U, const double* u_min, const double* u_max,
                     const uint8_t* mask, double* rec, double* L, double* J,
                     int32_t* state, void* stream) {
-  return pddp::derivs_impl<double>(p, B, N, Z, U, u_min, u_max, mask, rec, L,
-                                   J, state, stream);
+  return pddp::derivs_impl<double>(p, false, nullptr, B, N, Z, U, u_min,
+                                   u_max, mask, rec, L, J, state, stream);
 }
 int pddp_line_search_f32(const pddp_problem* p, int B, int N, int A,
                          const float* Z, const float* U, const float* gains,
@@ -537,9 +504,9 @@ int pddp_line_search_f32(const pddp_problem* p, int B, int N, int A,
                          const float* u_max, const uint8_t* active,
                          const int32_t* bwd_status, float* Zc, float* Uc,
                          float* Jc, void* stream) {
-  return pddp::line_search_impl<float>(p, B, N, A, Z, U, gains, alphas, u_min,
-                                       u_max, active, bwd_status, Zc, Uc, Jc,
-                                       stream);
+  return pddp::line_search_impl<float>(p, false, nullptr, B, N, A, Z, U, gains,
+                                       alphas, u_min, u_max, active,
+                                       bwd_status, Zc, Uc, Jc, stream);
 }
 int pddp_line_search_f64(const pddp_problem* p, int B, int N, int A,
                          const double* Z, const double* U, const double* gains,
@@ -547,9 +514,65 @@ int pddp_line_search_f64(const pddp_problem* p, int B, int N, int A,
                          const double* u_max, const uint8_t* active,
                          const int32_t* bwd_status, double* Zc, double* Uc,
                          double* Jc, void* stream) {
-  return pddp::line_search_impl<double>(p, B, N, A, Z, U, gains, alphas, u_min,
-                                        u_max, active, bwd_status, Zc, Uc, Jc,
-                                        stream);
+  return pddp::line_search_impl<double>(p, false, nullptr, B, N, A, Z, U,
+                                        gains, alphas, u_min, u_max, active,
+                                        bwd_status, Zc, Uc, Jc, stream);
+}
+
+// the same with a problem per trajectory: row b of `table`
+int pddp_nominal_rollout_batch_f32(const pddp_problem* p, const float* table,
+                                   int B, int N, const float* z0,
+                                   const float* U, const float* u_min,
+                                   const float* u_max, const uint8_t* mask,
+                                   float* Z, void* stream) {
+  return pddp::nominal_rollout_impl<float>(p, true, table, B, N, z0, U, u_min,
+                                           u_max, mask, Z, stream);
+}
+int pddp_nominal_rollout_batch_f64(const pddp_problem* p, const double* table,
+                                   int B, int N, const double* z0,
+                                   const double* U, const double* u_min,
+                                   const double* u_max, const uint8_t* mask,
+                                   double* Z, void* stream) {
+  return pddp::nominal_rollout_impl<double>(p, true, table, B, N, z0, U,
+                                            u_min, u_max, mask, Z, stream);
+}
+int pddp_derivs_batch_f32(const pddp_problem* p, const float* table, int B,
+                          int N, const float* Z, const float* U,
+                          const float* u_min, const float* u_max,
+                          const uint8_t* mask, float* rec, float* L, float* J,
+                          int32_t* state, void* stream) {
+  return pddp::derivs_impl<float>(p, true, table, B, N, Z, U, u_min, u_max,
+                                  mask, rec, L, J, state, stream);
+}
+int pddp_derivs_batch_f64(const pddp_problem* p, const double* table, int B,
+                          int N, const double* Z, const double* U,
+                          const double* u_min, const double* u_max,
+                          const uint8_t* mask, double* rec, double* L,
+                          double* J, int32_t* state, void* stream) {
+  return pddp::derivs_impl<double>(p, true, table, B, N, Z, U, u_min, u_max,
+                                   mask, rec, L, J, state, stream);
+}
+int pddp_line_search_batch_f32(const pddp_problem* p, const float* table,
+                               int B, int N, int A, const float* Z,
+                               const float* U, const float* gains,
+                               const float* alphas, const float* u_min,
+                               const float* u_max, const uint8_t* active,
+                               const int32_t* bwd_status, float* Zc, float* Uc,
+                               float* Jc, void* stream) {
+  return pddp::line_search_impl<float>(p, true, table, B, N, A, Z, U, gains,
+                                       alphas, u_min, u_max, active,
+                                       bwd_status, Zc, Uc, Jc, stream);
+}
+int pddp_line_search_batch_f64(const pddp_problem* p, const double* table,
+                               int B, int N, int A, const double* Z,
+                               const double* U, const double* gains,
+                               const double* alphas, const double* u_min,
+                               const double* u_max, const uint8_t* active,
+                               const int32_t* bwd_status, double* Zc,
+                               double* Uc, double* Jc, void* stream) {
+  return pddp::line_search_impl<double>(p, true, table, B, N, A, Z, U, gains,
+                                        alphas, u_min, u_max, active,
+                                        bwd_status, Zc, Uc, Jc, stream);
 }
 
 }  // extern "C"

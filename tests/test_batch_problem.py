@@ -1,5 +1,5 @@
 """Per-trajectory problems (ILQRSolver.set_batch_problem, the pddp_*_batch_*
-entry points of csrc/batch_problem.hip): every trajectory of the batch with
+entry points of csrc/problem_kernels.hip): every trajectory of the batch with
 its own model parameters and goals, against the CPU oracle run once per
 trajectory on that trajectory's own problem.
 

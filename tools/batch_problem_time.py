@@ -1,5 +1,5 @@
-"""What a per-trajectory problem costs (ILQRSolver.set_batch_problem,
-csrc/batch_problem.hip): cartpole f32, 4096 trajectories, horizon 100,
+"""What a per-trajectory problem costs (ILQRSolver.set_batch_problem, the
+batch_* kernels of csrc/problem_kernels.hip): cartpole f32, 4096 trajectories, horizon 100,
 bounded, the fit's ten step sizes; every row of the table is the shared
 problem, so both forms do the same work on the same buffers.
 
@@ -11,7 +11,16 @@ problem, so both forms do the same work on the same buffers.
     round's launch sequence with the uniform kernels), and the round with the
     table; pddp_event_record around each round.
 
-WARM warm-up launches, median of REPS: python tools/batch_problem_time.py [B]"""
+  - with --against LIB, first of all: the six launches of the problem
+    kernels (nominal rollout, records and the plain search - one lane per
+    trajectory and step size -, each with one problem and with the table) in
+    the loaded build (PDDP_HIP_LIB, else the tree's) and in the build LIB,
+    alternating launch by launch on the same buffers, events attached to the
+    dispatch itself.  A build holds its own if its median is not above the
+    other's maximum over the same repetitions.
+
+WARM warm-up launches, median of REPS:
+    python tools/batch_problem_time.py [B] [--against LIB]"""
 import ctypes
 import os
 import sys
@@ -23,7 +32,9 @@ from pddp_amd.controllers.solver import ILQRSolver
 from pddp_amd.examples import cartpole
 from pddp_amd.utils.encoding import StateEncoding
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+B = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 4096
+AGAINST = sys.argv[sys.argv.index("--against") + 1] \
+    if "--against" in sys.argv else None
 N, WARM, REPS = 100, 5, 20
 td = torch.float32
 lib = _native.lib()
@@ -78,8 +89,52 @@ print("candidates, steps 0 .. 8: largest deviation %.2e of the largest entry"
       % dev)
 assert dev < 2e-4
 e0, e1 = event(), event()
-times = {"uniform": [], "batch": []}
 table = s.batch_table
+
+# -- the problem kernels, this build against another --------------------------
+if AGAINST:
+    other = ctypes.CDLL(AGAINST)
+    p, st = _native.ptr, s._s()
+    A17 = 17  # (above 16 step sizes the uniform entry point runs the plain kernel)
+    al17 = torch.linspace(1.0, 0.01, A17).to(td).cuda()
+    Zc17 = torch.empty(B, N + 1, A17, 4, dtype=td, device="cuda")
+    Uc17 = torch.empty(B, N, A17, 1, dtype=td, device="cuda")
+    Jc17 = torch.empty(B, A17, dtype=td, device="cuda")
+    head = {"": (ctypes.addressof(s.problem),),
+            "_batch": (ctypes.addressof(s.problem), p(table))}
+    roll = (B, N, p(s.z0), p(s.U), p(s.u_min), p(s.u_max), None, p(s.Z), st)
+    der = (B, N, p(s.Z), p(s.U), p(s.u_min), p(s.u_max), None, p(s._rec),
+           p(s.L), p(s.J_opt), None, st)
+
+    def search(A, al, Zc, Uc, Jc):
+        return (B, N, A, p(s.Z), p(s.U), p(s.gains), p(al), p(s.u_min),
+                p(s.u_max), None, p(s.bwd_status), p(Zc), p(Uc), p(Jc), st)
+
+    for name, form, args in (
+            ("pddp_nominal_rollout", "", roll), ("pddp_derivs", "", der),
+            ("pddp_line_search", "", search(A17, al17, Zc17, Uc17, Jc17)),
+            ("pddp_nominal_rollout", "_batch", roll),
+            ("pddp_derivs", "_batch", der),
+            ("pddp_line_search", "_batch",
+             search(s.A, s.alphas, s.Zc, s.Uc, s.Jc))):
+        ts = {"this": [], "other": []}
+        for i in range(WARM + REPS):
+            for build, l in (("this", lib), ("other", other)):
+                fn = getattr(l, name + form + "_f32")
+                fn.argtypes = _native._SIGS[name + form]
+                l.pddp_attach_events.argtypes = [ctypes.c_void_p] * 2
+                l.pddp_attach_events(e0, e1)
+                _native.check(fn(*head[form], *args), name + form)
+                t = elapsed_us(e0, e1)
+                if i >= WARM:
+                    ts[build].append(t)
+        print("%s%s_f32%s, B %d N %d: this build %s; %s %s; %s" % (
+            name, form, ", A %d" % args[2] if "search" in name else "", B, N,
+            stats(ts["this"]), AGAINST, stats(ts["other"]),
+            "holds" if np.median(ts["this"]) <= max(ts["other"])
+            else "SLOWER"), flush=True)
+
+times = {"uniform": [], "batch": []}
 for i in range(WARM + REPS):
     for leg in ("uniform", "batch"):
         s.batch_table = table if leg == "batch" else None
