@@ -432,9 +432,10 @@ class ILQRSolver(object):
     @_on_device
     def backward(self, active=None, reg=None, branch=None, bounded=True,
                  variant=0, events=None):
-        """variant: 0 auto, 1 generic kernel, 2 / 3 specialised n=4 kernel
-        (IEEE / approximate division), 6 / 7 closed-form BoxQP, 8 / 9 split
-        over two wavefronts, see include/pddp_hip.h.  `events`: a
+        """variant: 0 auto, 1 generic kernel; n = 4: 6 / 7 sixteen lanes per
+        trajectory (IEEE / approximate division), 16 / 17 / 18 four lanes;
+        14 / 15 the matrix-core kernels (m = 1, n <= 30), 26 / 27 their step
+        split over two wavefronts - the list in csrc/riccati.hip.  `events`: a
         (start, stop) pair of pddp_event handles to attach to the dispatch."""
         self.sync_records()
         p = _native.ptr

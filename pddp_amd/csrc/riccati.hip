@@ -248,9 +248,10 @@ int pddp_riccati_backward_f64(int B, int N, int n, int m, const double* rec,
                                              reg, branch, active, gains,
                                              status, stream, 0);
 }
-/* Same sweep through a chosen kernel variant (A/B tests):
- * 0 auto, 1 generic one-wavefront-per-trajectory kernel, 2 specialised n=4/m=1
- * kernel, 3 the same with rcp/sqrt approximations (f32). */
+/* Same sweep through a chosen kernel variant (A/B tests): 0 auto,
+ * 1 the generic kernel, 6 / 7 and 16 / 17 / 18 the n = 4 sweeps, 14 / 15 the
+ * matrix-core kernels, 26 / 27 their two-wavefront split - the list at
+ * riccati_backward_impl. */
 int pddp_riccati_backward_variant_f32(int B, int N, int n, int m,
                                       const float* rec, const float* u_min,
                                       const float* u_max, const double* reg,

@@ -30,6 +30,13 @@
 // fp64: the f64 instruction's C/D layout puts row g + 4 r (not 4 g + r) in
 // register r of lane group g; with the k-slab of MFMA r taken as k = g + 4 r
 // everything above holds unchanged (`Tile<T>::row`).
+// Shared texts, each written once and included (riccati_mfma16_nominal.hpp
+// includes the same four): mfma_operand.inc (which record word an entry of
+// F~ / L~ reads), mfma16_products.inc (both products, row n, the regularised
+// row), mfma_gain_step.inc (the scalar gains; also riccati_mfma32.hpp and
+// riccati_mfma32s.hpp), mfma16_value_update.inc (V', V_z' from the tile).  The
+// step below keeps what is this kernel's own: the gathers at an immediate slot
+// offset, the tile's vector store, the wait for and the refill of the slot.
 #pragma once
 
 #include "riccati_n4.hpp"
@@ -120,25 +127,16 @@ __global__ __launch_bounds__(kWave * kWaves) void riccati_mfma16_kernel(
   T umin = T(0), umax = T(0);
   if constexpr (BOUNDED) { umin = a.u_min[0]; umax = a.u_max[0]; }
 
-  // ---- word offsets of this lane's operands inside a record (-1: zero)
+  // ---- word offsets of this lane's operands inside a record (S: the first
+  // word of the zeroed padding)
   int oF[4], oL[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int k = TL::row(g, r);  // F~ row / L~ row
-    oF[r] = (k < n) ? (j < n ? lay.oFz + k * n + j
-                             : (j == n ? lay.oFu + k : S))
-                    : S;  // (word S: the first word of the zeroed padding)
-    int o = S;
-    if (k < n) {
-      if (j < n) o = lay.oLzz + k * n + j;
-      else if (j == n) o = lay.oLuz + k;  // L_uz^T
-      else if (j == 15) o = lay.oLz + k;
-    } else if (k == n) {
-      if (j < n) o = lay.oLuz + j;
-      else if (j == n) o = lay.oLuu;
-      else if (j == 15) o = lay.oLu;
-    }
-    oL[r] = o;
+#define PDDP_OPERAND_F oF[r]
+#define PDDP_OPERAND_L oL[r]
+#define PDDP_OPERAND_JZ 15
+#include "mfma_operand.inc"
   }
   // Cholesky branch (ilqr.py:587-625): Q_uu, Q_uz once more with V + reg I,
   // i.e. + reg f^T F~ (row n of F~^T F~): this lane's share needs f[4g + r]
@@ -216,34 +214,9 @@ __global__ __launch_bounds__(kWave * kWaves) void riccati_mfma16_kernel(
       La[r] = pL[r][so];
     }
     const T Un = BOUNDED ? pU[so] : T(0);
-    T ffrow = T(0);  // (f^T F~)[j]: f^T F_z for j < n, f.f at j = n
-    if constexpr (CHOL) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ffrow += pFf[r][so] * Fa[r];
-      ffrow += __shfl_xor(ffrow, 16);
-      ffrow += __shfl_xor(ffrow, 32);
-    }
-
-    // ---- X = V F~ ; X[:, 15] = V_z (column 15 of F~ is zero)
-    Acc X = {Vz[0], Vz[1], Vz[2], Vz[3]};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) X = TL::mma(V[r], Fa[r], X);
-    // ---- Q~ = L~ + F~^T X
-    Acc Q = {La[0], La[1], La[2], La[3]};
-    Q = TL::mma(Fa[0], X[0], Q);
-    Q = TL::mma(Fa[1], X[1], Q);
-    Q = TL::mma(Fa[2], X[2], Q);
-    Q = TL::mma(Fa[3], X[3], Q);
-
-    // row n (register rn of lane group gn) of Q~ is (Q_uz | Q_uu | Q_u at
-    // column 15)
-    const int gn = TL::group_of(n), rn = TL::reg_of(n);
-    const T rowv = rn == 0 ? Q[0] : (rn == 1 ? Q[1] : (rn == 2 ? Q[2] : Q[3]));
-    const T Quu = TL::read_lane(rowv, gn * 16 + n);
-    const T Qu = TL::read_lane(rowv, gn * 16 + 15);
-    // the regularised row (Q_uz_reg | Q_uu_reg) of the Cholesky branch
-    const T rowg = CHOL ? rowv + reg * ffrow : rowv;
-    const T Quug = CHOL ? TL::read_lane(rowg, gn * 16 + n) : Quu;
+#define PDDP_M16_F(r) pFf[r][so]
+#define PDDP_M16_ROW_N_HERE
+#include "mfma16_products.inc"
     // transpose tile: T[col][row] = Q~[row][col]; row 15 (free: n + 1 <= 15)
     // carries Q_uz_reg
     if constexpr (sizeof(T) == 4) {
@@ -256,52 +229,14 @@ __global__ __launch_bounds__(kWave * kWaves) void riccati_mfma16_kernel(
       if (g == gn) tile[j * 16 + 15] = rowg;
     }
 
-    // ---- gains (every lane the same scalars)                 (ilqr.py:629-657)
-    int st = PDDP_BWD_OK;
-    T qp_Q;
-    if constexpr (CHOL) {
-      qp_Q = Quug;  // Cholesky of Q_uu_reg                        (ilqr.py:595)
-      if (!BOUNDED && (!(Quug > T(0)) || !is_finite(Quug))) st = PDDP_BWD_NOT_PD;
-    } else {
-      if (!is_finite(Quu)) st = PDDP_BWD_NAN;     // eig raises (ilqr.py:631)
-      const T e = (Quu < T(0)) ? T(1e-12) : Quu;  // ilqr.py:633
-      qp_Q = e + reg;                             // ilqr.py:634
-    }
-    T kt, sE;
-    bool Kz = false;
-    int stt = st;
-    if constexpr (BOUNDED) {
-      n4::QpClosed<T, FAST> qc;
-      qc.solve(kprev, qp_Q, Qu, umin - Un, umax - Un);
-      kt = qc.x;
-      Kz = !qc.free_;
-      bool fail = qc.fail;
-      if (__builtin_amdgcn_ballot_w64(qc.slow) != 0) {
-        const n4::SlowQpOut<T> o = n4::boxqp1_outlined<T, FAST>(
-            kprev, qp_Q, Qu, umin - Un, umax - Un, lstep0, ls_tail, lane);
-        kt = o.x;
-        Kz = (o.result_free & 1) == 0;
-        fail = o.result_free < 2;
-      }
-      // (a NaN Q_uu fails `eig` before the BoxQP is reached, ilqr.py:631)
-      if (fail && st == PDDP_BWD_OK) stt = PDDP_BWD_BOXQP_FAILED;
-      if constexpr (FAST) sE = Kz ? T(0) : qc.inv;
-      else sE = Kz ? T(0) : n4::div_<false>(n4::div_<false>(T(1), qc.U), qc.U);
-    } else {
-      sE = n4::div_<FAST>(T(1), qp_Q);  // (E / e) E^T             (ilqr.py:636)
-      kt = -(sE * Qu);
-      // NaN in k or K raises (ilqr.py:639-640)
-      const bool nanK = (g == gn) && (j < n) && (sE * rowg != sE * rowg);
-      if (!CHOL && (kt != kt || __builtin_amdgcn_ballot_w64(nanK) != 0))
-        stt = PDDP_BWD_NAN;
-    }
-    if (status == PDDP_BWD_OK && stt != PDDP_BWD_OK) status = stt;
-    kprev = kt;
+#define PDDP_GAIN_ROW g == gn
+#define PDDP_GAIN_COL j
+#define PDDP_GAIN_KROW rowg
+#include "mfma_gain_step.inc"
     const T c = sE * (sE * Quu - T(2));
     const T w = kt - sE * (Qu + Quu * kt);
     const T c2 = sE * sE * Quu;        // Cholesky branch: K = -sE Q_uz_reg
     const T wz = sE * (Qu + Quu * kt);
-
     // ---- k, K of step t: lanes of row n hold Q_uz[j] (j < n), lane j = n: k
     {
       const T val = (j < n) ? -(sE * rowg) : kt;
@@ -311,28 +246,7 @@ __global__ __launch_bounds__(kWave * kWaves) void riccati_mfma16_kernel(
     // this slot is consumed: refill it, kRing steps further down the sweep
     dma(slot, t - kRing);
 
-    // ---- V' = sym(Q_zz) + c Q_uz^T Q_uz,  V_z' = Q_z + Q_uz^T w
-    const T Quz_j = tile[j * 16 + n];  // Q~[n][j]
-    const T Qg_j = CHOL ? tile[j * 16 + 15] : T(0);  // Q_uz_reg[j]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int k = TL::row(g, r);
-      const T QT = tile[k * 16 + j];      // Q~[j][k]
-      const T Quz_k = tile[k * 16 + n];   // Q~[n][k]
-      const T sym = T(0.5) * (Q[r] + QT);
-      if constexpr (CHOL) {
-        // V' = sym + K^T Quu K + K^T Quz + Quz^T K,  K = -sE Q_uz_reg
-        const T Qg_k = tile[k * 16 + 15];
-        const T v = sym + c2 * (Qg_k * Qg_j) - sE * (Qg_k * Quz_j + Quz_k * Qg_j);
-        // (no masks on V', V_z': their entries outside the n x n block only
-        // ever meet zero rows / columns of F~ in the next step's products)
-        V[r] = v;
-        Vz[r] = (j == 15) ? Q[r] + Quz_k * kt - Qg_k * wz : T(0);
-      } else {
-        V[r] = n4::fma_(c * Quz_k, Quz_j, sym);
-        Vz[r] = (j == 15) ? n4::fma_(Quz_k, w, Q[r]) : T(0);
-      }
-    }
+#include "mfma16_value_update.inc"
   };
   // record tau lives in slot (N - 1 - tau) % kRing
   int t = N - 1;

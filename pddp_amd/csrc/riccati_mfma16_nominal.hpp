@@ -18,6 +18,10 @@
 // slot (t mod RB); a record costs a lane 300 .. 1500 instructions, 5 .. 25 per
 // step of the sweep.  Stage costs go to LDS and from there to L [B][N + 1];
 // J_opt = their sum in t order (ilqr.py:289) where `fresh` is set.
+// The step is riccati_mfma16.hpp's, from the same included texts
+// (mfma_operand.inc, mfma16_products.inc, mfma_gain_step.inc,
+// mfma16_value_update.inc); its own are the gathers at a run-time slot, the
+// tile's scalar stores and the LDS fences.
 #pragma once
 
 #include "models.hpp"
@@ -110,20 +114,10 @@ __global__ __launch_bounds__(kWave * kWaves) void riccati_mfma16_nominal_kernel(
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int k = TL::row(g, r);
-    oF[r] = (k < n) ? (j < n ? lay.oFz + k * n + j
-                             : (j == n ? lay.oFu + k : S))
-                    : S;
-    int o = S;
-    if (k < n) {
-      if (j < n) o = lay.oLzz + k * n + j;
-      else if (j == n) o = lay.oLuz + k;  // L_uz^T
-      else if (j == 15) o = lay.oLz + k;
-    } else if (k == n) {
-      if (j < n) o = lay.oLuz + j;
-      else if (j == n) o = lay.oLuu;
-      else if (j == 15) o = lay.oLu;
-    }
-    oL[r] = o;
+#define PDDP_OPERAND_F oF[r]
+#define PDDP_OPERAND_L oL[r]
+#define PDDP_OPERAND_JZ 15
+#include "mfma_operand.inc"
     oFf[r] = (k < n) ? lay.oFu + k : S;
   }
 
@@ -145,7 +139,6 @@ __global__ __launch_bounds__(kWave * kWaves) void riccati_mfma16_nominal_kernel(
   int status = PDDP_BWD_OK;
   const int gn = TL::group_of(n), rn = TL::reg_of(n);
   // one step of the sweep on the record in ring slot `slot`
-  // (riccati_mfma16.hpp's, the operands gathered at a run-time slot offset)
   auto step = [&](const int t, const int slot) {
     const T* R = ring + slot * SW;
     T Fa[4], La[4];
@@ -155,28 +148,8 @@ __global__ __launch_bounds__(kWave * kWaves) void riccati_mfma16_nominal_kernel(
       La[r] = R[oL[r]];
     }
     const T Un = BOUNDED ? R[lay.oU] : T(0);
-    T ffrow = T(0);  // (f^T F~)[j]: f^T F_z for j < n, f.f at j = n
-    if constexpr (CHOL) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ffrow += R[oFf[r]] * Fa[r];
-      ffrow += __shfl_xor(ffrow, 16);
-      ffrow += __shfl_xor(ffrow, 32);
-    }
-    // ---- X = V F~ ; X[:, 15] = V_z ;  Q~ = L~ + F~^T X
-    Acc X = {Vz[0], Vz[1], Vz[2], Vz[3]};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) X = TL::mma(V[r], Fa[r], X);
-    Acc Q = {La[0], La[1], La[2], La[3]};
-    Q = TL::mma(Fa[0], X[0], Q);
-    Q = TL::mma(Fa[1], X[1], Q);
-    Q = TL::mma(Fa[2], X[2], Q);
-    Q = TL::mma(Fa[3], X[3], Q);
-
-    const T rowv = rn == 0 ? Q[0] : (rn == 1 ? Q[1] : (rn == 2 ? Q[2] : Q[3]));
-    const T Quu = TL::read_lane(rowv, gn * 16 + n);
-    const T Qu = TL::read_lane(rowv, gn * 16 + 15);
-    const T rowg = CHOL ? rowv + reg * ffrow : rowv;
-    const T Quug = CHOL ? TL::read_lane(rowg, gn * 16 + n) : Quu;
+#define PDDP_M16_F(r) R[oFf[r]]
+#include "mfma16_products.inc"
     // transpose tile: T[col][row] = Q~[row][col]; row 15 carries Q_uz_reg
 #pragma unroll
     for (int r = 0; r < 4; ++r) tile[j * 16 + TL::row(g, r)] = Q[r];
@@ -184,72 +157,22 @@ __global__ __launch_bounds__(kWave * kWaves) void riccati_mfma16_nominal_kernel(
       if (g == gn) tile[j * 16 + 15] = rowg;
     }
 
-    // ---- gains (every lane the same scalars)                 (ilqr.py:629-657)
-    int st = PDDP_BWD_OK;
-    T qp_Q;
-    if constexpr (CHOL) {
-      qp_Q = Quug;  // Cholesky of Q_uu_reg                        (ilqr.py:595)
-      if (!BOUNDED && (!(Quug > T(0)) || !is_finite(Quug))) st = PDDP_BWD_NOT_PD;
-    } else {
-      if (!is_finite(Quu)) st = PDDP_BWD_NAN;     // eig raises (ilqr.py:631)
-      const T e = (Quu < T(0)) ? T(1e-12) : Quu;  // ilqr.py:633
-      qp_Q = e + reg;                             // ilqr.py:634
-    }
-    T kt, sE;
-    int stt = st;
-    if constexpr (BOUNDED) {
-      n4::QpClosed<T, FAST> qc;
-      qc.solve(kprev, qp_Q, Qu, umin - Un, umax - Un);
-      kt = qc.x;
-      bool Kz = !qc.free_, fail = qc.fail;
-      if (__builtin_amdgcn_ballot_w64(qc.slow) != 0) {
-        const n4::SlowQpOut<T> o = n4::boxqp1_outlined<T, FAST>(
-            kprev, qp_Q, Qu, umin - Un, umax - Un, lstep0, ls_tail, lane);
-        kt = o.x;
-        Kz = (o.result_free & 1) == 0;
-        fail = o.result_free < 2;
-      }
-      // (a NaN Q_uu fails `eig` before the BoxQP is reached, ilqr.py:631)
-      if (fail && st == PDDP_BWD_OK) stt = PDDP_BWD_BOXQP_FAILED;
-      if constexpr (FAST) sE = Kz ? T(0) : qc.inv;
-      else sE = Kz ? T(0) : n4::div_<false>(n4::div_<false>(T(1), qc.U), qc.U);
-    } else {
-      sE = n4::div_<FAST>(T(1), qp_Q);  // (E / e) E^T             (ilqr.py:636)
-      kt = -(sE * Qu);
-      const bool nanK = (g == gn) && (j < n) && (sE * rowg != sE * rowg);
-      if (!CHOL && (kt != kt || __builtin_amdgcn_ballot_w64(nanK) != 0))
-        stt = PDDP_BWD_NAN;
-    }
-    if (status == PDDP_BWD_OK && stt != PDDP_BWD_OK) status = stt;
-    kprev = kt;
+#define PDDP_GAIN_ROW g == gn
+#define PDDP_GAIN_COL j
+#define PDDP_GAIN_KROW rowg
+#include "mfma_gain_step.inc"
     const T c = sE * (sE * Quu - T(2));
     const T w = kt - sE * (Qu + Quu * kt);
     const T c2 = sE * sE * Quu;        // Cholesky branch: K = -sE Q_uz_reg
     const T wz = sE * (Qu + Quu * kt);
-    {  // k, K of step t
+    // ---- k, K of step t: lanes of row n hold Q_uz[j] (j < n), lane j = n: k
+    {
       const T val = (j < n) ? -(sE * rowg) : kt;
       T* dst = gains_b + (size_t)t * lay.gstride + (j < n ? 1 + j : 0);
       if (g == gn && j <= n) *dst = val;
     }
-    // ---- V' = sym(Q_zz) + c Q_uz^T Q_uz,  V_z' = Q_z + Q_uz^T w
     lds_fence();
-    const T Quz_j = tile[j * 16 + n];  // Q~[n][j]
-    const T Qg_j = CHOL ? tile[j * 16 + 15] : T(0);  // Q_uz_reg[j]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int k = TL::row(g, r);
-      const T QT = tile[k * 16 + j];      // Q~[j][k]
-      const T Quz_k = tile[k * 16 + n];   // Q~[n][k]
-      const T sym = T(0.5) * (Q[r] + QT);
-      if constexpr (CHOL) {
-        const T Qg_k = tile[k * 16 + 15];
-        V[r] = sym + c2 * (Qg_k * Qg_j) - sE * (Qg_k * Quz_j + Quz_k * Qg_j);
-        Vz[r] = (j == 15) ? Q[r] + Quz_k * kt - Qg_k * wz : T(0);
-      } else {
-        V[r] = n4::fma_(c * Quz_k, Quz_j, sym);
-        Vz[r] = (j == 15) ? n4::fma_(Quz_k, w, Q[r]) : T(0);
-      }
-    }
+#include "mfma16_value_update.inc"
     lds_fence();  // (the tile is written again by the next step)
   };
   for (int t = N - 1; t >= 0; --t) {

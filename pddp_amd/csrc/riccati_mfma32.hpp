@@ -12,6 +12,12 @@
 // product when the k-slot h of instruction r is taken to be that row; X's
 // registers are then the B operand of Q~ = L~ + F~^T X, and the sixteen F~
 // words a lane gathers serve both products (see riccati_mfma16.hpp).
+// The scalar gains of a step are mfma_gain_step.inc, the text the 16x16
+// kernels include.  The operand map below is mfma_operand.inc's function of
+// (k, j) with column 31 for the first-order terms, but stays written here: it
+// marks entries outside the matrices with -1 first, and the shared form (word
+// S at once) compiles to other set-up code; `mK` and the fallback word of
+// `oFf` are this kernel's own in any case.
 #pragma once
 
 #include <type_traits>
@@ -233,50 +239,14 @@ __global__ __launch_bounds__(kThreads) void riccati_mfma32_kernel(
       if (h == hn) tile[j * kTileLd + 31] = rowg;
     }
 
-    // ---- gains (every lane the same scalars)                 (ilqr.py:629-657)
-    int st = PDDP_BWD_OK;
-    T qp_Q;
-    if constexpr (CHOL) {
-      qp_Q = Quug;  // Cholesky of Q_uu_reg                        (ilqr.py:595)
-      if (!BOUNDED && (!(Quug > T(0)) || !is_finite(Quug))) st = PDDP_BWD_NOT_PD;
-    } else {
-      if (!is_finite(Quu)) st = PDDP_BWD_NAN;     // eig raises (ilqr.py:631)
-      const T e = (Quu < T(0)) ? T(1e-12) : Quu;  // ilqr.py:633
-      qp_Q = e + reg;                             // ilqr.py:634
-    }
-    T kt, sE;
-    int stt = st;
-    if constexpr (BOUNDED) {
-      n4::QpClosed<T, FAST> qc;
-      qc.solve(kprev, qp_Q, Qu, umin - Un, umax - Un);
-      kt = qc.x;
-      bool Kz = !qc.free_, fail = qc.fail;
-      if (__builtin_amdgcn_ballot_w64(qc.slow) != 0) {
-        const n4::SlowQpOut<T> o = n4::boxqp1_outlined<T, FAST>(
-            kprev, qp_Q, Qu, umin - Un, umax - Un, lstep0, ls_tail, lane);
-        kt = o.x;
-        Kz = (o.result_free & 1) == 0;
-        fail = o.result_free < 2;
-      }
-      // (a NaN Q_uu fails `eig` before the BoxQP is reached, ilqr.py:631)
-      if (fail && st == PDDP_BWD_OK) stt = PDDP_BWD_BOXQP_FAILED;
-      if constexpr (FAST) sE = Kz ? T(0) : qc.inv;
-      else sE = Kz ? T(0) : n4::div_<false>(n4::div_<false>(T(1), qc.U), qc.U);
-    } else {
-      sE = n4::div_<FAST>(T(1), qp_Q);  // (E / e) E^T             (ilqr.py:636)
-      kt = -(sE * Qu);
-      // NaN in k or K raises (ilqr.py:639-640)
-      const bool nanK = (h == hn) && (j < n) && (sE * rowg != sE * rowg);
-      if (!CHOL && (kt != kt || __builtin_amdgcn_ballot_w64(nanK) != 0))
-        stt = PDDP_BWD_NAN;
-    }
-    if (status == PDDP_BWD_OK && stt != PDDP_BWD_OK) status = stt;
-    kprev = kt;
+#define PDDP_GAIN_ROW h == hn
+#define PDDP_GAIN_COL j
+#define PDDP_GAIN_KROW rowg
+#include "mfma_gain_step.inc"
     const T c = sE * (sE * Quu - T(2));
     const T w = kt - sE * (Qu + Quu * kt);
     const T c2 = sE * sE * Quu;        // Cholesky branch: K = -sE Q_uz_reg
     const T wz = sE * (Qu + Quu * kt);
-
     // ---- k, K of step t: lanes of row n hold Q_uz[j] (j < n), lane j = n: k
     {
       const T val = (j < n) ? -(sE * rowg) : kt;

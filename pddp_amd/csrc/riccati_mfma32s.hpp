@@ -41,7 +41,11 @@
 // step pair - 2 x (896 matrix + ~800 other) cycles at n = 27 - is what the
 // sweep takes.)
 // Eig-clamp branches (B, D: the controller's default); the Cholesky branches
-// stay on the one-wave kernel.
+// stay on the one-wave kernel.  The scalar gains are mfma_gain_step.inc (CHOL =
+// false), shared with the other matrix-core sweeps.  The operand map is the
+// same function of (k, j) as mfma_operand.inc's, applied to PERMUTED indices
+// (lg below) and with two columns per row for F~: it stays written here, in
+// riccati_mfma32.hpp's -1 form.
 #pragma once
 
 #include "riccati_mfma32.hpp"
@@ -311,42 +315,17 @@ __global__ __launch_bounds__(kThreads) void riccati_mfma32s_kernel(
     }
     const f32x4 Qz = *reinterpret_cast<const f32x4*>(
         tile + 31 * kTileLd + 16 * W + 4 * g);  // Q~[16 w + 4 g + r][31]
-    // gains (every lane the same scalars)                      (ilqr.py:629-657)
-    int st = PDDP_BWD_OK;
-    if (!is_finite(Quu)) st = PDDP_BWD_NAN;     // eig raises (ilqr.py:631)
-    const T e = (Quu < T(0)) ? T(1e-12) : Quu;  // ilqr.py:633
-    const T qp_Q = e + reg;                     // ilqr.py:634
-    T kt, sE;
-    int stt = st;
-    if constexpr (BOUNDED) {
-      n4::QpClosed<T, FAST> qc;
-      qc.solve(kprev, qp_Q, Qu, umin - Un, umax - Un);
-      kt = qc.x;
-      bool Kz = !qc.free_, fail = qc.fail;
-      if (__builtin_amdgcn_ballot_w64(qc.slow) != 0) {
-        const n4::SlowQpOut<T> o = n4::boxqp1_outlined<T, FAST>(
-            kprev, qp_Q, Qu, umin - Un, umax - Un, lstep0, ls_tail, lane);
-        kt = o.x;
-        Kz = (o.result_free & 1) == 0;
-        fail = o.result_free < 2;
-      }
-      // (a NaN Q_uu fails `eig` before the BoxQP is reached, ilqr.py:631)
-      if (fail && st == PDDP_BWD_OK) stt = PDDP_BWD_BOXQP_FAILED;
-      if constexpr (FAST) sE = Kz ? T(0) : qc.inv;
-      else sE = Kz ? T(0) : n4::div_<false>(n4::div_<false>(T(1), qc.U), qc.U);
-    } else {
-      sE = n4::div_<FAST>(T(1), qp_Q);  // (E / e) E^T             (ilqr.py:636)
-      kt = -(sE * Qu);
-      // NaN in k or K raises (ilqr.py:639-640)
-      const bool nanK = (g == gn) && (jl < n) && (sE * Quz_j != sE * Quz_j);
-      // (the partner sees its own columns only: the statuses are merged below)
-      if (kt != kt || __builtin_amdgcn_ballot_w64(nanK) != 0) stt = PDDP_BWD_NAN;
-    }
-    if (status == PDDP_BWD_OK && stt != PDDP_BWD_OK) status = stt;
-    kprev = kt;
+    // (eig-clamp only.  In the unbounded branch's NaN test of K the partner
+    // sees its own columns only: the statuses are merged below)
+    constexpr bool CHOL = false;
+    const T Quug = Quu;
+#define PDDP_GAIN_ROW g == gn
+#define PDDP_GAIN_COL jl
+#define PDDP_GAIN_KROW Quz_j
+#include "mfma_gain_step.inc"
     const T cc = sE * (sE * Quu - T(2));
     const T wc = kt - sE * (Qu + Quu * kt);
-    // k, K of step t: this wave's columns of row n
+    // ---- k, K of step t: lanes of row n hold Q_uz[j] (j < n), lane j = n: k
     {
       const T val = (jl < n) ? -(sE * Quz_j) : kt;
       T* dst = gains_b + (size_t)t * lay.gstride + (jl < n ? 1 + jl : 0);
