@@ -395,6 +395,33 @@ int pddp_sweep_nominal_f64(const pddp_problem* problem, int B, int N,
  * test knob); -1 only queries.  Returns the previous choice. */
 int pddp_sweep_nominal_kernel(int which);
 
+/* What a cartpole launch of pddp_sweep_nominal_f32 / _f64 (rounds == 0) or of
+ * pddp_round_nominal_f32 (rounds != 0) looks like for these arguments: the
+ * plan every such launch is made from (csrc/riccati_n4_elem.hpp,
+ * n4_nominal_plan).  element_size 4 or 8; has_u_min / has_u_max: whether that
+ * bound is given; kernel_choice: as pddp_sweep_nominal_kernel (the sweep's;
+ * the round ignores it); A is looked at for the round only.  Returns what the
+ * launch returns before its first HIP call - 0, PDDP_E_BADARG, or
+ * PDDP_E_UNSUPPORTED for everything the cartpole's kernels do not serve (other
+ * models and encodings among it) - and with 0 writes plan[PDDP_N4_PLAN_*].
+ * Host function: no HIP call. */
+enum {
+  PDDP_N4_PLAN_BRANCH = 0,  /* 0 eig-clamp bounded, 1 eig-clamp unbounded,
+                             * 2 V_zz-regularised unbounded, 3 ... bounded */
+  PDDP_N4_PLAN_SPARSE = 1,  /* stage cost on {x, sin, cos} only (else full) */
+  PDDP_N4_PLAN_OVERLAP = 2, /* record generator on wavefronts of its own */
+  PDDP_N4_PLAN_MULTI = 3,   /* round: several rounds per launch */
+  PDDP_N4_PLAN_CARRY = 4,   /* round: the nominal's last rows stay in LDS */
+  PDDP_N4_PLAN_GRID = 5,    /* workgroups */
+  PDDP_N4_PLAN_THREADS = 6, /* threads per workgroup */
+  PDDP_N4_PLAN_LDS = 7,     /* dynamic LDS, bytes */
+  PDDP_N4_PLAN_FIELDS = 8
+};
+int pddp_n4_nominal_plan(const pddp_problem* problem, int element_size, int B,
+                         int N, int A, int has_u_min, int has_u_max,
+                         int branch, int rounds, int kernel_choice,
+                         int32_t* plan);
+
 /* ---- one launch for the rest of a round: the line search, the accept step
  * and the derivative records of the trajectories whose nominal changed and
  * whose fit goes on.  Same arguments and semantics as the three calls; Z, U, active are

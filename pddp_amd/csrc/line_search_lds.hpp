@@ -177,7 +177,7 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
   // CartpoleCost's live rows {x, sin, cos} - the configuration it is built for
   constexpr bool kPaired = PRE && MODEL == PDDP_MODEL_CARTPOLE &&
                            std::is_same<T, float>::value && GST == 6 &&
-                           QM == 0b11001u;
+                           QM == kSparseMask<PDDP_MODEL_CARTPOLE>;
   __shared__ int sh_dec[WPB][4][2];  // H = 2: {amin_out, fresh} per trajectory
   const int lane = tid & (kWave - 1);
   const int wave_all = tid >> 6;

@@ -475,6 +475,12 @@ inline unsigned live_mask(const double* Q, int na) {
 }
 template <int MODEL>
 constexpr unsigned kFullMask = (1u << ModelDims<MODEL>::na) - 1u;
+// The one sparse stage-cost pattern instantiated per model: the shipped
+// example cost's (CartpoleCost: {x, sin, cos}).  Models without a sparse
+// instantiation: the full mask.
+template <int MODEL>
+constexpr unsigned kSparseMask =
+    MODEL == PDDP_MODEL_CARTPOLE ? 0b11001u : kFullMask<MODEL>;
 
 // Cost value only (line search, ilqr.py:764-791). u == nullptr <=> terminal.
 // QM: the live rows / columns of the matrix (live_mask); the terms dropped are

@@ -5,6 +5,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/pddp_hip.h"
 
 #define PDDP_DEV __device__ __forceinline__
@@ -95,6 +97,21 @@ inline LaunchEvents& launch_events() {
 inline int launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
+}
+
+// A launch with `lds_bytes` of dynamic LDS, which may exceed the 64 KB a
+// kernel gets by default: allow it (on every call), then launch through
+// PDDP_LAUNCH.  The arguments convert to the kernel's parameter types here.
+template <typename... P>
+int launch_dyn_lds(void (*kernel)(P...), dim3 grid, dim3 block,
+                   size_t lds_bytes, hipStream_t st,
+                   std::common_type_t<P>... args) {
+  const hipError_t e = hipFuncSetAttribute(
+      (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+      (int)lds_bytes);
+  if (e != hipSuccess) return (int)e;
+  PDDP_LAUNCH(kernel, grid, block, lds_bytes, st, args...);
+  return launch_status();
 }
 
 }  // namespace pddp

@@ -150,13 +150,9 @@ __global__ __launch_bounds__(kWave) void batch_line_search_kernel(
 // --------------------------------------------------------------------------
 // launchers
 // --------------------------------------------------------------------------
-// The one sparse stage-cost pattern instantiated per model: the shipped
-// example cost's (cartpole: {x, sin, cos}); a cost matrix with entries outside
-// it runs the full form.  Models without a sparse instantiation: the full mask
-// (the dispatch below then folds to one launch).
-template <int MODEL>
-constexpr unsigned kSparseMask =
-    MODEL == PDDP_MODEL_CARTPOLE ? 0b11001u : kFullMask<MODEL>;
+// (kSparseMask, models.hpp: a cost matrix with entries outside it runs the
+// full form; for a model without a sparse instantiation the dispatch below
+// folds to one launch)
 template <int MODEL, unsigned QM>
 static bool stage_cost_on(const pddp_problem& p) {
   if (QM == kFullMask<MODEL>) return false;

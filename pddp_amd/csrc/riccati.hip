@@ -38,13 +38,8 @@ static int dispatch_nmax(const RiccatiArgs<T>& a, hipStream_t st) {
   // 160 KB; f32 reaches n = 114, f64 n = 80.
   const size_t bytes = riccati_lds_elems(a.n, M) * sizeof(T);
   if (bytes > 160 * 1024) return PDDP_E_UNSUPPORTED;
-  auto kernel = riccati_large_kernel<T, M>;
-  const hipError_t e = hipFuncSetAttribute(
-      (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-      (int)bytes);
-  if (e != hipSuccess) return (int)e;
-  PDDP_LAUNCH(kernel, dim3(a.B), dim3(kLargeThreads), bytes, st, a);
-  return launch_status();
+  return launch_dyn_lds(riccati_large_kernel<T, M>, dim3(a.B),
+                        dim3(kLargeThreads), bytes, st, a);
 }
 
 template <typename T>

@@ -221,18 +221,12 @@ static int launch_m16_nominal_model(const pddp_problem& p,
   const bool chol = a.branch == PDDP_BRANCH_CHOLESKY;
   constexpr bool FAST = sizeof(T) == 4;
 #define PDDP_M16N_GO(Bd, C)                                                    \
-  do {                                                                         \
-    auto kern = m16n::riccati_mfma16_nominal_kernel<T, MODEL, Bd, FAST, C, RB>; \
-    const hipError_t e_ = hipFuncSetAttribute(                                 \
-        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-        (int)lds);                                                             \
-    if (e_ != hipSuccess) return (int)e_;                                      \
-    PDDP_LAUNCH(kern, grid, block, lds, st, a, gen, P);                        \
-  } while (0)
+  return launch_dyn_lds(                                                       \
+      m16n::riccati_mfma16_nominal_kernel<T, MODEL, Bd, FAST, C, RB>, grid,    \
+      block, lds, st, a, gen, P)
   if (bounded) { if (chol) PDDP_M16N_GO(true, true); else PDDP_M16N_GO(true, false); }
   else { if (chol) PDDP_M16N_GO(false, true); else PDDP_M16N_GO(false, false); }
 #undef PDDP_M16N_GO
-  return launch_status();
 }
 
 template <typename T>

@@ -306,15 +306,9 @@ static int launch_mfma32(const RiccatiArgs<float>& a, hipStream_t st,
       block(m32::kThreads);
   const bool bounded = a.u_min != nullptr;
 #define PDDP_M32(Bd, F, ND)                                                    \
-  do {                                                                         \
-    auto kern = chol ? m32::riccati_mfma32_kernel<Bd, F, ND, true>             \
-                     : m32::riccati_mfma32_kernel<Bd, F, ND, false>;           \
-    const hipError_t e_ = hipFuncSetAttribute(                                 \
-        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-        (int)lds);                                                             \
-    if (e_ != hipSuccess) return (int)e_;                                      \
-    PDDP_LAUNCH(kern, grid, block, lds, st, a);                                \
-  } while (0)
+  return launch_dyn_lds(chol ? m32::riccati_mfma32_kernel<Bd, F, ND, true>     \
+                             : m32::riccati_mfma32_kernel<Bd, F, ND, false>,   \
+                        grid, block, lds, st, a)
 #define PDDP_M32_ND(Bd, F)                                                     \
   do {                                                                         \
     if (ndma == 4) PDDP_M32(Bd, F, 4); else PDDP_M32(Bd, F, 8);                \
@@ -323,7 +317,6 @@ static int launch_mfma32(const RiccatiArgs<float>& a, hipStream_t st,
   else { if (fast_math) PDDP_M32_ND(false, true); else PDDP_M32_ND(false, false); }
 #undef PDDP_M32_ND
 #undef PDDP_M32
-  return launch_status();
 }
 
 }  // namespace pddp

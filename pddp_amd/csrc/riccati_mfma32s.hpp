@@ -409,14 +409,8 @@ static int launch_mfma32s(const RiccatiArgs<float>& a, hipStream_t st,
   const dim3 grid((a.B + tj - 1) / tj), block(m32s::kThreads);
   const bool bounded = a.u_min != nullptr;
 #define PDDP_M32S(Bd, F, ND)                                                   \
-  do {                                                                         \
-    auto kern = m32s::riccati_mfma32s_kernel<Bd, F, ND>;                       \
-    const hipError_t e_ = hipFuncSetAttribute(                                 \
-        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-        (int)lds);                                                             \
-    if (e_ != hipSuccess) return (int)e_;                                      \
-    PDDP_LAUNCH(kern, grid, block, lds, st, a);                                \
-  } while (0)
+  return launch_dyn_lds(m32s::riccati_mfma32s_kernel<Bd, F, ND>, grid, block,  \
+                        lds, st, a)
 #define PDDP_M32S_ND(Bd, F)                                                    \
   do {                                                                         \
     if (ndma == 4) PDDP_M32S(Bd, F, 4); else PDDP_M32S(Bd, F, 8);              \
@@ -425,7 +419,6 @@ static int launch_mfma32s(const RiccatiArgs<float>& a, hipStream_t st,
   else { if (fast_math) PDDP_M32S_ND(false, true); else PDDP_M32S_ND(false, false); }
 #undef PDDP_M32S_ND
 #undef PDDP_M32S
-  return launch_status();
 }
 
 }  // namespace pddp

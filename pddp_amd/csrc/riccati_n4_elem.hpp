@@ -1094,89 +1094,145 @@ inline int& nominal_kernel_choice() {
 
 // The gain branch of a sweep's arguments (n4e::kBr*), -1: not served (one
 // bound without the other).
-inline int n4_branch_of(const void* u_min, const void* u_max, int branch) {
-  if ((u_min == nullptr) != (u_max == nullptr)) return -1;
-  const bool bounded = u_min != nullptr;
+inline int n4_branch_of(bool has_u_min, bool has_u_max, int branch) {
+  if (has_u_min != has_u_max) return -1;
+  const bool bounded = has_u_min;
   if (branch == PDDP_BRANCH_EIG) return bounded ? n4e::kBrEigBox : n4e::kBrEig;
   if (branch == PDDP_BRANCH_CHOLESKY)
     return bounded ? n4e::kBrCholBox : n4e::kBrChol;
   return -1;
 }
-// cartpole_branches.hip: the kernels of every branch but kBrEigBox (a
-// translation unit of their own; the benched kernels stay as they are)
-int launch_n4_branches(const pddp_problem& p, const RiccatiArgs<float>& a,
-                       const n4d::GenArgs<float>& gen, hipStream_t st,
-                       bool ovl, int br);
-int launch_n4_branches_f64(const pddp_problem& p, const RiccatiArgs<double>& a,
-                           const n4d::GenArgs<double>& gen, hipStream_t st,
-                           int br);
 
-static int launch_n4_elem(const pddp_problem& p, const RiccatiArgs<float>& a,
-                          const n4d::GenArgs<float>& gen, hipStream_t st,
-                          int overlap = -1) {
-  const int br = n4_branch_of(a.u_min, a.u_max, a.branch);
-  if (p.model != PDDP_MODEL_CARTPOLE ||
-      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || br < 0 || a.N < 1)
-    return PDDP_E_UNSUPPORTED;
-  const ProblemT<float> P = convert_problem<float>(p);
-  constexpr int kPer = n4e::kWaves * n4e::kTrajW;  // trajectories / workgroup
-  const dim3 grid((a.B + kPer - 1) / kPer);
-  // the generator on a wavefront of its own while one workgroup per CU holds
-  // the batch; beyond that the SIMDs have other wavefronts to issue from and
-  // the smaller LDS footprint (more workgroups per CU) counts
-  const bool ovl = overlap < 0 ? grid.x <= 256u : overlap != 0;
-  if (br != n4e::kBrEigBox) return launch_n4_branches(p, a, gen, st, ovl, br);
-  constexpr unsigned kSparse = 0b11001u;  // CartpoleCost: {x, sin, cos}
-  const bool sparse =
-      (live_mask(p.Q, ModelDims<PDDP_MODEL_CARTPOLE>::na) & ~kSparse) == 0;
-#define PDDP_ELEM_GO(QMV, OV)                                                 \
-  do {                                                                        \
-    auto kern = n4e::riccati_n4_elem_kernel<QMV, OV>;                         \
-    const size_t lds = (size_t)n4e::kWaves * sizeof(float) *                  \
-                       (OV ? n4e::kPairLdsOvl : n4e::kPairLdsInl);            \
-    const hipError_t e = hipFuncSetAttribute(                                 \
-        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-        (int)lds);                                                            \
-    if (e != hipSuccess) return (int)e;                                       \
-    PDDP_LAUNCH(kern, grid, dim3((OV ? 2 : 1) * n4e::kWaves * kWave), lds,    \
-                st, a, gen, P);                                               \
-  } while (0)
-  constexpr unsigned kFull = kFullMask<PDDP_MODEL_CARTPOLE>;
-  if (sparse) { if (ovl) PDDP_ELEM_GO(kSparse, true); else PDDP_ELEM_GO(kSparse, false); }
-  else { if (ovl) PDDP_ELEM_GO(kFull, true); else PDDP_ELEM_GO(kFull, false); }
-#undef PDDP_ELEM_GO
-  return launch_status();
+// The argument blocks of a sweep from the nominal: no records (`rec` NULL),
+// the nominal and where its costs go in their place.
+template <typename T>
+struct NominalArgs {
+  RiccatiArgs<T> a;
+  n4d::GenArgs<T> gen;
+};
+template <typename T>
+inline NominalArgs<T> nominal_args(const pddp_problem& p, int B, int N,
+                                   const T* Z, const T* U, const T* u_min,
+                                   const T* u_max, const double* reg,
+                                   int branch, const uint8_t* active,
+                                   uint8_t* fresh, T* gains, int32_t* status,
+                                   T* L, T* J_opt) {
+  const int n = p.model == PDDP_MODEL_CARTPOLE ? 4 : p.state_size;
+  return {{B, N, n, nullptr, u_min, u_max, reg, branch, active, gains, status},
+          {Z, U, L, J_opt, fresh}};
 }
 
-static int launch_n4_elem_f64(const pddp_problem& p,
-                              const RiccatiArgs<double>& a,
-                              const n4d::GenArgs<double>& gen, hipStream_t st) {
-  const int br = n4_branch_of(a.u_min, a.u_max, a.branch);
+// What a launch of the cartpole's sweep from the nominal (pddp_sweep_nominal_*)
+// or of its one-launch round (pddp_round_nominal_f32) looks like.  Everything
+// about it that is decided on the host is decided in n4_nominal_plan; the
+// launchers pick the instantiation a plan names and launch it.
+struct N4NominalPlan {
+  int br;          // n4e::kBr*: kBrEigBox the kernels of riccati_nominal.hip /
+                   // round_n4.hip, the others those of cartpole_branches.hip
+  bool sparse;     // stage cost mask kSparseMask (else kFullMask)
+  bool ovl;        // generator on partner wavefronts (else inline)
+  bool multi;      // round: several rounds per launch
+  int use_carry;   // round: the nominal's last rows ride in LDS between rounds
+  unsigned grid;   // workgroups of kPer trajectories
+  unsigned threads;
+  size_t lds;      // dynamic LDS, bytes
+};
+// `round`: the one-launch round of `rounds` rounds with A step sizes (else the
+// sweep alone; A and rounds are not looked at); `choice`:
+// nominal_kernel_choice(), the sweep's.  0, or PDDP_E_UNSUPPORTED.
+inline int n4_nominal_plan(const pddp_problem& p, size_t elem_size, bool round,
+                           int B, int N, int A, bool has_u_min, bool has_u_max,
+                           int branch, int rounds, int choice,
+                           N4NominalPlan& pl) {
+  constexpr int kPer = n4e::kWaves * n4e::kTrajW;  // trajectories / workgroup
+  constexpr size_t kRoundLdsMax = 159 * 1024;      // what one workgroup may take
+  pl.br = n4_branch_of(has_u_min, has_u_max, branch);
   if (p.model != PDDP_MODEL_CARTPOLE ||
-      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || br < 0 || a.N < 1)
+      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || pl.br < 0 || N < 1)
     return PDDP_E_UNSUPPORTED;
-  if (br != n4e::kBrEigBox) return launch_n4_branches_f64(p, a, gen, st, br);
-  const ProblemT<double> P = convert_problem<double>(p);
-  constexpr int kPer = n4e::kWaves * n4e::kTrajW;
-  const dim3 grid((a.B + kPer - 1) / kPer);
-  constexpr unsigned kSparse = 0b11001u;
-  constexpr unsigned kFull = kFullMask<PDDP_MODEL_CARTPOLE>;
-  const bool sparse =
-      (live_mask(p.Q, ModelDims<PDDP_MODEL_CARTPOLE>::na) & ~kSparse) == 0;
-  const size_t lds =
-      (size_t)n4e::kWaves * sizeof(double) * n4e::kPairLdsInl;  // 106 KB
-#define PDDP_ELEM64_GO(QMV)                                                   \
-  do {                                                                        \
-    auto kern = n4e::riccati_n4_elem_f64_kernel<QMV>;                         \
-    const hipError_t e = hipFuncSetAttribute(                                 \
-        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-        (int)lds);                                                            \
-    if (e != hipSuccess) return (int)e;                                       \
-    PDDP_LAUNCH(kern, grid, dim3(n4e::kWaves * kWave), lds, st, a, gen, P);   \
-  } while (0)
-  if (sparse) PDDP_ELEM64_GO(kSparse); else PDDP_ELEM64_GO(kFull);
-#undef PDDP_ELEM64_GO
-  return launch_status();
+  pl.sparse = (live_mask(p.Q, ModelDims<PDDP_MODEL_CARTPOLE>::na) &
+               ~kSparseMask<PDDP_MODEL_CARTPOLE>) == 0;
+  pl.grid = (unsigned)((B + kPer - 1) / kPer);
+  pl.multi = false;
+  pl.use_carry = 0;
+  if (!round) {
+    // the generator on a wavefront of its own while one workgroup per CU holds
+    // the batch; beyond that the SIMDs have other wavefronts to issue from and
+    // the smaller LDS footprint (more workgroups per CU) counts.  float64: the
+    // inline form (106 KB)
+    pl.ovl = elem_size == sizeof(float) &&
+             (choice == 3 ? false : choice == 4 ? true : pl.grid <= 256u);
+    pl.lds = n4e::kWaves * elem_size *
+             (pl.ovl ? n4e::kPairLdsOvl : n4e::kPairLdsInl);
+  } else {
+    // float32; one workgroup per CU (142 KB of LDS at N = 100): beyond 256
+    // workgroups the two launches, whose forms for large batches share a CU,
+    // are the faster round
+    if (elem_size != sizeof(float) || N + 1 > 128 || A > 16 || rounds < 1 ||
+        pl.grid > 256u)
+      return PDDP_E_UNSUPPORTED;
+    pl.ovl = true;
+    pl.multi = rounds > 1;
+    // the sweep's pair buffers, the search's gain rows and - several rounds
+    // per launch, where they fit (N <= 123) - the carried rows
+    const size_t lds0 = n4e::kWaves * sizeof(float) *
+                        (n4e::kPairLdsOvl + n4e::round_gains_floats(N));
+    const size_t lds1 = lds0 + n4e::kWaves * sizeof(float) * n4e::kCarryF;
+    pl.use_carry = pl.multi && lds1 <= kRoundLdsMax;
+    pl.lds = pl.use_carry ? lds1 : lds0;
+    if (pl.lds > kRoundLdsMax) return PDDP_E_UNSUPPORTED;
+  }
+  pl.threads = (pl.ovl ? 2 : 1) * n4e::kWaves * kWave;
+  return 0;
+}
+
+// PDDP_N4_BY_MASK(K): the instantiation K(cost mask) that plan `pl` names
+#define PDDP_N4_BY_MASK(K)                                                    \
+  (pl.sparse ? K(kSparseMask<PDDP_MODEL_CARTPOLE>)                            \
+             : K(kFullMask<PDDP_MODEL_CARTPOLE>))
+
+// cartpole_branches.hip: the kernels of every branch but kBrEigBox (a
+// translation unit of their own; the benched kernels stay as they are)
+int launch_n4_branches(const pddp_problem& p, const N4NominalPlan& pl,
+                       const RiccatiArgs<float>& a,
+                       const n4d::GenArgs<float>& gen, hipStream_t st);
+int launch_n4_branches(const pddp_problem& p, const N4NominalPlan& pl,
+                       const RiccatiArgs<double>& a,
+                       const n4d::GenArgs<double>& gen, hipStream_t st);
+
+// The sweep alone, float32 and float64: the plan, then the instantiation it
+// names.  (Not templates: every translation unit that includes this header
+// instantiates the six kernels below, as it always has.)
+template <typename T>
+static int n4_sweep_plan(const pddp_problem& p, const RiccatiArgs<T>& a,
+                         N4NominalPlan& pl) {
+  return n4_nominal_plan(p, sizeof(T), false, a.B, a.N, 0, a.u_min != nullptr,
+                         a.u_max != nullptr, a.branch, 0,
+                         nominal_kernel_choice(), pl);
+}
+static int launch_n4_elem(const pddp_problem& p, const RiccatiArgs<float>& a,
+                          const n4d::GenArgs<float>& gen, hipStream_t st) {
+  N4NominalPlan pl;
+  if (const int rc = n4_sweep_plan(p, a, pl)) return rc;
+  if (pl.br != n4e::kBrEigBox) return launch_n4_branches(p, pl, a, gen, st);
+#define PDDP_K(QM)                                                            \
+  (pl.ovl ? n4e::riccati_n4_elem_kernel<QM, true>                             \
+          : n4e::riccati_n4_elem_kernel<QM, false>)
+  return launch_dyn_lds(PDDP_N4_BY_MASK(PDDP_K), dim3(pl.grid),
+                        dim3(pl.threads), pl.lds, st, a, gen,
+                        convert_problem<float>(p));
+#undef PDDP_K
+}
+static int launch_n4_elem(const pddp_problem& p, const RiccatiArgs<double>& a,
+                          const n4d::GenArgs<double>& gen, hipStream_t st) {
+  N4NominalPlan pl;
+  if (const int rc = n4_sweep_plan(p, a, pl)) return rc;
+  if (pl.br != n4e::kBrEigBox) return launch_n4_branches(p, pl, a, gen, st);
+#define PDDP_K(QM) n4e::riccati_n4_elem_f64_kernel<QM>
+  return launch_dyn_lds(PDDP_N4_BY_MASK(PDDP_K), dim3(pl.grid),
+                        dim3(pl.threads), pl.lds, st, a, gen,
+                        convert_problem<double>(p));
+#undef PDDP_K
 }
 
 }  // namespace pddp

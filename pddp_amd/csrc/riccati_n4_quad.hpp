@@ -623,24 +623,13 @@ static int launch_n4_quad(const RiccatiArgs<T>& a, hipStream_t st,
     if (!bounded) return PDDP_E_UNSUPPORTED;
     auto k0 = n4q::riccati_n4_quad_kernel<T, false, true, false, R, 1, true>;
     auto k1 = n4q::riccati_n4_quad_kernel<T, true, true, false, R, 1, true>;
-    auto kern = chol ? k1 : k0;
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)lds1);
-    if (e != hipSuccess) return (int)e;
-    PDDP_LAUNCH(kern, dim3(waves), dim3(kWave), lds1, st, a);
-    return launch_status();
+    return launch_dyn_lds(chol ? k1 : k0, dim3(waves), dim3(kWave), lds1, st,
+                          a);
   }
 #define PDDP_Q4_GO(C, Bd, F, W)                                               \
-  do {                                                                        \
-    auto kern = n4q::riccati_n4_quad_kernel<T, C, Bd, F, R, W>;               \
-    const hipError_t e = hipFuncSetAttribute(                                 \
-        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-        (int)(W * lds1));                                                     \
-    if (e != hipSuccess) return (int)e;                                       \
-    PDDP_LAUNCH(kern, dim3((waves + W - 1) / W), dim3(kWave * W), W * lds1,   \
-                st, a);                                                       \
-  } while (0)
+  return launch_dyn_lds(n4q::riccati_n4_quad_kernel<T, C, Bd, F, R, W>,       \
+                        dim3((waves + W - 1) / W), dim3(kWave * W), W * lds1, \
+                        st, a)
 #define PDDP_Q4_LAUNCH(C, Bd, F)                                              \
   do {                                                                        \
     if (wpb == 4) PDDP_Q4_GO(C, Bd, F, 4);                                    \
@@ -662,7 +651,6 @@ static int launch_n4_quad(const RiccatiArgs<T>& a, hipStream_t st,
 #undef PDDP_Q4_BRANCH
 #undef PDDP_Q4_LAUNCH
 #undef PDDP_Q4_GO
-  return launch_status();
 }
 
 }  // namespace pddp

@@ -1,12 +1,43 @@
 // riccati_nominal.hip - the sweeps that evaluate their derivative records
-// themselves, from the nominal trajectory (pddp_sweep_nominal_*): the n = 4
-// sweep of riccati_n4_elem.hpp (cartpole; f32 with the generator on partner
-// wavefronts, f64 inline) and the 16 x 16 matrix-core sweep of
-// riccati_mfma16_nominal.hpp (pendulum, double cartpole).  A translation unit
+// themselves, from the nominal trajectory (pddp_sweep_nominal_*: one
+// implementation for both types): the n = 4 sweep of riccati_n4_elem.hpp
+// (cartpole; launched as n4_nominal_plan says - f32 with the generator on
+// partner wavefronts or inline, f64 inline) and the 16 x 16 matrix-core sweep
+// of riccati_mfma16_nominal.hpp (pendulum, double cartpole); and
+// pddp_n4_nominal_plan, the host-only query of that plan.  A translation unit
 // of its own: no SLP pairing (the FMAs take DPP operands, riccati_quad.hip)
 // and matrix-instruction results in ordinary VGPRs.
 #include "riccati_n4_elem.hpp"
 #include "riccati_mfma16_nominal.hpp"
+
+namespace pddp {
+
+template <typename T>
+static int sweep_nominal(const pddp_problem* problem, int B, int N, const T* Z,
+                         const T* U, const T* u_min, const T* u_max,
+                         const double* reg, int branch, const uint8_t* active,
+                         uint8_t* fresh, T* gains, int32_t* status, T* L,
+                         T* J_opt, void* stream) {
+  if (problem == nullptr || B <= 0 || N <= 0 || Z == nullptr || U == nullptr ||
+      reg == nullptr || gains == nullptr || status == nullptr ||
+      L == nullptr || J_opt == nullptr)
+    return PDDP_E_BADARG;
+  if (branch != PDDP_BRANCH_EIG && branch != PDDP_BRANCH_CHOLESKY)
+    return PDDP_E_BADARG;
+  const NominalArgs<T> sw =
+      nominal_args<T>(*problem, B, N, Z, U, u_min, u_max, reg, branch, active,
+                      fresh, gains, status, L, J_opt);
+  // cartpole: riccati_n4_elem.hpp, launched as n4_nominal_plan says (f32: its
+  // record generator inline, on wavefronts of its own, or - auto - by batch;
+  // f64: inline)
+  if (problem->model == PDDP_MODEL_CARTPOLE)
+    return launch_n4_elem(*problem, sw.a, sw.gen, (hipStream_t)stream);
+  // pendulum, double cartpole: the 16 x 16 matrix-core sweep with its
+  // records generated in the wavefront (riccati_mfma16_nominal.hpp)
+  return launch_m16_nominal<T>(*problem, sw.a, sw.gen, (hipStream_t)stream);
+}
+
+}  // namespace pddp
 
 extern "C" int pddp_sweep_nominal_f32(const pddp_problem* problem, int B, int N,
                                       const float* Z, const float* U,
@@ -15,36 +46,10 @@ extern "C" int pddp_sweep_nominal_f32(const pddp_problem* problem, int B, int N,
                                       const uint8_t* active, uint8_t* fresh,
                                       float* gains, int32_t* status, float* L,
                                       float* J_opt, void* stream) {
-  if (problem == nullptr || B <= 0 || N <= 0 || Z == nullptr || U == nullptr ||
-      reg == nullptr || gains == nullptr || status == nullptr ||
-      L == nullptr || J_opt == nullptr)
-    return PDDP_E_BADARG;
-  if (branch != PDDP_BRANCH_EIG && branch != PDDP_BRANCH_CHOLESKY)
-    return PDDP_E_BADARG;
-  pddp::RiccatiArgs<float> a;
-  a.B = B; a.N = N; a.n = 4;
-  a.rec = nullptr;
-  a.u_min = u_min; a.u_max = u_max;
-  a.reg = reg;
-  a.branch = branch;
-  a.active = active;
-  a.gains = gains;
-  a.status = status;
-  const pddp::n4d::GenArgs<float> gen = {Z, U, L, J_opt, fresh};
-  if (problem->model != PDDP_MODEL_CARTPOLE) {
-    // pendulum, double cartpole: the 16 x 16 matrix-core sweep with its
-    // records generated in the wavefront (riccati_mfma16_nominal.hpp)
-    a.n = problem->state_size;
-    return pddp::launch_m16_nominal<float>(*problem, a, gen,
-                                           (hipStream_t)stream);
-  }
-  // riccati_n4_elem.hpp: its record generator inline, on wavefronts of its
-  // own, or (auto) by batch
-  const int choice = pddp::nominal_kernel_choice();
-  return pddp::launch_n4_elem(*problem, a, gen, (hipStream_t)stream,
-                              choice == 3 ? 0 : choice == 4 ? 1 : -1);
+  return pddp::sweep_nominal<float>(problem, B, N, Z, U, u_min, u_max, reg,
+                                    branch, active, fresh, gains, status, L,
+                                    J_opt, stream);
 }
-
 extern "C" int pddp_sweep_nominal_f64(const pddp_problem* problem, int B, int N,
                                       const double* Z, const double* U,
                                       const double* u_min, const double* u_max,
@@ -52,29 +57,36 @@ extern "C" int pddp_sweep_nominal_f64(const pddp_problem* problem, int B, int N,
                                       const uint8_t* active, uint8_t* fresh,
                                       double* gains, int32_t* status, double* L,
                                       double* J_opt, void* stream) {
-  if (problem == nullptr || B <= 0 || N <= 0 || Z == nullptr || U == nullptr ||
-      reg == nullptr || gains == nullptr || status == nullptr ||
-      L == nullptr || J_opt == nullptr)
+  return pddp::sweep_nominal<double>(problem, B, N, Z, U, u_min, u_max, reg,
+                                     branch, active, fresh, gains, status, L,
+                                     J_opt, stream);
+}
+
+extern "C" int pddp_n4_nominal_plan(const pddp_problem* problem,
+                                    int element_size, int B, int N, int A,
+                                    int has_u_min, int has_u_max, int branch,
+                                    int rounds, int kernel_choice,
+                                    int32_t* plan) {
+  const bool round = rounds != 0;
+  if (problem == nullptr || plan == nullptr || B <= 0 || N <= 0 ||
+      (round && A <= 0) || (element_size != 4 && element_size != 8))
     return PDDP_E_BADARG;
   if (branch != PDDP_BRANCH_EIG && branch != PDDP_BRANCH_CHOLESKY)
     return PDDP_E_BADARG;
-  pddp::RiccatiArgs<double> a;
-  a.B = B; a.N = N; a.n = problem->state_size;
-  a.rec = nullptr;
-  a.u_min = u_min; a.u_max = u_max;
-  a.reg = reg;
-  a.branch = branch;
-  a.active = active;
-  a.gains = gains;
-  a.status = status;
-  const pddp::n4d::GenArgs<double> gen = {Z, U, L, J_opt, fresh};
-  if (problem->model == PDDP_MODEL_CARTPOLE) {
-    // riccati_n4_elem.hpp in float64 (round 5): the inline form
-    a.n = 4;
-    return pddp::launch_n4_elem_f64(*problem, a, gen, (hipStream_t)stream);
-  }
-  return pddp::launch_m16_nominal<double>(*problem, a, gen,
-                                          (hipStream_t)stream);
+  pddp::N4NominalPlan pl;
+  if (const int rc = pddp::n4_nominal_plan(
+          *problem, (size_t)element_size, round, B, N, A, has_u_min != 0,
+          has_u_max != 0, branch, rounds, kernel_choice, pl))
+    return rc;
+  plan[PDDP_N4_PLAN_BRANCH] = pl.br;
+  plan[PDDP_N4_PLAN_SPARSE] = pl.sparse;
+  plan[PDDP_N4_PLAN_OVERLAP] = pl.ovl;
+  plan[PDDP_N4_PLAN_MULTI] = pl.multi;
+  plan[PDDP_N4_PLAN_CARRY] = pl.use_carry;
+  plan[PDDP_N4_PLAN_GRID] = (int32_t)pl.grid;
+  plan[PDDP_N4_PLAN_THREADS] = (int32_t)pl.threads;
+  plan[PDDP_N4_PLAN_LDS] = (int32_t)pl.lds;
+  return 0;
 }
 
 namespace pddp {

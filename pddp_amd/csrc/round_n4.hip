@@ -1,8 +1,9 @@
 // round_n4.hip - ONE launch for a whole round of the cartpole f32 path
 // (BASELINE.json configs[1]; this file: the kernels of the bounded eig-clamp
 // branch and the entry point - the other three gain branches run the same
-// body, round_n4_body.hpp, in the kernels of cartpole_branches.hip): the
-// backward sweep from the nominal
+// body, round_n4_body.hpp, in the kernels of cartpole_branches.hip; what the
+// launch looks like for all four is n4_nominal_plan's, riccati_n4_elem.hpp):
+// the backward sweep from the nominal
 // (riccati_n4_elem.hpp; ilqr.py:489-674 with the records of :393-486 evaluated
 // in place) and then, in the SAME wavefronts for the same four trajectories,
 // the batched line search, argmin, accept / regularisation schedule and the
@@ -47,50 +48,30 @@ __global__ __launch_bounds__(2 * n4e::kWaves * kWave) void round_n4_kernel(
                                            rounds, phase_ticks, use_carry);
 }
 
+// n4_nominal_plan (riccati_n4_elem.hpp) decides the launch; here: the kernel
+// instantiation it names
 static int launch_round_n4(const pddp_problem& p, const RiccatiArgs<float>& a,
                            const n4d::GenArgs<float>& gen,
                            const LineSearchArgs<float>& ls,
                            const AcceptArgs<float>& ac, float* scratch,
                            int rounds, long long* phase_ticks,
                            hipStream_t st) {
-  const int br = n4_branch_of(a.u_min, a.u_max, a.branch);
-  if (p.model != PDDP_MODEL_CARTPOLE ||
-      p.encoding != PDDP_ENC_IGNORE_UNCERTAINTY || br < 0 || a.N < 1 ||
-      a.N + 1 > 128 || ls.A > 16 || rounds < 1)
-    return PDDP_E_UNSUPPORTED;
+  N4NominalPlan pl;
+  if (const int rc = n4_nominal_plan(p, sizeof(float), true, a.B, a.N, ls.A,
+                                     a.u_min != nullptr, a.u_max != nullptr,
+                                     a.branch, rounds, 0, pl))
+    return rc;
   // (the other gain branches: kernels of their own, cartpole_branches.hip)
-  if (br != n4e::kBrEigBox)
-    return launch_round_n4_branches(p, a, gen, ls, ac, scratch, rounds,
-                                    phase_ticks, st, br);
-  constexpr int kPer = n4e::kWaves * n4e::kTrajW;  // trajectories / workgroup
-  const dim3 grid((a.B + kPer - 1) / kPer);
-  // one workgroup per CU (142 KB of LDS at N = 100): beyond 256 workgroups
-  // the two launches, whose forms for large batches share a CU, are the
-  // faster round
-  if (grid.x > 256u) return PDDP_E_UNSUPPORTED;
-  // (several rounds per launch: the carried rows, where they fit - N <= 123)
-  int use_carry;
-  const size_t lds = round_n4_lds(a.N, rounds, use_carry);
-  if (lds == 0) return PDDP_E_UNSUPPORTED;
-  const ProblemT<float> P = convert_problem<float>(p);
-  constexpr unsigned kSparse = 0b11001u;  // CartpoleCost: {x, sin, cos}
-  constexpr unsigned kFull = kFullMask<PDDP_MODEL_CARTPOLE>;
-  const bool sparse =
-      (live_mask(p.Q, ModelDims<PDDP_MODEL_CARTPOLE>::na) & ~kSparse) == 0;
-#define PDDP_ROUND_GO(QMV)                                                    \
-  do {                                                                        \
-    auto kern = rounds > 1 ? round_n4_kernel<QMV, true>                       \
-                           : round_n4_kernel<QMV, false>;                     \
-    const hipError_t e = hipFuncSetAttribute(                                 \
-        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-        (int)lds);                                                            \
-    if (e != hipSuccess) return (int)e;                                       \
-    PDDP_LAUNCH(kern, grid, dim3(2 * n4e::kWaves * kWave), lds, st, a, gen,   \
-                P, ls, ac, scratch, rounds, phase_ticks, use_carry);          \
-  } while (0)
-  if (sparse) PDDP_ROUND_GO(kSparse); else PDDP_ROUND_GO(kFull);
-#undef PDDP_ROUND_GO
-  return launch_status();
+  if (pl.br != n4e::kBrEigBox)
+    return launch_round_n4_branches(p, pl, a, gen, ls, ac, scratch, rounds,
+                                    phase_ticks, st);
+#define PDDP_K(QM)                                                            \
+  (pl.multi ? round_n4_kernel<QM, true> : round_n4_kernel<QM, false>)
+  return launch_dyn_lds(PDDP_N4_BY_MASK(PDDP_K), dim3(pl.grid),
+                        dim3(pl.threads), pl.lds, st, a, gen,
+                        convert_problem<float>(p), ls, ac, scratch, rounds,
+                        phase_ticks, pl.use_carry);
+#undef PDDP_K
 }
 
 }  // namespace pddp
@@ -109,22 +90,16 @@ extern "C" int pddp_round_nominal_f32(
     return PDDP_E_BADARG;
   if (branch != PDDP_BRANCH_EIG && branch != PDDP_BRANCH_CHOLESKY)
     return PDDP_E_BADARG;
-  pddp::RiccatiArgs<float> a;
-  a.B = B; a.N = N; a.n = 4;
-  a.rec = nullptr;
-  a.u_min = u_min; a.u_max = u_max;
-  a.reg = mu;
-  a.branch = branch;
-  a.active = active;
-  a.gains = gains;
-  a.status = bwd_status;
-  const pddp::n4d::GenArgs<float> gen = {Z, U, L, J_opt, fresh};
+  // (mu: the sweep's regulariser and the schedule's state)
+  const pddp::NominalArgs<float> sw = pddp::nominal_args<float>(
+      *problem, B, N, Z, U, u_min, u_max, mu, branch, active, fresh, gains,
+      bwd_status, L, J_opt);
   const pddp::LineSearchArgs<float> ls{B, N, A, Z, U, gains, alphas, u_min,
                                        u_max, active, bwd_status, Zc, Uc, Jc};
   const pddp::AcceptArgs<float> ac{
       B, N, 4, 1, A, Zc, Uc, Jc, gains, bwd_status, tol, max_reg, n_iterations,
       Z, U, gains_acc, J_opt, mu, delta, state, iter, active, fresh, n_live};
-  return pddp::launch_round_n4(*problem, a, gen, ls, ac, scratch, rounds,
+  return pddp::launch_round_n4(*problem, sw.a, sw.gen, ls, ac, scratch, rounds,
                                phase_ticks, (hipStream_t)stream);
 }
 

@@ -77,24 +77,13 @@ PDDP_DEV void round_n4_body(const RiccatiArgs<float>& a,
   }
 }
 
-// The launch's LDS, bytes: the sweep's pair buffers, the search's gain rows
-// and - several rounds per launch, where they fit (N <= 123) - the carried
-// rows.  0: the horizon does not fit the 159 KB one workgroup may take.
-inline size_t round_n4_lds(int N, int rounds, int& use_carry) {
-  const size_t lds0 = (size_t)n4e::kWaves * sizeof(float) *
-                      (n4e::kPairLdsOvl + n4e::round_gains_floats(N));
-  const size_t lds1 = lds0 + (size_t)n4e::kWaves * sizeof(float) * n4e::kCarryF;
-  use_carry = rounds > 1 && lds1 <= 159 * 1024;
-  const size_t lds = use_carry ? lds1 : lds0;
-  return lds > 159 * 1024 ? 0 : lds;
-}
-
 // cartpole_branches.hip: every gain branch but n4e::kBrEigBox
-int launch_round_n4_branches(const pddp_problem& p, const RiccatiArgs<float>& a,
+int launch_round_n4_branches(const pddp_problem& p, const N4NominalPlan& pl,
+                             const RiccatiArgs<float>& a,
                              const n4d::GenArgs<float>& gen,
                              const LineSearchArgs<float>& ls,
                              const AcceptArgs<float>& ac, float* scratch,
-                             int rounds, long long* phase_ticks, hipStream_t st,
-                             int br);
+                             int rounds, long long* phase_ticks,
+                             hipStream_t st);
 
 }  // namespace pddp

@@ -1,7 +1,8 @@
 """Duration of the sweep from the nominal (pddp_sweep_nominal_f32,
 riccati_n4_elem.hpp: generator inline / on wavefronts of its own / auto) and of
-the recorded deferred sweep (variant 25) on the same fresh nominal, events on
-the dispatches; gains against each other:
+the sweep on records that `auto` takes for the batch (variant 7; 17 from 12288
+trajectories on) on the same fresh nominal, events on the dispatches; gains
+against each other:
 python tools/nominal_sweep_time.py [B ...]"""
 import ctypes
 import os
@@ -32,7 +33,8 @@ for B in [int(v) for v in sys.argv[1:]] or [4096]:
                 assert s.sweep_nominal(events=ev)
             else:
                 s._rec_stale = False
-                s.backward(active=s.active, variant=25, events=ev)
+                s.backward(active=s.active, variant=17 if B >= 12288 else 7,
+                           events=ev)
         torch.cuda.synchronize()
         d = np.array(pool.durations()) * 1e6
         out[name] = (s.gains.clone(), s.bwd_status.clone(), s.L.clone(),
