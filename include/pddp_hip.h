@@ -304,6 +304,50 @@ int pddp_line_search_batch_f64(const pddp_problem* problem,
                                const int32_t* bwd_status, double* Zc,
                                double* Uc, double* Jc, void* stream);
 
+/* ---- pddp.py:209-245 _apply_controller() with ilqr.py:318-355 forward() as
+ * the controller, batched and with the sample models as the plant: S
+ * closed-loop rollouts of every trajectory's policy (Z, U, K), each from its
+ * own initial state on its own plant (csrc/closed_loop.hip).  Rollout (b, s):
+ *
+ *   x_0 = z0s[b][s]                      (z0s == NULL: Z[b][0])
+ *   u_t = clamp(U[b][t] + K[b][t] (x_t - Z[b][t]))     t = 0 .. N-1
+ *         (gains == NULL: the open-loop action tensor form, u_t = clamp(U[b][t]);
+ *          bounds NULL together: no clamp; the clamped action is what is applied,
+ *          recorded and costed, as in pddp_line_search_*)
+ *   J += l(x_t, u_t);  x_{t+1} = plant_{b,s}(x_t, u_t);  J += l_f(x_N)
+ *
+ * Z [B][N+1][n], U [B][N][m] the nominal; gains [B][N][m + m n] in the sweep's
+ * layout (the K part only is read; gains_acc of pddp_accept_* is the
+ * reference's self._K); z0s [B][S][n]; plant [B][S][PDDP_BATCH_ROW], rows in
+ * the table's layout above (params | x_goal | u_goal): the dynamics AND the
+ * cost of rollout (b, s) are that row's; plant == NULL: every rollout runs
+ * `problem`'s own params and goals.  Q, Q_term, R, the model and the encoding
+ * are `problem`'s, as for the _batch_ entry points.
+ * Xc [B][N+1][S][n], Uc [B][N][S][m] out, time-major like Zc / Uc of the line
+ * search (the rollouts of a trajectory write one contiguous segment per step);
+ * both or neither: with NULL nothing but costs leaves the chip.  Jc [B][S]
+ * out, required.  stats [B][4] out, nullable: {mean, min, max of the finite
+ * costs, number of finite costs} of trajectory b, reduced inside the launch in
+ * an order that depends on S alone (the same controller gives the same bits
+ * wherever it sits in the batch); no finite cost: mean = min = max = +inf,
+ * count 0.  active [B] nullable: trajectories with active[b] == 0 are skipped,
+ * nothing of theirs is read or written.
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY, any
+ * B, N, S >= 1.  PDDP_E_BADARG: a null required pointer, a non-positive size,
+ * exactly one of Xc / Uc; PDDP_E_UNSUPPORTED: any other encoding; both before
+ * any HIP call. */
+int pddp_closed_loop_f32(const pddp_problem* problem, int B, int N, int S,
+                         const float* Z, const float* U, const float* gains,
+                         const float* z0s, const float* plant,
+                         const float* u_min, const float* u_max,
+                         const uint8_t* active, float* Xc, float* Uc,
+                         float* Jc, float* stats, void* stream);
+int pddp_closed_loop_f64(const pddp_problem* problem, int B, int N, int S,
+                         const double* Z, const double* U, const double* gains,
+                         const double* z0s, const double* plant,
+                         const double* u_min, const double* u_max,
+                         const uint8_t* active, double* Xc, double* Uc,
+                         double* Jc, double* stats, void* stream);
 /* ---- ilqr.py:102-181 _step() accept / reject, :364-390 mu schedule and the
  * fit() loop bookkeeping (:298-314), per trajectory, device resident -------- */
 /* Controller state arrays (all [B]):

@@ -293,6 +293,23 @@ class iLQRController(Controller):
         self._U_nominal = torch.cat([Un[..., 1:, :], Un[..., -1:, :]], -2)
         return u
 
+    def closed_loop(self, **kwargs):
+        """The fitted policy of every trajectory run in closed loop on the
+        device, S rollouts each: `ILQRSolver.closed_loop` (its arguments) of
+        the solver of the last fit / step, trajectories kept.  Returns what
+        `_apply_controller` (pddp.py:209-245) returns, with a trajectory axis:
+        ((X[:-1], U, X[1:] - X[:-1]), J), X time-major [N+1][S][n] per
+        trajectory and J [S]; after a fit without batch axis the one
+        trajectory's, otherwise with the leading B."""
+        if self._solver is None:
+            raise RuntimeError("You need to call fit or step first")
+        r = self._solver.closed_loop(keep=True, **kwargs)
+        X, U, J = r.X, r.U, r.J
+        if not self._batched:
+            X, U, J = X[0], U[0], J[0]
+        head, tail = X[..., :-1, :, :], X[..., 1:, :, :]  # (the time axis)
+        return (head, U, tail - head), J
+
 
 # ---------------------------------------------------------------------------
 # module functions with the reference's signatures

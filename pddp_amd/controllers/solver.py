@@ -242,22 +242,9 @@ class ILQRSolver(object):
                 "set_batch_problem needs a sample problem under "
                 "IGNORE_UNCERTAINTY on the native path (no plugin, no "
                 "Gaussian encoding)")
-        N_ = _native
-        prob = self.problem
-        P, na, m = self._PARAM_COUNT[prob.model], prob.aug_size, self.m
-        # the shared row: double -> T as convert_problem (csrc/models.hpp)
-        row = torch.zeros(N_.BATCH_ROW, dtype=torch.float64)
-        row[N_.BATCH_PARAMS:N_.BATCH_PARAMS + N_.MAX_PARAMS] = \
-            torch.tensor(list(prob.params), dtype=torch.float64)
-        row[N_.BATCH_X_GOAL:N_.BATCH_X_GOAL + N_.MAX_AUG] = \
-            torch.tensor(list(prob.x_goal), dtype=torch.float64)
-        row[N_.BATCH_U_GOAL:N_.BATCH_U_GOAL + N_.MAX_ACTION] = \
-            torch.tensor(list(prob.u_goal), dtype=torch.float64)
-        table = row.to(self.dtype).to(self.device).repeat(self.B, 1)
-        for name, block, off, width in (
-                ("params", params, N_.BATCH_PARAMS, P),
-                ("x_goal", x_goal, N_.BATCH_X_GOAL, na),
-                ("u_goal", u_goal, N_.BATCH_U_GOAL, m)):
+        table = self._shared_row().repeat(self.B, 1)
+        for name, block, off, width in self._row_blocks(params, x_goal,
+                                                        u_goal):
             if block is None:
                 continue
             block = torch.as_tensor(block)
@@ -272,6 +259,30 @@ class ILQRSolver(object):
         self._derivs_due = True
         self._rec_stale = True  # (the records in `_rec`: another problem's)
         self._graph = None
+
+    def _shared_row(self):
+        """The shared problem as one row of the table's layout
+        (include/pddp_hip.h): double -> T as convert_problem
+        (csrc/models.hpp)."""
+        N_ = _native
+        prob = self.problem
+        row = torch.zeros(N_.BATCH_ROW, dtype=torch.float64)
+        row[N_.BATCH_PARAMS:N_.BATCH_PARAMS + N_.MAX_PARAMS] = \
+            torch.tensor(list(prob.params), dtype=torch.float64)
+        row[N_.BATCH_X_GOAL:N_.BATCH_X_GOAL + N_.MAX_AUG] = \
+            torch.tensor(list(prob.x_goal), dtype=torch.float64)
+        row[N_.BATCH_U_GOAL:N_.BATCH_U_GOAL + N_.MAX_ACTION] = \
+            torch.tensor(list(prob.u_goal), dtype=torch.float64)
+        return row.to(self.dtype).to(self.device)
+
+    def _row_blocks(self, params, x_goal, u_goal):
+        """(name, block, offset in a row, width) of a row's three fields."""
+        N_ = _native
+        prob = self.problem
+        return (("params", params, N_.BATCH_PARAMS,
+                 self._PARAM_COUNT[prob.model]),
+                ("x_goal", x_goal, N_.BATCH_X_GOAL, prob.aug_size),
+                ("u_goal", u_goal, N_.BATCH_U_GOAL, self.m))
 
     def clear_batch_problem(self):
         """Back to one problem for the whole batch: the plan's inputs as the
@@ -623,6 +634,95 @@ class ILQRSolver(object):
         if rc == 0 and events is not None:
             self.last_search_timed = "search_accept"
         return self._search_accept_done(rc == 0, records)
+
+    @_on_device
+    def closed_loop(self, samples=None, z0=None, params=None, x_goal=None,
+                    u_goal=None, feedback=True, accepted=True, keep=False,
+                    active=None, events=None):
+        """Runs every trajectory's policy in closed loop, S rollouts each
+        (pddp_closed_loop_*: the batched `_apply_controller`, pddp.py:209-245,
+        with the sample models as the plant): rollout (b, s) starts at
+        `z0[b][s]` ([B][S][n]; default: the nominal's first state), applies
+        u = clamp(U + K (x - Z)) and steps the plant of row (b, s).
+
+        Plant fields `params` ([.][P], dt first), `x_goal` ([.][na]), `u_goal`
+        ([.][m]) as in `set_batch_problem`, each [B][S][.] or [B][.] (the same
+        for every s); a field not given is `batch_table`'s if a table is set,
+        else the shared problem's; no field and no table: the shared problem
+        for every rollout.  The cost of a rollout uses its row's goals.
+        `samples` S defaults to z0.shape[1], else 1.  `accepted`: the gains of
+        the accepted nominal (`gains_acc`, the reference's `_K`) or the last
+        sweep's; `feedback=False`: open loop, u = clamp(U).  `active` [B]
+        uint8: trajectories with 0 are skipped, their outputs NaN (X, U:
+        unspecified).  `events`: a (start, stop) pair for the dispatch.
+
+        Returns an object with `J` [B][S], `stats` [B][4] = (mean, min, max of
+        the finite costs, their number) and, with `keep`, `X` [B][N+1][S][n],
+        `U` [B][N][S][m] (None otherwise: only costs leave the chip).
+        Stream-ordered on the solver's stream; the controller state, the
+        nominal, the plan and a captured graph are not touched."""
+        if not self._batch_problem_possible():
+            raise _native.NativeError(
+                "closed_loop needs a sample problem under IGNORE_UNCERTAINTY "
+                "on the native path (no plugin, no Gaussian encoding)")
+        B, N, n, m = self.B, self.N, self.n, self.m
+        opts = dict(dtype=self.dtype, device=self.device)
+        if z0 is not None:
+            z0 = torch.as_tensor(z0).to(**opts)
+            if z0.dim() != 3 or z0.shape[0] != B or z0.shape[2] != n:
+                raise _native.NativeError(
+                    "closed_loop: z0 has shape %s, expected (%d, S, %d)" % (
+                        tuple(z0.shape), B, n))
+        S = int(samples) if samples is not None else \
+            (z0.shape[1] if z0 is not None else 1)
+        if S < 1 or (z0 is not None and z0.shape[1] != S):
+            raise _native.NativeError(
+                "closed_loop: %d samples, z0 of shape %s" % (
+                    S, None if z0 is None else tuple(z0.shape)))
+        plant = None
+        if self.batch_table is not None or not (
+                params is None and x_goal is None and u_goal is None):
+            base = self.batch_table if self.batch_table is not None else \
+                self._shared_row().repeat(B, 1)
+            plant = base.unsqueeze(1).repeat(1, S, 1)
+            for name, block, off, width in self._row_blocks(params, x_goal,
+                                                            u_goal):
+                if block is None:
+                    continue
+                block = torch.as_tensor(block).to(**opts)
+                if block.dim() == 2:
+                    block = block.unsqueeze(1).expand(-1, S, -1)
+                if tuple(block.shape) != (B, S, width):
+                    raise _native.NativeError(
+                        "closed_loop: %s has shape %s, expected (%d, [%d, ]"
+                        "%d)" % (name, tuple(torch.as_tensor(block).shape), B,
+                                 S, width))
+                plant[:, :, off:off + width] = block
+        if active is not None and not (
+                torch.is_tensor(active) and active.dtype == torch.uint8 and
+                active.device == self.device and
+                tuple(active.shape) == (B,)):
+            raise _native.NativeError(
+                "closed_loop: active must be a uint8 tensor of shape (%d,) on "
+                "%s" % (B, self.device))
+        gains = None if not feedback else \
+            (self.gains_acc if accepted else self.gains)
+        fill = float("nan")
+        out = types.SimpleNamespace(
+            J=torch.full((B, S), fill, **opts) if active is not None
+            else torch.empty(B, S, **opts),
+            stats=torch.full((B, 4), fill, **opts) if active is not None
+            else torch.empty(B, 4, **opts),
+            X=torch.empty(B, N + 1, S, n, **opts) if keep else None,
+            U=torch.empty(B, N, S, m, **opts) if keep else None)
+        p = _native.ptr
+        self._launch(
+            events, _native.call, "pddp_closed_loop", self.dtype, self._pp, B,
+            N, S, p(self.Z), p(self.U), p(gains),
+            p(None if z0 is None else z0.contiguous()), p(plant),
+            p(self.u_min), p(self.u_max), p(active), p(out.X), p(out.U),
+            p(out.J), p(out.stats), self._s())
+        return out
 
     def rounds(self, count, tol=5e-6, max_reg=1e10, n_iterations=50,
                events=None):
