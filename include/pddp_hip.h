@@ -348,6 +348,66 @@ int pddp_closed_loop_f64(const pddp_problem* problem, int B, int N, int S,
                          const double* u_min, const double* u_max,
                          const uint8_t* active, double* Xc, double* Uc,
                          double* Jc, double* stats, void* stream);
+
+/* ---- pddp.py:209-245 _apply_controller(mpc=True) with ilqr.py:355-362
+ * forward(mpc=True) as the controller, batched and with the sample models as
+ * the plant: the hand-over between two control steps of a receding-horizon
+ * trial, one launch per control step AFTER that step's rounds
+ * (csrc/mpc_advance.hip; one lane per trajectory).  Trajectory b at control
+ * step t of T, in this order:
+ *
+ *   state_log[b][t] = state[b];  live_log[b][t] = active[b] != 0
+ *         (as the rounds left them; live: the rounds ran out before the
+ *          trajectory was accepted, converged or exhausted its regularisation)
+ *   x = z0[b];  u = clamp(U[b][0])   (bounds NULL together: no clamp)
+ *   Xlog[b][t] = x;  Ulog[b][t] = u;  Jcl[b] = (t == 0 ? 0 : Jcl[b]) + l(x, u)
+ *   x' = plant_b(x, u) + disturbance[b][t]       (disturbance == NULL: + 0)
+ *   t == T-1:  Xlog[b][T] = x';  Jcl[b] += l_f(x')
+ *   U[b][i] = U[b][i+1], i < N-1; the last row stays (repeated): a plain copy
+ *         of the unclamped words;  z0[b] = x'
+ *   Z[b][0..N] = the rollout of the shifted U from x' with clamped actions
+ *         under the CONTROLLER's model: what pddp_nominal_rollout[_batch]_*
+ *         computes for (z0, U) as this launch leaves them
+ *   mu = 0, delta = 2, state = UNDEFINED, iter = 1, active = 1, fresh = 1
+ *         (the regularisation reset, ilqr.py:364-367, and the start of a fit
+ *          loop with n_iterations = 1)
+ *
+ * table [B][PDDP_BATCH_ROW], nullable: the controller's model of trajectory b
+ * is row b (the layout above), else `problem`'s own params and goals.  plant
+ * [B][PDDP_BATCH_ROW], nullable: the plant's dynamics AND the cost of the
+ * trial are that row's; NULL: the plant is the controller's model.  Q, Q_term,
+ * R, the model and the encoding are `problem`'s.  z0 [B][n], U [B][N][m],
+ * Z [B][N+1][n], the controller state arrays ([B], as pddp_accept_*) in / out.
+ * disturbance [B][T][n].  Xlog [B][T+1][n], Ulog [B][T][m], Jcl [B],
+ * state_log [B][T] int32, live_log [B][T] uint8: the trial, written at t (and
+ * T); Jcl is summed in t order by the trajectory's lane, no atomics.
+ * mask [B] nullable: trajectories with mask[b] == 0 are left entirely
+ * untouched, nothing of theirs is read or written.  n_live
+ * [PDDP_LIVE_SHARDS], nullable: zeroed by the launch whatever the mask says
+ * (it belongs to no trajectory).
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY, any
+ * B, N, T >= 1.  PDDP_E_BADARG: a null required pointer (everything but table,
+ * plant, the bounds, disturbance, mask and n_live), a non-positive size, t
+ * outside [0, T); PDDP_E_UNSUPPORTED: any other encoding or model; both before
+ * any HIP call. */
+int pddp_mpc_advance_f32(const pddp_problem* problem, const float* table,
+                         int B, int N, int T, int t, float* z0, float* U,
+                         float* Z, const float* u_min, const float* u_max,
+                         const float* plant, const float* disturbance,
+                         const uint8_t* mask, float* Xlog, float* Ulog,
+                         float* Jcl, int32_t* state_log, uint8_t* live_log,
+                         double* mu, double* delta, int32_t* state,
+                         int32_t* iter, uint8_t* active, uint8_t* fresh,
+                         int32_t* n_live, void* stream);
+int pddp_mpc_advance_f64(const pddp_problem* problem, const double* table,
+                         int B, int N, int T, int t, double* z0, double* U,
+                         double* Z, const double* u_min, const double* u_max,
+                         const double* plant, const double* disturbance,
+                         const uint8_t* mask, double* Xlog, double* Ulog,
+                         double* Jcl, int32_t* state_log, uint8_t* live_log,
+                         double* mu, double* delta, int32_t* state,
+                         int32_t* iter, uint8_t* active, uint8_t* fresh,
+                         int32_t* n_live, void* stream);
 /* ---- ilqr.py:102-181 _step() accept / reject, :364-390 mu schedule and the
  * fit() loop bookkeeping (:298-314), per trajectory, device resident -------- */
 /* Controller state arrays (all [B]):

@@ -79,6 +79,7 @@ _SIGS = {
     "pddp_derivs_batch": [_P, _P, c_int, c_int] + [_P] * 10,
     "pddp_line_search_batch": [_P, _P, c_int, c_int, c_int] + [_P] * 12,
     "pddp_closed_loop": [_P, c_int, c_int, c_int] + [_P] * 13,
+    "pddp_mpc_advance": [_P, _P] + [c_int] * 4 + [_P] * 21,
     "pddp_search_accept": [_P, c_int, c_int, c_int] + [_P] * 11 +
                           [c_double, c_double, c_int] +
                           [_P] * 11,
@@ -137,7 +138,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_derivs",
           "pddp_line_search", "pddp_search_accept", "pddp_accept",
           "pddp_nominal_rollout_batch", "pddp_derivs_batch",
-          "pddp_line_search_batch", "pddp_closed_loop",
+          "pddp_line_search_batch", "pddp_closed_loop", "pddp_mpc_advance",
           "pddp_pack_best", "pddp_sweep_nominal", "pddp_gp_step",
           "pddp_gp_step_masked",
           "pddp_gp_rollout")

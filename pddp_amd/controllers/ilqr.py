@@ -310,6 +310,24 @@ class iLQRController(Controller):
         head, tail = X[..., :-1, :, :], X[..., 1:, :, :]  # (the time axis)
         return (head, U, tail - head), J
 
+    def mpc_closed_loop(self, steps, rounds_per_step=10, **kwargs):
+        """A receding-horizon trial of every trajectory on the device:
+        `ILQRSolver.mpc_closed_loop` (its arguments) of the solver of the last
+        fit / step - `steps` control steps of at most `rounds_per_step`
+        attempts each, from that solver's nominal and with its step sizes.
+        Returns what `_apply_controller(..., mpc=True)` (pddp.py:209-245)
+        returns, ((X[:-1], U, X[1:] - X[:-1]), J) with X [steps+1][n] and J a
+        scalar per trajectory; after a fit without batch axis the one
+        trajectory's, otherwise with the leading B."""
+        if self._solver is None:
+            raise RuntimeError("You need to call fit or step first")
+        r = self._solver.mpc_closed_loop(steps, rounds_per_step, **kwargs)
+        X, U, J = r.X, r.U, r.J
+        if not self._batched:
+            X, U, J = X[0], U[0], J[0]
+        head, tail = X[..., :-1, :], X[..., 1:, :]  # (the time axis)
+        return (head, U, tail - head), J
+
 
 # ---------------------------------------------------------------------------
 # module functions with the reference's signatures

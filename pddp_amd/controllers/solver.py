@@ -724,6 +724,142 @@ class ILQRSolver(object):
             p(out.J), p(out.stats), self._s())
         return out
 
+    def _plant_table(self, what, params, x_goal, u_goal):
+        """[B][BATCH_ROW] plant rows of a trial whose fields are [B][.]: a
+        field not given is `batch_table`'s if a table is set, else the shared
+        problem's; None when that leaves the controller's own model."""
+        if params is None and x_goal is None and u_goal is None:
+            return None
+        B = self.B
+        plant = (self.batch_table.clone() if self.batch_table is not None
+                 else self._shared_row().repeat(B, 1))
+        for name, block, off, width in self._row_blocks(params, x_goal,
+                                                        u_goal):
+            if block is None:
+                continue
+            block = torch.as_tensor(block)
+            if tuple(block.shape) != (B, width):
+                raise _native.NativeError(
+                    "%s: %s has shape %s, expected (%d, %d)" % (
+                        what, name, tuple(block.shape), B, width))
+            plant[:, off:off + width] = block.to(dtype=self.dtype,
+                                                 device=self.device)
+        return plant.contiguous()
+
+    @_on_device
+    def mpc_closed_loop(self, steps, rounds_per_step, z0=None, params=None,
+                        x_goal=None, u_goal=None, disturbance=None, tol=5e-6,
+                        max_reg=1e10, active=None, events=None):
+        """A receding-horizon trial of every trajectory on its own plant, on
+        the device (the batched `_apply_controller(..., mpc=True)`,
+        pddp.py:209-245, around `forward(mpc=True)`, ilqr.py:355-362, with the
+        sample models as the plant).  Starts with `set_nominal(z0 or self.z0,
+        self.U)`; then `steps` control steps, each
+
+            rounds(rounds_per_step, tol, max_reg, n_iterations=1)
+            pddp_mpc_advance_*   (csrc/mpc_advance.hip)
+
+        The rounds are one `step()` of every controller - a trajectory that is
+        accepted, has converged or has exhausted its regularisation goes
+        inactive, a round with nothing live is a no-op - cut off after
+        `rounds_per_step` attempts; the advance applies clamp(U[b][0]) to plant
+        b, adds `disturbance[b][t]` ([B][steps][n], optional), logs the trial,
+        shifts U by one (the last row repeated), rolls out the new nominal
+        from the plant's next state under the controller's model and re-arms
+        the controller state.  The controller's model is the solver's as it
+        stands, with `batch_table` or without, and the rounds take whatever
+        sequence `_plan()` answers.  The step sizes are the solver's own:
+        `mpc_alphas` at construction gives the reference's MPC schedule.
+
+        Plant fields `params` ([B][P], dt first), `x_goal` ([B][na]), `u_goal`
+        ([B][m]) as in `closed_loop`; a field not given is `batch_table`'s if
+        a table is set, else the shared problem's; none given: the plant is
+        the controller's model.  The cost of the trial uses the plant row's
+        goals.  `active` [B] uint8: trajectories with 0 are neither optimised
+        nor advanced, their outputs NaN (`X`, `U`, `J`) and 0.
+
+        Returns an object with `X` [B][steps+1][n], `U` [B][steps][m] (the
+        clamped actions applied), `J` [B], `states` [B][steps] (the iLQRState
+        each control step's rounds ended in) and `unfinished` [B][steps]
+        uint8 (1: the rounds ran out before the step was decided; the nominal
+        applied is then the one the last accepted attempt left).  No host
+        synchronisation; everything is stream-ordered on the solver's stream,
+        `events` a (start, stop) pair recorded around the whole loop.
+        Afterwards the solver holds the nominal rolled out from x_T with the
+        shifted actions and a re-armed controller state: a second call with
+        `z0=None` continues the trial."""
+        if not self._batch_problem_possible():
+            raise _native.NativeError(
+                "mpc_closed_loop needs a sample problem under "
+                "IGNORE_UNCERTAINTY on the native path (no plugin, no Gaussian "
+                "encoding)")
+        B, N, n, m = self.B, self.N, self.n, self.m
+        T, R = int(steps), int(rounds_per_step)
+        if T < 1 or R < 1:
+            raise _native.NativeError(
+                "mpc_closed_loop: %d steps of %d rounds" % (T, R))
+        opts = dict(dtype=self.dtype, device=self.device)
+        if z0 is not None:
+            z0 = torch.as_tensor(z0).to(**opts)
+            if tuple(z0.shape) != (B, n):
+                raise _native.NativeError(
+                    "mpc_closed_loop: z0 has shape %s, expected (%d, %d)" % (
+                        tuple(z0.shape), B, n))
+        if disturbance is not None:
+            disturbance = torch.as_tensor(disturbance).to(**opts).contiguous()
+            if tuple(disturbance.shape) != (B, T, n):
+                raise _native.NativeError(
+                    "mpc_closed_loop: disturbance has shape %s, expected "
+                    "(%d, %d, %d)" % (tuple(disturbance.shape), B, T, n))
+        if active is not None and not (
+                torch.is_tensor(active) and active.dtype == torch.uint8 and
+                active.device == self.device and
+                tuple(active.shape) == (B,)):
+            raise _native.NativeError(
+                "mpc_closed_loop: active must be a uint8 tensor of shape "
+                "(%d,) on %s" % (B, self.device))
+        plant = self._plant_table("mpc_closed_loop", params, x_goal, u_goal)
+        masked = active is not None
+        fill = float("nan")
+        i32 = dict(dtype=torch.int32, device=self.device)
+        u8 = dict(dtype=torch.uint8, device=self.device)
+        out = types.SimpleNamespace(
+            X=torch.full((B, T + 1, n), fill, **opts) if masked
+            else torch.empty(B, T + 1, n, **opts),
+            U=torch.full((B, T, m), fill, **opts) if masked
+            else torch.empty(B, T, m, **opts),
+            J=torch.full((B,), fill, **opts) if masked
+            else torch.empty(B, **opts),
+            states=torch.zeros(B, T, **i32) if masked
+            else torch.empty(B, T, **i32),
+            unfinished=torch.zeros(B, T, **u8) if masked
+            else torch.empty(B, T, **u8))
+        record = _native.lib().pddp_event_record
+        if events is not None:
+            _native.check(record(events[0], self._s()), "pddp_event_record")
+        self.set_nominal(self.z0 if z0 is None else z0, self.U)
+        if masked:  # (the skipped ones take no part in the rounds either)
+            self.active.mul_(active)
+            self.fresh.mul_(active)
+        p = _native.ptr
+        b = self._buffers()
+        tail = (p(self.z0), b.U, b.Z, b.u_min, b.u_max, p(plant),
+                p(disturbance), p(active), p(out.X), p(out.U), p(out.J),
+                p(out.states), p(out.unfinished), b.mu, b.delta, b.state,
+                b.iter, b.active, b.fresh, b.n_live)
+        advance = getattr(_native.lib(),
+                          "pddp_mpc_advance_" + _native.suffix(self.dtype))
+        for t in range(T):
+            self.rounds(R, tol, max_reg, n_iterations=1)
+            _native.check(
+                advance(self._pp, p(self.batch_table), B, N, T, t, *tail,
+                        self._s()), "pddp_mpc_advance")
+            # (as set_nominal leaves the host flags: every nominal is new)
+            self._derivs_due = True
+        if events is not None:
+            _native.check(record(events[1], self._s()), "pddp_event_record")
+        return out
+
     def rounds(self, count, tol=5e-6, max_reg=1e10, n_iterations=50,
                events=None):
         """`count` rounds; in one launch where pddp_round_nominal_f32 applies
