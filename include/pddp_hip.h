@@ -408,6 +408,89 @@ int pddp_mpc_advance_f64(const pddp_problem* problem, const double* table,
                          double* mu, double* delta, int32_t* state,
                          int32_t* iter, uint8_t* active, uint8_t* fresh,
                          int32_t* n_live, void* stream);
+
+/* ---- reference tracking: a goal PER TIME STEP (csrc/tracking.hip) ---------
+ * `ref` [B][ref_len][PDDP_REF_ROW], device memory of the run's dtype: row k of
+ * trajectory b holds the goals of step k of its reference,
+ *   [PDDP_REF_X_GOAL .. +7]  x_goal  (augmented coordinates, PDDP_MAX_AUG)
+ *   [PDDP_REF_U_GOAL .. +3]  u_goal  (PDDP_MAX_ACTION)
+ * (the widths of the table's fields above).  Entries beyond the model's sizes
+ * are never read.  An f32 row is 48 bytes, an f64 row 96: rows are 16-byte
+ * aligned when the base is.  Horizon index i = 0 .. N (N: the terminal step)
+ * of trajectory b reads row min(ref_t0 + i, ref_len - 1): the last row is
+ * held, a reference may be shorter than a window or a trial.  The terminal
+ * step reads its row's x_goal only.
+ * Q, Q_term, R, the model, the encoding and the action bounds are `problem`'s.
+ * table [B][PDDP_BATCH_ROW], nullable: the model parameters of trajectory b
+ * are row b's (its goal fields are not read), else `problem`'s.
+ *
+ * pddp_derivs_track_* / pddp_line_search_track_*: every other argument and
+ * every result as pddp_derivs_batch_* / pddp_line_search_batch_* (one
+ * workgroup per trajectory and one lane per time step; one lane per
+ * (trajectory, step size), any A).
+ * pddp_mpc_advance_track_*: pddp_mpc_advance_* with
+ *   Jcl[b] += l(x, u) under row ref_t0;  t == T-1: += l_f(x') under row
+ *   ref_t0 + 1 (both clamped to the last row)
+ * plant [B][PDDP_BATCH_ROW], nullable: the plant's PARAMETERS only; its goal
+ * fields are not read.  Shift, rollout and re-arm read no goal.
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY.
+ * PDDP_E_BADARG: ref == NULL, ref_len < 1, ref_t0 < 0 and everything the
+ * siblings answer it for; PDDP_E_UNSUPPORTED: any other encoding or model;
+ * both before any HIP call. */
+#define PDDP_REF_ROW 12
+#define PDDP_REF_X_GOAL 0
+#define PDDP_REF_U_GOAL 8
+int pddp_derivs_track_f32(const pddp_problem* problem, const float* table,
+                          const float* ref, int ref_len, int ref_t0, int B,
+                          int N, const float* Z, const float* U,
+                          const float* u_min, const float* u_max,
+                          const uint8_t* mask, float* rec, float* L, float* J,
+                          int32_t* state, void* stream);
+int pddp_derivs_track_f64(const pddp_problem* problem, const double* table,
+                          const double* ref, int ref_len, int ref_t0, int B,
+                          int N, const double* Z, const double* U,
+                          const double* u_min, const double* u_max,
+                          const uint8_t* mask, double* rec, double* L,
+                          double* J, int32_t* state, void* stream);
+int pddp_line_search_track_f32(const pddp_problem* problem, const float* table,
+                               const float* ref, int ref_len, int ref_t0,
+                               int B, int N, int A, const float* Z,
+                               const float* U, const float* gains,
+                               const float* alphas, const float* u_min,
+                               const float* u_max, const uint8_t* active,
+                               const int32_t* bwd_status, float* Zc, float* Uc,
+                               float* Jc, void* stream);
+int pddp_line_search_track_f64(const pddp_problem* problem,
+                               const double* table, const double* ref,
+                               int ref_len, int ref_t0, int B, int N, int A,
+                               const double* Z, const double* U,
+                               const double* gains, const double* alphas,
+                               const double* u_min, const double* u_max,
+                               const uint8_t* active,
+                               const int32_t* bwd_status, double* Zc,
+                               double* Uc, double* Jc, void* stream);
+int pddp_mpc_advance_track_f32(const pddp_problem* problem, const float* table,
+                               const float* ref, int ref_len, int ref_t0,
+                               int B, int N, int T, int t, float* z0, float* U,
+                               float* Z, const float* u_min,
+                               const float* u_max, const float* plant,
+                               const float* disturbance, const uint8_t* mask,
+                               float* Xlog, float* Ulog, float* Jcl,
+                               int32_t* state_log, uint8_t* live_log,
+                               double* mu, double* delta, int32_t* state,
+                               int32_t* iter, uint8_t* active, uint8_t* fresh,
+                               int32_t* n_live, void* stream);
+int pddp_mpc_advance_track_f64(const pddp_problem* problem,
+                               const double* table, const double* ref,
+                               int ref_len, int ref_t0, int B, int N, int T,
+                               int t, double* z0, double* U, double* Z,
+                               const double* u_min, const double* u_max,
+                               const double* plant, const double* disturbance,
+                               const uint8_t* mask, double* Xlog, double* Ulog,
+                               double* Jcl, int32_t* state_log,
+                               uint8_t* live_log, double* mu, double* delta,
+                               int32_t* state, int32_t* iter, uint8_t* active,
+                               uint8_t* fresh, int32_t* n_live, void* stream);
 /* ---- ilqr.py:102-181 _step() accept / reject, :364-390 mu schedule and the
  * fit() loop bookkeeping (:298-314), per trajectory, device resident -------- */
 /* Controller state arrays (all [B]):

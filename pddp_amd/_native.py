@@ -21,6 +21,9 @@ MAX_AUG, MAX_ACTION, MAX_PARAMS = 8, 4, 8
 # the per-trajectory table of the pddp_*_batch_* entry points: one row per
 # trajectory (PDDP_BATCH_* of include/pddp_hip.h)
 BATCH_ROW, BATCH_PARAMS, BATCH_X_GOAL, BATCH_U_GOAL = 20, 0, 8, 16
+# the reference of the pddp_*_track_* entry points: one row per trajectory and
+# time step (PDDP_REF_* of include/pddp_hip.h)
+REF_ROW, REF_X_GOAL, REF_U_GOAL = 12, 0, 8
 
 c_int, c_double, c_void_p = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 
@@ -80,6 +83,9 @@ _SIGS = {
     "pddp_line_search_batch": [_P, _P, c_int, c_int, c_int] + [_P] * 12,
     "pddp_closed_loop": [_P, c_int, c_int, c_int] + [_P] * 13,
     "pddp_mpc_advance": [_P, _P] + [c_int] * 4 + [_P] * 21,
+    "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
+    "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
+    "pddp_mpc_advance_track": [_P, _P, _P] + [c_int] * 6 + [_P] * 21,
     "pddp_search_accept": [_P, c_int, c_int, c_int] + [_P] * 11 +
                           [c_double, c_double, c_int] +
                           [_P] * 11,
@@ -139,6 +145,8 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_line_search", "pddp_search_accept", "pddp_accept",
           "pddp_nominal_rollout_batch", "pddp_derivs_batch",
           "pddp_line_search_batch", "pddp_closed_loop", "pddp_mpc_advance",
+          "pddp_derivs_track", "pddp_line_search_track",
+          "pddp_mpc_advance_track",
           "pddp_pack_best", "pddp_sweep_nominal", "pddp_gp_step",
           "pddp_gp_step_masked",
           "pddp_gp_rollout")

@@ -310,6 +310,20 @@ class iLQRController(Controller):
         head, tail = X[..., :-1, :, :], X[..., 1:, :, :]  # (the time axis)
         return (head, U, tail - head), J
 
+    def set_reference(self, x_ref, u_ref=None, start=0):
+        """A goal per time step for the solver of the last fit / step:
+        `ILQRSolver.set_reference` (its arguments; with a fit without batch
+        axis, [1][L][.]).  `mpc_closed_loop` then follows the reference."""
+        if self._solver is None:
+            raise RuntimeError("You need to call fit or step first")
+        self._solver.set_reference(x_ref, u_ref, start)
+
+    def clear_reference(self):
+        """`ILQRSolver.clear_reference` of the solver of the last fit / step."""
+        if self._solver is None:
+            raise RuntimeError("You need to call fit or step first")
+        self._solver.clear_reference()
+
     def mpc_closed_loop(self, steps, rounds_per_step=10, **kwargs):
         """A receding-horizon trial of every trajectory on the device:
         `ILQRSolver.mpc_closed_loop` (its arguments) of the solver of the last

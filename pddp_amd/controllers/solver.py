@@ -44,6 +44,11 @@ is 0 and neither `_nominal_sweep` nor `_fused` is False.
 `set_batch_problem()` gives every trajectory its own model parameters and
 goals (`batch_table`): derivs, nominal rollout and line search are then the
 pddp_*_batch_* entry points, and every round is records+separate.
+
+`set_reference()` gives every trajectory a goal per TIME STEP (`reference`,
+read from row `ref_start` on): derivs and line search are then the
+pddp_*_track_* entry points, every round is records+separate, and
+`mpc_closed_loop()` moves the window by one row per control step.
 """
 import ctypes
 import functools
@@ -175,6 +180,10 @@ class ILQRSolver(object):
         # [B][_native.BATCH_ROW] per-trajectory parameters and goals, or None:
         # set_batch_problem()
         self.batch_table = None
+        # [B][L][_native.REF_ROW] goals per time step, or None, and the row
+        # horizon index 0 reads: set_reference()
+        self.reference = None
+        self.ref_start = 0
 
     def _nominal_sweep_possible(self):
         """pddp_sweep_nominal_*'s domain (include/pddp_hip.h).  At every
@@ -286,18 +295,119 @@ class ILQRSolver(object):
 
     def clear_batch_problem(self):
         """Back to one problem for the whole batch: the plan's inputs as the
-        constructor leaves them.  (Nothing to do without a table.)"""
+        constructor leaves them (while a reference is set, once that is
+        cleared too).  (Nothing to do without a table.)"""
         if self.batch_table is None:
             return
         self.batch_table = None
-        self._fused = self._one_launch = None
-        self._nominal_sweep = None if (self._nominal_sweep_possible() and
-                                       self._nominal_sweep_pays()) else False
+        self._restore_plan()
+
+    def _restore_plan(self):
+        """After a table or a reference went: the plan's inputs as the
+        constructor leaves them, unless the other one is still set."""
+        if self.batch_table is None and self.reference is None:
+            self._fused = self._one_launch = None
+            self._nominal_sweep = None if (
+                self._nominal_sweep_possible() and
+                self._nominal_sweep_pays()) else False
         self._derivs_due = True
         self._rec_stale = True
         self._graph = None
 
+    @_on_device
+    def set_reference(self, x_ref, u_ref=None, start=0):
+        """A goal per time step (reference tracking): `x_ref` [B][L][na] in
+        augmented coordinates, `u_ref` [B][L][m] (default: in every row the
+        table's `u_goal` if a table is set, else the shared problem's).
+        Horizon index i = 0 .. N of trajectory b takes its goals from row
+        min(start + i, L - 1): the last row is held, the terminal step reads
+        its row's `x_goal` only.  Q, Q_term, R, the model, the encoding and the
+        bounds stay the problem's; the model parameters stay the table's where
+        one is set.
+
+        Builds `reference` ([B][L][12], include/pddp_hip.h) and `ref_start`;
+        from then on the derivative records and the line search are the
+        pddp_*_track_* entry points and every round is derivs, backward,
+        line_search, accept (`records+separate`); `mpc_closed_loop()` reads
+        the window from `ref_start + t` at control step t.  The sweep from the
+        nominal, the one-launch round, the fused search and `closed_loop()`
+        take one goal per trajectory and refuse.  The nominal rollout reads no
+        goal: the current nominal stays as it is."""
+        if not self._batch_problem_possible():
+            raise _native.NativeError(
+                "set_reference needs a sample problem under "
+                "IGNORE_UNCERTAINTY on the native path (no plugin, no "
+                "Gaussian encoding)")
+        N_ = _native
+        B, na, m = self.B, self.problem.aug_size, self.m
+        opts = dict(dtype=self.dtype, device=self.device)
+        x_ref = torch.as_tensor(x_ref)
+        if x_ref.dim() != 3 or x_ref.shape[0] != B or x_ref.shape[1] < 1 or \
+                x_ref.shape[2] != na:
+            raise _native.NativeError(
+                "set_reference: x_ref has shape %s, expected (%d, L >= 1, "
+                "%d)" % (tuple(x_ref.shape), B, na))
+        L = x_ref.shape[1]
+        if u_ref is not None:
+            u_ref = torch.as_tensor(u_ref)
+            if tuple(u_ref.shape) != (B, L, m):
+                raise _native.NativeError(
+                    "set_reference: u_ref has shape %s, expected (%d, %d, "
+                    "%d)" % (tuple(u_ref.shape), B, L, m))
+        start = self._ref_start_of(start)
+        base = self.batch_table if self.batch_table is not None else \
+            self._shared_row().repeat(B, 1)
+        ref = torch.zeros(B, L, N_.REF_ROW, **opts)
+        ref[:, :, N_.REF_U_GOAL:N_.REF_U_GOAL + N_.MAX_ACTION] = \
+            base[:, None, N_.BATCH_U_GOAL:N_.BATCH_U_GOAL + N_.MAX_ACTION]
+        ref[:, :, N_.REF_X_GOAL:N_.REF_X_GOAL + na] = x_ref.to(**opts)
+        if u_ref is not None:
+            ref[:, :, N_.REF_U_GOAL:N_.REF_U_GOAL + m] = u_ref.to(**opts)
+        self.reference = ref.contiguous()
+        self.ref_start = start
+        self._one_launch = self._nominal_sweep = self._fused = False
+        self._derivs_due = True
+        self._rec_stale = True  # (the records in `_rec`: another goal's)
+        self._graph = None
+
+    def _ref_start_of(self, start):
+        if int(start) != start or int(start) < 0 or int(start) > 0x7fffffff:
+            raise _native.NativeError(
+                "the reference's window starts at a row index >= 0, got %r" %
+                (start,))
+        return int(start)
+
+    def set_reference_start(self, start):
+        """Moves the window: horizon index 0 reads row `start` from now on
+        (the records of the nominal are evaluated again, a captured round is
+        dropped)."""
+        if self.reference is None:
+            raise _native.NativeError(
+                "set_reference_start: no reference is set")
+        self.ref_start = self._ref_start_of(start)
+        self._derivs_due = True
+        self._rec_stale = True
+        self._graph = None
+
+    def clear_reference(self):
+        """Back to one goal per trajectory: what `clear_batch_problem()`
+        restores; with a table still set its plan stays.  (Nothing to do
+        without a reference.)"""
+        if self.reference is None:
+            return
+        self.reference = None
+        self.ref_start = 0
+        self._restore_plan()
+
+    def _one_goal(self, what):
+        if self.reference is not None:
+            raise _native.NativeError(
+                "%s takes ONE goal per trajectory; with a reference "
+                "(set_reference) a round is derivs, backward, line_search, "
+                "accept" % what)
+
     def _one_problem(self, what):
+        self._one_goal(what)
         if self.batch_table is not None:
             raise _native.NativeError(
                 "%s evaluates ONE problem for the whole batch; with "
@@ -312,6 +422,17 @@ class ILQRSolver(object):
             return _native.call(name, self.dtype, self._pp, *args)
         return _native.call(name + "_batch", self.dtype, self._pp,
                             _native.ptr(self.batch_table), *args)
+
+    def _goal_call(self, name, *args):
+        """A problem kernel that reads the goals (records, line search): the
+        `_track` entry point, with the table's address or NULL, while a
+        reference is set."""
+        if self.reference is None:
+            return self._problem_call(name, *args)
+        return _native.call(name + "_track", self.dtype, self._pp,
+                            _native.ptr(self.batch_table),
+                            _native.ptr(self.reference),
+                            self.reference.shape[1], self.ref_start, *args)
 
     @property
     def rec(self):
@@ -329,10 +450,10 @@ class ILQRSolver(object):
 
     def _derivs(self, mask, J, state):
         p = _native.ptr
-        self._problem_call("pddp_derivs", self.B, self.N,
-                           p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
-                           p(mask), p(self._rec), p(self.L), p(J), p(state),
-                           self._s())
+        self._goal_call("pddp_derivs", self.B, self.N,
+                        p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
+                        p(mask), p(self._rec), p(self.L), p(J), p(state),
+                        self._s())
 
     # -- views in the reference's tensor layout -----------------------------
     def record_views(self):
@@ -466,7 +587,7 @@ class ILQRSolver(object):
     # -- the round's launch plan ----------------------------------------------
     def _plan(self, variant, search_events=None):
         """The sequence a round tries first (module docstring)."""
-        if self.batch_table is not None:
+        if self.batch_table is not None or self.reference is not None:
             # (the other sequences' kernels take one problem for the batch)
             return RECORDS_SEPARATE
         if variant == 0 and self._nominal_sweep is not False and \
@@ -477,7 +598,7 @@ class ILQRSolver(object):
 
     def _fused_allowed(self):
         return self.plugin is None and self._fused is not False and \
-            self.batch_table is None
+            self.batch_table is None and self.reference is None
 
     def _one_launch_applied(self):
         return self._one_launch is True
@@ -596,7 +717,7 @@ class ILQRSolver(object):
         if self.plugin is not None:
             return self.plugin.line_search(self, active, use_status)
         b = self._buffers()
-        self._problem_call(
+        self._goal_call(
             "pddp_line_search", self.B, self.N,
             self.A, b.Z, b.U, b.gains, b.alphas, b.u_min, b.u_max,
             _native.ptr(active), b.bwd_status if use_status else None,
@@ -611,9 +732,17 @@ class ILQRSolver(object):
                      b.gains_acc, b.J_opt, b.mu, b.delta, b.state, b.iter,
                      b.active, b.fresh, b.n_live, self._s())
 
-    @_on_device
     def search_accept(self, tol, max_reg, n_iterations, events=None,
                       records=True):
+        """`_search_accept`, refused while a reference is set (round() then
+        makes the separate calls by itself)."""
+        self._one_goal("search_accept")
+        return self._search_accept(tol, max_reg, n_iterations, events,
+                                   records)
+
+    @_on_device
+    def _search_accept(self, tol, max_reg, n_iterations, events=None,
+                       records=True):
         """Line search + accept + derivative records of the new nominals in
         one launch (pddp_search_accept_*).  False when the fused kernel does
         not apply; the caller then makes the separate calls.  `events`: a
@@ -660,7 +789,9 @@ class ILQRSolver(object):
         the finite costs, their number) and, with `keep`, `X` [B][N+1][S][n],
         `U` [B][N][S][m] (None otherwise: only costs leave the chip).
         Stream-ordered on the solver's stream; the controller state, the
-        nominal, the plan and a captured graph are not touched."""
+        nominal, the plan and a captured graph are not touched.  Refused
+        while a reference is set: the rollouts are costed under one goal."""
+        self._one_goal("closed_loop")
         if not self._batch_problem_possible():
             raise _native.NativeError(
                 "closed_loop needs a sample problem under IGNORE_UNCERTAINTY "
@@ -787,7 +918,15 @@ class ILQRSolver(object):
         `events` a (start, stop) pair recorded around the whole loop.
         Afterwards the solver holds the nominal rolled out from x_T with the
         shifted actions and a re-armed controller state: a second call with
-        `z0=None` continues the trial."""
+        `z0=None` continues the trial.
+
+        With a reference (`set_reference`) control step t optimises against
+        the window that starts at row `ref_start + t`, the advance is
+        pddp_mpc_advance_track_* - the stage cost of the trial under that
+        row, the terminal cost under the next - and the plant fields supply
+        parameters only (`x_goal`, `u_goal` are not read).  Only the integer
+        offset changes from step to step; afterwards `ref_start` has advanced
+        by `steps`, so that a continued trial continues the reference."""
         if not self._batch_problem_possible():
             raise _native.NativeError(
                 "mpc_closed_loop needs a sample problem under "
@@ -847,15 +986,23 @@ class ILQRSolver(object):
                 p(disturbance), p(active), p(out.X), p(out.U), p(out.J),
                 p(out.states), p(out.unfinished), b.mu, b.delta, b.state,
                 b.iter, b.active, b.fresh, b.n_live)
+        tracking = self.reference is not None
+        name = "pddp_mpc_advance_track" if tracking else "pddp_mpc_advance"
         advance = getattr(_native.lib(),
-                          "pddp_mpc_advance_" + _native.suffix(self.dtype))
+                          name + "_" + _native.suffix(self.dtype))
         for t in range(T):
             self.rounds(R, tol, max_reg, n_iterations=1)
+            ref = () if not tracking else (
+                p(self.reference), self.reference.shape[1], self.ref_start)
             _native.check(
-                advance(self._pp, p(self.batch_table), B, N, T, t, *tail,
-                        self._s()), "pddp_mpc_advance")
+                advance(self._pp, p(self.batch_table), *ref, B, N, T, t,
+                        *tail, self._s()), name)
             # (as set_nominal leaves the host flags: every nominal is new)
             self._derivs_due = True
+            if tracking:  # the next step's window; its records are all new
+                self.ref_start += 1
+        if tracking:
+            self._graph = None  # (captured under another window)
         if events is not None:
             _native.check(record(events[1], self._s()), "pddp_event_record")
         return out
@@ -896,8 +1043,8 @@ class ILQRSolver(object):
         # none, and `fresh` stays set until the next sweep has summed the stage
         # costs of the new nominal into J_opt)
         self._derivs_due = False
-        if self.search_accept(tol, max_reg, n_iterations, events=search_events,
-                              records=not nominal):
+        if self._search_accept(tol, max_reg, n_iterations,
+                               events=search_events, records=not nominal):
             return
         ev = None
         if nominal:
@@ -941,7 +1088,7 @@ class ILQRSolver(object):
                self.kernel_variant)
         if self._graph is not None and self._graph[0] == key:
             return self._graph[1]
-        if self.batch_table is not None:
+        if self.batch_table is not None or self.reference is not None:
             self.sync_records()  # (a launch that belongs to no round)
         torch.cuda.synchronize(self.device)
         if self.plugin is None:
