@@ -8,23 +8,17 @@
 //   the feedback law                   ilqr.py:318-355 (forward, mpc=False)
 //   the cost of a rollout              ilqr.py:764-791 (_trajectory_cost)
 //
-// A translation unit of its own: it includes models.hpp and problem_args.hpp
-// as they are and shares no text with problem_kernels.hip (csrc/Makefile:
-// moving shared text around changes the FMA contraction of the kernels there).
+// A translation unit of its own (csrc/Makefile: FLAGS_closed_loop).  Its loop
+// resembles the line search's but is its own text - the feedback law and the
+// output layout differ; the parameter count is model_params.hpp's, the row
+// writer stays written out at its one call site.
 #include <limits>
 #include <type_traits>
 #include "models.hpp"
 #include "problem_args.hpp"
+#include "model_params.hpp"
 
 namespace pddp {
-
-// parameters of each model, dt included (include/pddp_problem.h; the copy of
-// problem_kernels.hip's)
-template <int MODEL>
-constexpr int kPlantParamCount = MODEL == PDDP_MODEL_CARTPOLE          ? 6
-                                 : MODEL == PDDP_MODEL_DOUBLE_CARTPOLE ? 8
-                                 : MODEL == PDDP_MODEL_PENDULUM        ? 5
-                                                                       : 3;
 
 // Mapping: one lane per rollout, s fastest.  A trajectory owns G consecutive
 // lanes, the launch's lane group:
@@ -111,11 +105,13 @@ __global__ __launch_bounds__(kClosedLoopThreads) void closed_loop_kernel(
       // over it, in registers for the whole rollout; Q, Qt and R are never
       // written and stay scalar operands of the kernel argument
       ProblemT<T> P = shared;
+      // (write_params_and_goals' statements in place: called, seven of the
+      // eight kernels come out as other instructions)
       if (a.plant != nullptr) {
         const T* row = a.plant + bs * PDDP_BATCH_ROW;
         P.dt = row[PDDP_BATCH_PARAMS];
 #pragma unroll
-        for (int i = 0; i < kPlantParamCount<MODEL> - 1; ++i)
+        for (int i = 0; i < kModelParamCount<MODEL> - 1; ++i)
           P.p[i] = row[PDDP_BATCH_PARAMS + 1 + i];
 #pragma unroll
         for (int i = 0; i < D::na; ++i) P.goal[i] = row[PDDP_BATCH_X_GOAL + i];

@@ -1,8 +1,11 @@
 // derivs_body.inc - the derivative records of one trajectory by its workgroup:
-// the text of derivs_kernel and batch_derivs_kernel (problem_kernels.hip).
+// the text of derivs_kernel and batch_derivs_kernel (problem_kernels.hip) and
+// of track_derivs_kernel (tracking.hip).
 // PDDP_PROBLEM_OF_B as in rollout_body.inc; PDDP_SPLIT_TERMINAL: record_of is
 // called under `if (terminal)` with the flag a constant in each call (see
-// batch_derivs_kernel).
+// batch_derivs_kernel).  PDDP_GOALS(point): empty, or with a goal per time
+// step what tracking.hip does at TAKE_X and TAKE_U (write step t's goals over
+// P's, the latter where the step has an action).
   using D = ModelDims<MODEL>;
   constexpr int n = D::n, m = D::m;
   constexpr RecLayout lay(n, m);
@@ -32,11 +35,14 @@
       const bool terminal = (t == N);
 #pragma unroll
       for (int j = 0; j < m; ++j) un[j] = terminal ? T(0) : Ub[t * m + j];
+      PDDP_GOALS(TAKE_X)
 #if PDDP_SPLIT_TERMINAL
-      if (terminal)
+      if (terminal) {
         l = record_of<T, MODEL>(P, z, un, true, bounded, a.u_min, a.u_max, w);
-      else
+      } else {
+        PDDP_GOALS(TAKE_U)
         l = record_of<T, MODEL>(P, z, un, false, bounded, a.u_min, a.u_max, w);
+      }
 #else
       l = record_of<T, MODEL>(P, z, un, terminal, bounded, a.u_min, a.u_max, w);
 #endif

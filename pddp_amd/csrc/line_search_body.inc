@@ -1,6 +1,11 @@
 // line_search_body.inc - one (trajectory, step size) candidate by its lane: the
-// text of line_search_kernel and batch_line_search_kernel (problem_kernels.hip).
-// PDDP_PROBLEM_OF_B as in rollout_body.inc.
+// text of line_search_kernel and batch_line_search_kernel (problem_kernels.hip)
+// and of track_line_search_kernel (tracking.hip).
+// PDDP_PROBLEM_OF_B as in rollout_body.inc.  PDDP_GOALS(point): empty, or with
+// a goal per time step what tracking.hip does at TAKE_FIRST (write row 0's over
+// P's), NEXT_ROW (name row t + 1, ahead of the nominal prefetch), PREFETCH_NEXT
+// (request it, behind the nominal prefetch) and TAKE_NEXT (write it over P's at
+// the end of the step; up to row N, the terminal cost's).
   using D = ModelDims<MODEL>;
   constexpr int n = D::n, m = D::m;
   constexpr int GS = m + m * n;
@@ -35,6 +40,7 @@
   for (int j = 0; j < m; ++j) ur[j] = Ub[j];
 #pragma unroll
   for (int j = 0; j < GS; ++j) gr[j] = Gb[j];
+  PDDP_GOALS(TAKE_FIRST)
 
   // time-major output [b][t][alpha][.]: at every step the A lanes of a
   // trajectory write one contiguous A*n-word segment (see the note at
@@ -47,12 +53,14 @@
     // prefetch the next step's nominal data before the dependent chain
     T zr2[n], ur2[m], gr2[GS];
     const int tn = (t + 1 < N) ? t + 1 : t;
+    PDDP_GOALS(NEXT_ROW)
 #pragma unroll
     for (int j = 0; j < n; ++j) zr2[j] = Zb[tn * n + j];
 #pragma unroll
     for (int j = 0; j < m; ++j) ur2[j] = Ub[tn * m + j];
 #pragma unroll
     for (int j = 0; j < GS; ++j) gr2[j] = Gb[tn * GS + j];
+    PDDP_GOALS(PREFETCH_NEXT)
 
 #pragma unroll
     for (int r = 0; r < m; ++r) {
@@ -80,6 +88,7 @@
     for (int j = 0; j < m; ++j) ur[j] = ur2[j];
 #pragma unroll
     for (int j = 0; j < GS; ++j) gr[j] = gr2[j];
+    PDDP_GOALS(TAKE_NEXT)
   }
 #pragma unroll
   for (int j = 0; j < n; ++j) Zci[(size_t)N * zstep + j] = z[j];

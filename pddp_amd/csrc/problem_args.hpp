@@ -18,6 +18,10 @@ struct RolloutArgs {
   T* Z;
 };
 
+// the workgroup of the derivative records (derivs_body.inc): one lane per time
+// step of a chunk
+constexpr int kDerivThreads = 64;
+
 template <typename T>
 struct DerivArgs {
   int B, N;

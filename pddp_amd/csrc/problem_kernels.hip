@@ -8,6 +8,7 @@
 #include <type_traits>
 #include "models.hpp"
 #include "problem_args.hpp"
+#include "model_params.hpp"
 #include "accept.hpp"
 #include "riccati_n4.hpp"  // DPP helpers of the 16-lane groups
 #include "line_search_lds.hpp"
@@ -21,7 +22,10 @@ namespace pddp {
 // PDDP_PROBLEM_OF_B as the shared problem with row b of `table`
 // [B][PDDP_BATCH_ROW] written over it (include/pddp_hip.h: params, x_goal,
 // u_goal).  The __global__ functions are that and nothing else; launchers,
-// argument checks and the dispatch on the model are shared too.
+// argument checks and the dispatch on the model are shared too.  The records'
+// and the search's texts are tracking.hip's as well (a goal PER TIME STEP): at
+// their PDDP_GOALS(point) that unit writes a reference row's goals over P's;
+// here the hook is empty.
 //
 // An included text and not a device function: as a forceinline function
 // <T, MODEL> (arguments by value or by reference, the problem handed in or
@@ -42,29 +46,15 @@ namespace pddp {
 // The backward sweep and the accept kernel never see the problem, so a round
 // with a table is derivs(batch), backward, line_search(batch), accept.
 
-// parameters of each model, dt included (include/pddp_problem.h)
-template <int MODEL>
-constexpr int kParamCount = MODEL == PDDP_MODEL_CARTPOLE          ? 6
-                            : MODEL == PDDP_MODEL_DOUBLE_CARTPOLE ? 8
-                            : MODEL == PDDP_MODEL_PENDULUM        ? 5
-                                                                  : 3;
-
-// The shared problem with trajectory b's row written over it.  Entries of the
-// row beyond the model's sizes are not read.
+// The shared problem with trajectory b's row written over it
+// (write_params_and_goals: model_params.hpp).  Returned by value into a const
+// `P`: with the two statements in the kernels' own scope the batch records and
+// searches come out as other instructions.
 template <typename T, int MODEL>
 PDDP_DEV ProblemT<T> problem_of_row(const ProblemT<T>& shared, const T* table,
                                     int b) {
-  using D = ModelDims<MODEL>;
-  const T* row = table + (size_t)b * PDDP_BATCH_ROW;
   ProblemT<T> P = shared;
-  P.dt = row[PDDP_BATCH_PARAMS];
-#pragma unroll
-  for (int i = 0; i < kParamCount<MODEL> - 1; ++i)
-    P.p[i] = row[PDDP_BATCH_PARAMS + 1 + i];
-#pragma unroll
-  for (int i = 0; i < D::na; ++i) P.goal[i] = row[PDDP_BATCH_X_GOAL + i];
-#pragma unroll
-  for (int i = 0; i < D::m; ++i) P.ugoal[i] = row[PDDP_BATCH_U_GOAL + i];
+  write_params_and_goals<T, MODEL>(P, table + (size_t)b * PDDP_BATCH_ROW);
   return P;
 }
 
@@ -96,14 +86,16 @@ __global__ __launch_bounds__(kWave) void batch_rollout_kernel(
 // (group_copy, store4: line_search_lds.hpp)
 // (record_of: models.hpp)
 
-constexpr int kDerivThreads = 64;
+// (kDerivThreads: problem_args.hpp)
 
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kDerivThreads) void derivs_kernel(
     ProblemT<T> P, DerivArgs<T> a) {
 #define PDDP_PROBLEM_OF_B
 #define PDDP_SPLIT_TERMINAL 0
+#define PDDP_GOALS(point)
 #include "derivs_body.inc"
+#undef PDDP_GOALS
 #undef PDDP_SPLIT_TERMINAL
 #undef PDDP_PROBLEM_OF_B
 }
@@ -119,7 +111,9 @@ __global__ __launch_bounds__(kDerivThreads) void batch_derivs_kernel(
     ProblemT<T> shared, DerivArgs<T> a, const T* table) {
 #define PDDP_PROBLEM_OF_B const ProblemT<T> P = problem_of_row<T, MODEL>(shared, table, b);
 #define PDDP_SPLIT_TERMINAL 1
+#define PDDP_GOALS(point)
 #include "derivs_body.inc"
+#undef PDDP_GOALS
 #undef PDDP_SPLIT_TERMINAL
 #undef PDDP_PROBLEM_OF_B
 }
@@ -135,7 +129,9 @@ template <typename T, int MODEL>
 __global__ __launch_bounds__(kWave) void line_search_kernel(
     ProblemT<T> P, LineSearchArgs<T> a) {
 #define PDDP_PROBLEM_OF_B
+#define PDDP_GOALS(point)
 #include "line_search_body.inc"
+#undef PDDP_GOALS
 #undef PDDP_PROBLEM_OF_B
 }
 
@@ -143,7 +139,9 @@ template <typename T, int MODEL>
 __global__ __launch_bounds__(kWave) void batch_line_search_kernel(
     ProblemT<T> shared, LineSearchArgs<T> a, const T* table) {
 #define PDDP_PROBLEM_OF_B const ProblemT<T> P = problem_of_row<T, MODEL>(shared, table, b);
+#define PDDP_GOALS(point)
 #include "line_search_body.inc"
+#undef PDDP_GOALS
 #undef PDDP_PROBLEM_OF_B
 }
 
@@ -435,140 +433,69 @@ int pddp_search_candidates(int mode) {
   return prev;
 }
 
-int pddp_search_accept_f32(const pddp_problem* p, int B, int N, int A, float* Z,
-                           float* U, const float* gains, const float* alphas,
-                           const float* u_min, const float* u_max,
-                           uint8_t* active, const int32_t* bwd_status,
-                           float* Zc, float* Uc, float* Jc, double tol,
-                           double max_reg, int n_iterations, float* gains_acc,
-                           float* J_opt, double* mu, double* delta,
-                           int32_t* state, int32_t* iter, uint8_t* fresh,
-                           int32_t* n_live, float* rec, float* L,
-                           void* stream) {
-  return pddp::search_accept_impl<float>(
-      p, B, N, A, Z, U, gains, alphas, u_min, u_max, active, bwd_status, Zc, Uc,
-      Jc, tol, max_reg, n_iterations, gains_acc, J_opt, mu, delta, state, iter,
-      fresh, n_live, rec, L, stream);
-}
-int pddp_search_accept_f64(const pddp_problem* p, int B, int N, int A,
-                           double* Z, double* U, const double* gains,
-                           const double* alphas, const double* u_min,
-                           const double* u_max, uint8_t* active,
-                           const int32_t* bwd_status, double* Zc, double* Uc,
-                           double* Jc, double tol, double max_reg,
-                           int n_iterations, double* gains_acc, double* J_opt,
-                           double* mu, double* delta, int32_t* state,
-                           int32_t* iter, uint8_t* fresh, int32_t* n_live,
-                           double* rec, double* L, void* stream) {
-  return pddp::search_accept_impl<double>(
-      p, B, N, A, Z, U, gains, alphas, u_min, u_max, active, bwd_status, Zc, Uc,
-      Jc, tol, max_reg, n_iterations, gains_acc, J_opt, mu, delta, state, iter,
-      fresh, n_live, rec, L, stream);
-}
+#define PDDP_PROBLEM_ENTRY_POINTS(SUF, T)                                      \
+  int pddp_search_accept_##SUF(                                                \
+      const pddp_problem* p, int B, int N, int A, T* Z, T* U, const T* gains,  \
+      const T* alphas, const T* u_min, const T* u_max, uint8_t* active,        \
+      const int32_t* bwd_status, T* Zc, T* Uc, T* Jc, double tol,              \
+      double max_reg, int n_iterations, T* gains_acc, T* J_opt, double* mu,    \
+      double* delta, int32_t* state, int32_t* iter, uint8_t* fresh,            \
+      int32_t* n_live, T* rec, T* L, void* stream) {                           \
+    return pddp::search_accept_impl<T>(                                        \
+        p, B, N, A, Z, U, gains, alphas, u_min, u_max, active, bwd_status, Zc, \
+        Uc, Jc, tol, max_reg, n_iterations, gains_acc, J_opt, mu, delta,       \
+        state, iter, fresh, n_live, rec, L, stream);                           \
+  }                                                                            \
+  int pddp_nominal_rollout_##SUF(                                              \
+      const pddp_problem* p, int B, int N, const T* z0, const T* U,            \
+      const T* u_min, const T* u_max, const uint8_t* mask, T* Z,               \
+      void* stream) {                                                          \
+    return pddp::nominal_rollout_impl<T>(p, false, nullptr, B, N, z0, U,       \
+                                         u_min, u_max, mask, Z, stream);       \
+  }                                                                            \
+  int pddp_derivs_##SUF(const pddp_problem* p, int B, int N, const T* Z,       \
+                        const T* U, const T* u_min, const T* u_max,            \
+                        const uint8_t* mask, T* rec, T* L, T* J,               \
+                        int32_t* state, void* stream) {                        \
+    return pddp::derivs_impl<T>(p, false, nullptr, B, N, Z, U, u_min, u_max,   \
+                                mask, rec, L, J, state, stream);               \
+  }                                                                            \
+  int pddp_line_search_##SUF(                                                  \
+      const pddp_problem* p, int B, int N, int A, const T* Z, const T* U,      \
+      const T* gains, const T* alphas, const T* u_min, const T* u_max,         \
+      const uint8_t* active, const int32_t* bwd_status, T* Zc, T* Uc, T* Jc,   \
+      void* stream) {                                                          \
+    return pddp::line_search_impl<T>(p, false, nullptr, B, N, A, Z, U, gains,  \
+                                     alphas, u_min, u_max, active, bwd_status, \
+                                     Zc, Uc, Jc, stream);                      \
+  }                                                                            \
+  /* the same with a problem per trajectory: row b of `table` */               \
+  int pddp_nominal_rollout_batch_##SUF(                                        \
+      const pddp_problem* p, const T* table, int B, int N, const T* z0,        \
+      const T* U, const T* u_min, const T* u_max, const uint8_t* mask, T* Z,   \
+      void* stream) {                                                          \
+    return pddp::nominal_rollout_impl<T>(p, true, table, B, N, z0, U, u_min,   \
+                                         u_max, mask, Z, stream);              \
+  }                                                                            \
+  int pddp_derivs_batch_##SUF(                                                 \
+      const pddp_problem* p, const T* table, int B, int N, const T* Z,         \
+      const T* U, const T* u_min, const T* u_max, const uint8_t* mask, T* rec, \
+      T* L, T* J, int32_t* state, void* stream) {                              \
+    return pddp::derivs_impl<T>(p, true, table, B, N, Z, U, u_min, u_max,      \
+                                mask, rec, L, J, state, stream);               \
+  }                                                                            \
+  int pddp_line_search_batch_##SUF(                                            \
+      const pddp_problem* p, const T* table, int B, int N, int A, const T* Z,  \
+      const T* U, const T* gains, const T* alphas, const T* u_min,             \
+      const T* u_max, const uint8_t* active, const int32_t* bwd_status, T* Zc, \
+      T* Uc, T* Jc, void* stream) {                                            \
+    return pddp::line_search_impl<T>(p, true, table, B, N, A, Z, U, gains,     \
+                                     alphas, u_min, u_max, active, bwd_status, \
+                                     Zc, Uc, Jc, stream);                      \
+  }
 
-int pddp_nominal_rollout_f32(const pddp_problem* p, int B, int N,
-                             const float* z0, const float* U,
-                             const float* u_min, const float* u_max,
-                             const uint8_t* mask, float* Z, void* stream) {
-  return pddp::nominal_rollout_impl<float>(p, false, nullptr, B, N, z0, U,
-                                           u_min, u_max, mask, Z, stream);
-}
-int pddp_nominal_rollout_f64(const pddp_problem* p, int B, int N,
-                             const double* z0, const double* U,
-                             const double* u_min, const double* u_max,
-                             const uint8_t* mask, double* Z, void* stream) {
-  return pddp::nominal_rollout_impl<double>(p, false, nullptr, B, N, z0, U,
-                                            u_min, u_max, mask, Z, stream);
-}
-int pddp_derivs_f32(const pddp_problem* p, int B, int N, const float* Z,
-                    const float* U, const float* u_min, const float* u_max,
-                    const uint8_t* mask, float* rec, float* L, float* J,
-                    int32_t* state, void* stream) {
-  return pddp::derivs_impl<float>(p, false, nullptr, B, N, Z, U, u_min, u_max,
-                                  mask, rec, L, J, state, stream);
-}
-int pddp_derivs_f64(const pddp_problem* p, int B, int N, const double* Z,
-                    const double* U, const double* u_min, const double* u_max,
-                    const uint8_t* mask, double* rec, double* L, double* J,
-                    int32_t* state, void* stream) {
-  return pddp::derivs_impl<double>(p, false, nullptr, B, N, Z, U, u_min,
-                                   u_max, mask, rec, L, J, state, stream);
-}
-int pddp_line_search_f32(const pddp_problem* p, int B, int N, int A,
-                         const float* Z, const float* U, const float* gains,
-                         const float* alphas, const float* u_min,
-                         const float* u_max, const uint8_t* active,
-                         const int32_t* bwd_status, float* Zc, float* Uc,
-                         float* Jc, void* stream) {
-  return pddp::line_search_impl<float>(p, false, nullptr, B, N, A, Z, U, gains,
-                                       alphas, u_min, u_max, active,
-                                       bwd_status, Zc, Uc, Jc, stream);
-}
-int pddp_line_search_f64(const pddp_problem* p, int B, int N, int A,
-                         const double* Z, const double* U, const double* gains,
-                         const double* alphas, const double* u_min,
-                         const double* u_max, const uint8_t* active,
-                         const int32_t* bwd_status, double* Zc, double* Uc,
-                         double* Jc, void* stream) {
-  return pddp::line_search_impl<double>(p, false, nullptr, B, N, A, Z, U,
-                                        gains, alphas, u_min, u_max, active,
-                                        bwd_status, Zc, Uc, Jc, stream);
-}
-
-// the same with a problem per trajectory: row b of `table`
-int pddp_nominal_rollout_batch_f32(const pddp_problem* p, const float* table,
-                                   int B, int N, const float* z0,
-                                   const float* U, const float* u_min,
-                                   const float* u_max, const uint8_t* mask,
-                                   float* Z, void* stream) {
-  return pddp::nominal_rollout_impl<float>(p, true, table, B, N, z0, U, u_min,
-                                           u_max, mask, Z, stream);
-}
-int pddp_nominal_rollout_batch_f64(const pddp_problem* p, const double* table,
-                                   int B, int N, const double* z0,
-                                   const double* U, const double* u_min,
-                                   const double* u_max, const uint8_t* mask,
-                                   double* Z, void* stream) {
-  return pddp::nominal_rollout_impl<double>(p, true, table, B, N, z0, U,
-                                            u_min, u_max, mask, Z, stream);
-}
-int pddp_derivs_batch_f32(const pddp_problem* p, const float* table, int B,
-                          int N, const float* Z, const float* U,
-                          const float* u_min, const float* u_max,
-                          const uint8_t* mask, float* rec, float* L, float* J,
-                          int32_t* state, void* stream) {
-  return pddp::derivs_impl<float>(p, true, table, B, N, Z, U, u_min, u_max,
-                                  mask, rec, L, J, state, stream);
-}
-int pddp_derivs_batch_f64(const pddp_problem* p, const double* table, int B,
-                          int N, const double* Z, const double* U,
-                          const double* u_min, const double* u_max,
-                          const uint8_t* mask, double* rec, double* L,
-                          double* J, int32_t* state, void* stream) {
-  return pddp::derivs_impl<double>(p, true, table, B, N, Z, U, u_min, u_max,
-                                   mask, rec, L, J, state, stream);
-}
-int pddp_line_search_batch_f32(const pddp_problem* p, const float* table,
-                               int B, int N, int A, const float* Z,
-                               const float* U, const float* gains,
-                               const float* alphas, const float* u_min,
-                               const float* u_max, const uint8_t* active,
-                               const int32_t* bwd_status, float* Zc, float* Uc,
-                               float* Jc, void* stream) {
-  return pddp::line_search_impl<float>(p, true, table, B, N, A, Z, U, gains,
-                                       alphas, u_min, u_max, active,
-                                       bwd_status, Zc, Uc, Jc, stream);
-}
-int pddp_line_search_batch_f64(const pddp_problem* p, const double* table,
-                               int B, int N, int A, const double* Z,
-                               const double* U, const double* gains,
-                               const double* alphas, const double* u_min,
-                               const double* u_max, const uint8_t* active,
-                               const int32_t* bwd_status, double* Zc,
-                               double* Uc, double* Jc, void* stream) {
-  return pddp::line_search_impl<double>(p, true, table, B, N, A, Z, U, gains,
-                                        alphas, u_min, u_max, active,
-                                        bwd_status, Zc, Uc, Jc, stream);
-}
+PDDP_PROBLEM_ENTRY_POINTS(f32, float)
+PDDP_PROBLEM_ENTRY_POINTS(f64, double)
+#undef PDDP_PROBLEM_ENTRY_POINTS
 
 }  // extern "C"
