@@ -349,6 +349,69 @@ int pddp_closed_loop_f64(const pddp_problem* problem, int B, int N, int S,
                          const uint8_t* active, double* Xc, double* Uc,
                          double* Jc, double* stats, void* stream);
 
+/* ---- pddp_closed_loop_* under process and measurement noise drawn on the
+ * device (csrc/closed_loop_noise.hip; the reference has no counterpart).
+ * Rollout (b, s), t = 0 .. N-1, in this order:
+ *
+ *   y   = x_t + v_std (.) v_t                (v_std == NULL: y = x_t)
+ *   u_t = clamp(U[b][t] + K[b][t] (y - Z[b][t]))  (gains == NULL: clamp(U[b][t]))
+ *   record x_t, u_t;  J += l(x_t, u_t)       (the true state, the applied
+ *                                             action, the plant row's goals)
+ *   x_{t+1} = plant_{b,s}(x_t, u_t) + w_std (.) w_t    (w_std == NULL: + 0)
+ *
+ * then J += l_f(x_N).  w_std, v_std [n], the launch's, of the run's type, not
+ * both NULL.  Every other argument, the output layout, the statistics and
+ * their order are pddp_closed_loop_*'s.
+ *
+ * w_t (stream 0) and v_t (stream 1) are n unit normals each, a pure function
+ * of (seed, rollout, step, stream, component) - no generator state, no noise
+ * tensor; the same seed gives the same noise to another controller:
+ *   Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter
+ *     r = sample_offset + b S + s  (uint64);
+ *     (c0, c1, c2, c3) = (r & 0xffffffff, r >> 32, t, (stream << 16) | k);
+ *   _f32: call k gives components 4k .. 4k+3: u(x) = ((x >> 9) + 0.5) 2^-23,
+ *     (z0, z1) = sqrt(-2 ln u(x0)) (cos, sin)(2 pi u(x1)), (z2, z3) likewise
+ *     from (x2, x3);
+ *   _f64: call k gives components 2k, 2k+1:
+ *     u(hi, lo) = (((hi << 20) | (lo >> 12)) + 0.5) 2^-52,
+ *     (z0, z1) = sqrt(-2 ln u(x0, x1)) (cos, sin)(2 pi u(x2, x3));
+ *   components beyond n are discarded.  `sample_offset` places a launch's
+ *   rollouts in a longer sequence: trajectories b0.. of a batch, run alone with
+ *   sample_offset + b0 S, see the noise they saw in the batch.
+ *
+ * pddp_closed_loop_draws_* writes those unit normals, W [B][N][S][n]
+ * (time-major like Xc), `which` 0 = w, 1 = v, through the rollouts' own device
+ * function: for tests, and to replay one rollout's noise elsewhere (e.g. as
+ * pddp_mpc_advance_*'s disturbance).
+ * PDDP_E_BADARG: what pddp_closed_loop_* refuses; w_std == v_std == NULL;
+ * draws: a null W, a non-positive size, which not 0 or 1, n > PDDP_MAX_STATE.
+ * PDDP_E_UNSUPPORTED: any encoding but PDDP_ENC_IGNORE_UNCERTAINTY.  All
+ * before any HIP call. */
+int pddp_closed_loop_noisy_f32(const pddp_problem* problem, int B, int N, int S,
+                               const float* Z, const float* U,
+                               const float* gains, const float* z0s,
+                               const float* plant, const float* u_min,
+                               const float* u_max, const float* w_std,
+                               const float* v_std, uint64_t seed,
+                               uint64_t sample_offset, const uint8_t* active,
+                               float* Xc, float* Uc, float* Jc, float* stats,
+                               void* stream);
+int pddp_closed_loop_noisy_f64(const pddp_problem* problem, int B, int N, int S,
+                               const double* Z, const double* U,
+                               const double* gains, const double* z0s,
+                               const double* plant, const double* u_min,
+                               const double* u_max, const double* w_std,
+                               const double* v_std, uint64_t seed,
+                               uint64_t sample_offset, const uint8_t* active,
+                               double* Xc, double* Uc, double* Jc,
+                               double* stats, void* stream);
+int pddp_closed_loop_draws_f32(int B, int N, int S, int n, int which,
+                               uint64_t seed, uint64_t sample_offset,
+                               float* W /* [B][N][S][n] */, void* stream);
+int pddp_closed_loop_draws_f64(int B, int N, int S, int n, int which,
+                               uint64_t seed, uint64_t sample_offset,
+                               double* W /* [B][N][S][n] */, void* stream);
+
 /* ---- pddp.py:209-245 _apply_controller(mpc=True) with ilqr.py:355-362
  * forward(mpc=True) as the controller, batched and with the sample models as
  * the plant: the hand-over between two control steps of a receding-horizon

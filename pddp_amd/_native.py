@@ -26,6 +26,7 @@ BATCH_ROW, BATCH_PARAMS, BATCH_X_GOAL, BATCH_U_GOAL = 20, 0, 8, 16
 REF_ROW, REF_X_GOAL, REF_U_GOAL = 12, 0, 8
 
 c_int, c_double, c_void_p = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
+c_uint64 = ctypes.c_uint64
 
 
 class PddpProblem(ctypes.Structure):
@@ -82,6 +83,9 @@ _SIGS = {
     "pddp_derivs_batch": [_P, _P, c_int, c_int] + [_P] * 10,
     "pddp_line_search_batch": [_P, _P, c_int, c_int, c_int] + [_P] * 12,
     "pddp_closed_loop": [_P, c_int, c_int, c_int] + [_P] * 13,
+    "pddp_closed_loop_noisy": [_P, c_int, c_int, c_int] + [_P] * 9 +
+                              [c_uint64, c_uint64] + [_P] * 6,
+    "pddp_closed_loop_draws": [c_int] * 5 + [c_uint64, c_uint64, _P, _P],
     "pddp_mpc_advance": [_P, _P] + [c_int] * 4 + [_P] * 21,
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
@@ -145,6 +149,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_line_search", "pddp_search_accept", "pddp_accept",
           "pddp_nominal_rollout_batch", "pddp_derivs_batch",
           "pddp_line_search_batch", "pddp_closed_loop", "pddp_mpc_advance",
+          "pddp_closed_loop_noisy", "pddp_closed_loop_draws",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
           "pddp_pack_best", "pddp_sweep_nominal", "pddp_gp_step",

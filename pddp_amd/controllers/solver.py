@@ -767,7 +767,8 @@ class ILQRSolver(object):
     @_on_device
     def closed_loop(self, samples=None, z0=None, params=None, x_goal=None,
                     u_goal=None, feedback=True, accepted=True, keep=False,
-                    active=None, events=None):
+                    active=None, events=None, process_std=None, obs_std=None,
+                    seed=0, sample_offset=0):
         """Runs every trajectory's policy in closed loop, S rollouts each
         (pddp_closed_loop_*: the batched `_apply_controller`, pddp.py:209-245,
         with the sample models as the plant): rollout (b, s) starts at
@@ -784,6 +785,15 @@ class ILQRSolver(object):
         sweep's; `feedback=False`: open loop, u = clamp(U).  `active` [B]
         uint8: trajectories with 0 are skipped, their outputs NaN (X, U:
         unspecified).  `events`: a (start, stop) pair for the dispatch.
+
+        `process_std`, `obs_std` (each a scalar or [n]; None: none of it):
+        noise drawn inside the rollouts (pddp_closed_loop_noisy_*) - the plant
+        steps to x' + process_std (.) w_t, the controller sees x + obs_std (.)
+        v_t, the cost is the true state's.  w_t, v_t are unit normals, a pure
+        function of (`seed`, `sample_offset` + b S + s, t, component): the same
+        seed repeats a run and gives another controller the same noise;
+        `closed_loop_draws` returns them.  With both None this is the
+        noise-free launch, as ever.
 
         Returns an object with `J` [B][S], `stats` [B][4] = (mean, min, max of
         the finite costs, their number) and, with `keep`, `X` [B][N+1][S][n],
@@ -847,13 +857,57 @@ class ILQRSolver(object):
             X=torch.empty(B, N + 1, S, n, **opts) if keep else None,
             U=torch.empty(B, N, S, m, **opts) if keep else None)
         p = _native.ptr
-        self._launch(
-            events, _native.call, "pddp_closed_loop", self.dtype, self._pp, B,
-            N, S, p(self.Z), p(self.U), p(gains),
-            p(None if z0 is None else z0.contiguous()), p(plant),
-            p(self.u_min), p(self.u_max), p(active), p(out.X), p(out.U),
-            p(out.J), p(out.stats), self._s())
+        head = (self._pp, B, N, S, p(self.Z), p(self.U), p(gains),
+                p(None if z0 is None else z0.contiguous()), p(plant),
+                p(self.u_min), p(self.u_max))
+        tail = (p(active), p(out.X), p(out.U), p(out.J), p(out.stats),
+                self._s())
+        if process_std is None and obs_std is None:
+            self._launch(events, _native.call, "pddp_closed_loop", self.dtype,
+                         *(head + tail))
+        else:
+            w_std = self._noise_std("process_std", process_std)
+            v_std = self._noise_std("obs_std", obs_std)
+            self._launch(events, _native.call, "pddp_closed_loop_noisy",
+                         self.dtype, *(head + (
+                             p(w_std), p(v_std), int(seed),
+                             int(sample_offset)) + tail))
         return out
+
+    def _noise_std(self, name, std):
+        """[n] device vector of a noise level given as a scalar or [n]."""
+        if std is None:
+            return None
+        # (a Python number goes straight to the run's dtype, not through f32)
+        std = torch.as_tensor(std, dtype=self.dtype, device=self.device)
+        if std.dim() == 0:
+            std = std.repeat(self.n)
+        if tuple(std.shape) != (self.n,):
+            raise _native.NativeError(
+                "closed_loop: %s has shape %s, expected a scalar or (%d,)" % (
+                    name, tuple(std.shape), self.n))
+        return std.contiguous()
+
+    @_on_device
+    def closed_loop_draws(self, samples, which="process", seed=0,
+                          sample_offset=0):
+        """The unit normals `closed_loop(samples, seed=, sample_offset=)`
+        draws, W [B][N][S][n] (pddp_closed_loop_draws_*; time-major like X):
+        `which` "process" for w_t, "obs" for v_t.  To look at, or to replay,
+        the noise of a rollout - e.g. process_std * W[b, :T, s] as
+        `mpc_closed_loop`'s disturbance."""
+        if which not in ("process", "obs"):
+            raise _native.NativeError(
+                "closed_loop_draws: which is %r, expected 'process' or 'obs'"
+                % (which,))
+        B, N, S = self.B, self.N, int(samples)
+        if S < 1:
+            raise _native.NativeError("closed_loop_draws: %d samples" % S)
+        W = torch.empty(B, N, S, self.n, dtype=self.dtype, device=self.device)
+        _native.call("pddp_closed_loop_draws", self.dtype, B, N, S, self.n,
+                     0 if which == "process" else 1, int(seed),
+                     int(sample_offset), _native.ptr(W), self._s())
+        return W
 
     def _plant_table(self, what, params, x_goal, u_goal):
         """[B][BATCH_ROW] plant rows of a trial whose fields are [B][.]: a
