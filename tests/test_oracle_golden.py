@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+from action_families import eig_sweep_numpy
 from golden_util import (DT, FWD_NAMES, TAGS_DC150, load, load_dc150, np_dtype,
                          rel_err, tags)
 
@@ -221,27 +222,12 @@ def test_backward_eig_branch_vs_numpy(dtype):
             k, K, status = o.backward(f["F_z"], f["F_u"], f["L_z"], f["L_u"],
                                       f["L_zz"], f["L_uz"], f["L_uu"], reg=reg)
             assert status == 0
-            N = f["F_u"].shape[0]
-            Vz, Vzz = f["L_z"][N], f["L_zz"][N]
-            for t in range(N - 1, -1, -1):
-                Fz, Fu = f["F_z"][t], f["F_u"][t]
-                Qz = f["L_z"][t] + Fz.T @ Vz
-                Qu = f["L_u"][t] + Fu.T @ Vz
-                Qzz = f["L_zz"][t] + Fz.T @ Vzz @ Fz
-                Qzz = 0.5 * (Qzz + Qzz.T)
-                Quz = f["L_uz"][t] + Fu.T @ Vzz @ Fz
-                Quu = f["L_uu"][t] + Fu.T @ Vzz @ Fu
-                Quu = 0.5 * (Quu + Quu.T)
-                e, E = np.linalg.eigh(Quu)
-                e = np.where(e < 0, 1e-12, e) + reg
-                inv = (E / e) @ E.T
-                kt, Kt = -inv @ Qu, -inv @ Quz
-                tol = 1e-9 if dtype == "f64" else 2e-3
-                assert np.allclose(k[t], kt, rtol=tol, atol=tol * 10)
-                assert np.allclose(K[t], Kt, rtol=tol, atol=tol * 10)
-                Vz = Qz + Kt.T @ Qu + Kt.T @ Quu @ kt + Quz.T @ kt
-                Vzz = Qzz + Kt.T @ Quu @ Kt + Kt.T @ Quz + Quz.T @ Kt
-                Vzz = 0.5 * (Vzz + Vzz.T)
+            # the float64 numpy restatement (action_families.eig_sweep_numpy)
+            kn, Kn, _ = eig_sweep_numpy(f, reg)
+            tol = 1e-9 if dtype == "f64" else 2e-3
+            for t in range(f["F_u"].shape[0]):
+                assert np.allclose(k[t], kn[t], rtol=tol, atol=tol * 10)
+                assert np.allclose(K[t], Kn[t], rtol=tol, atol=tol * 10)
 
 
 @pytest.mark.parametrize("mode", ["bounded", "free"])
