@@ -75,15 +75,37 @@ def _eye(D, dtype, device):
 
 
 def _cholesky_upper(C, jitter=1e-12, max_jitter=10.0):
-    """Jittered upper Cholesky, escalating x10 (encoding.py:536-564)."""
+    """Jittered upper Cholesky, escalating x10 PER MATRIX: the reference
+    recurses over the batch (encoding.py:536-564, :548-553), so a matrix that
+    needs a higher rung leaves the factors of the others alone.  A batch that
+    passes the first rung is one `cholesky_ex` call.  Otherwise the failed
+    matrices alone climb the ladder (values only), and the factor is taken
+    once more with every matrix at its own rung - a matrix at the rung it had
+    passed gets the bits it had; nothing autograd sees comes from a failed
+    factorisation."""
     eye = _eye(C.shape[-1], C.dtype, C.device)
-    while True:
-        L, info = torch.linalg.cholesky_ex(C + jitter * eye, upper=True)
-        if not bool((info != 0).any()):
-            return L
-        jitter *= 10
-        if jitter > max_jitter:
-            raise RuntimeError("covariance is not positive-definite")
+    L, info = torch.linalg.cholesky_ex(C + jitter * eye, upper=True)
+    bad = info != 0
+    if not bool(bad.any()):
+        return L
+    rung = torch.full(info.shape, jitter, dtype=C.dtype, device=C.device)
+    with torch.no_grad():
+        Cd = C.detach()
+        while bool(bad.any()):
+            jitter *= 10
+            if jitter > max_jitter:
+                raise RuntimeError("covariance is not positive-definite")
+            _, again = torch.linalg.cholesky_ex(Cd[bad] + jitter * eye,
+                                                upper=True)
+            rung[bad] = jitter
+            still = bad.clone()
+            still[bad] = again != 0
+            bad = still
+    L, info = torch.linalg.cholesky_ex(
+        C + rung.unsqueeze(-1).unsqueeze(-1) * eye, upper=True)
+    if bool((info != 0).any()):
+        raise RuntimeError("covariance is not positive-definite")
+    return L
 
 
 def _covar_from(C, V, S):
