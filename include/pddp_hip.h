@@ -554,6 +554,48 @@ int pddp_mpc_advance_track_f64(const pddp_problem* problem,
                                uint8_t* live_log, double* mu, double* delta,
                                int32_t* state, int32_t* iter, uint8_t* active,
                                uint8_t* fresh, int32_t* n_live, void* stream);
+
+/* ---- pddp_closed_loop_* / pddp_closed_loop_noisy_* ALONG A REFERENCE
+ * (csrc/closed_loop_track.hip): the same S rollouts per trajectory, costed
+ * under a goal per time step.  Rollout (b, s) takes
+ *
+ *   J += l(x_t, u_t)  under row min(ref_t0 + t, ref_len - 1) of trajectory b,
+ *                     t = 0 .. N-1
+ *   J += l_f(x_N)     under row min(ref_t0 + N, ref_len - 1), x_goal only
+ *
+ * `ref` [B][ref_len][PDDP_REF_ROW] in the layout above; the S rollouts of a
+ * trajectory share its reference.  plant [B][S][PDDP_BATCH_ROW], nullable: the
+ * plant's PARAMETERS only; its goal fields are not read.  w_std, v_std, seed,
+ * sample_offset: pddp_closed_loop_noisy_*'s law and draws - rollout (b, s) at
+ * step t sees the normals pddp_closed_loop_draws_* writes for it;
+ * w_std == v_std == NULL is the noise-free launch, valid here.  Every other
+ * argument, the feedback law, the clamp, the output layout, the statistics and
+ * their order are pddp_closed_loop_*'s: none of them reads a goal.
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY, any
+ * B, N, S >= 1.  PDDP_E_BADARG: what pddp_closed_loop_* refuses; ref == NULL,
+ * ref_len < 1, ref_t0 < 0; PDDP_E_UNSUPPORTED: any other encoding; both before
+ * any HIP call. */
+int pddp_closed_loop_track_f32(const pddp_problem* problem, const float* ref,
+                               int ref_len, int ref_t0, int B, int N, int S,
+                               const float* Z, const float* U,
+                               const float* gains, const float* z0s,
+                               const float* plant, const float* u_min,
+                               const float* u_max, const float* w_std,
+                               const float* v_std, uint64_t seed,
+                               uint64_t sample_offset, const uint8_t* active,
+                               float* Xc, float* Uc, float* Jc, float* stats,
+                               void* stream);
+int pddp_closed_loop_track_f64(const pddp_problem* problem, const double* ref,
+                               int ref_len, int ref_t0, int B, int N, int S,
+                               const double* Z, const double* U,
+                               const double* gains, const double* z0s,
+                               const double* plant, const double* u_min,
+                               const double* u_max, const double* w_std,
+                               const double* v_std, uint64_t seed,
+                               uint64_t sample_offset, const uint8_t* active,
+                               double* Xc, double* Uc, double* Jc,
+                               double* stats, void* stream);
+
 /* ---- ilqr.py:102-181 _step() accept / reject, :364-390 mu schedule and the
  * fit() loop bookkeeping (:298-314), per trajectory, device resident -------- */
 /* Controller state arrays (all [B]):

@@ -86,6 +86,8 @@ _SIGS = {
     "pddp_closed_loop_noisy": [_P, c_int, c_int, c_int] + [_P] * 9 +
                               [c_uint64, c_uint64] + [_P] * 6,
     "pddp_closed_loop_draws": [c_int] * 5 + [c_uint64, c_uint64, _P, _P],
+    "pddp_closed_loop_track": [_P, _P] + [c_int] * 5 + [_P] * 9 +
+                              [c_uint64, c_uint64] + [_P] * 6,
     "pddp_mpc_advance": [_P, _P] + [c_int] * 4 + [_P] * 21,
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
@@ -150,6 +152,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_nominal_rollout_batch", "pddp_derivs_batch",
           "pddp_line_search_batch", "pddp_closed_loop", "pddp_mpc_advance",
           "pddp_closed_loop_noisy", "pddp_closed_loop_draws",
+          "pddp_closed_loop_track",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
           "pddp_pack_best", "pddp_sweep_nominal", "pddp_gp_step",

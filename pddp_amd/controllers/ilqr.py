@@ -300,7 +300,10 @@ class iLQRController(Controller):
         `_apply_controller` (pddp.py:209-245) returns, with a trajectory axis:
         ((X[:-1], U, X[1:] - X[:-1]), J), X time-major [N+1][S][n] per
         trajectory and J [S]; after a fit without batch axis the one
-        trajectory's, otherwise with the leading B."""
+        trajectory's, otherwise with the leading B.  After `set_reference`,
+        `track=True` costs the rollouts along the reference (from the row the
+        window stands at); without it the call is refused while a reference
+        is set."""
         if self._solver is None:
             raise RuntimeError("You need to call fit or step first")
         r = self._solver.closed_loop(keep=True, **kwargs)

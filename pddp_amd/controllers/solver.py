@@ -330,8 +330,9 @@ class ILQRSolver(object):
         pddp_*_track_* entry points and every round is derivs, backward,
         line_search, accept (`records+separate`); `mpc_closed_loop()` reads
         the window from `ref_start + t` at control step t.  The sweep from the
-        nominal, the one-launch round, the fused search and `closed_loop()`
-        take one goal per trajectory and refuse.  The nominal rollout reads no
+        nominal, the one-launch round and the fused search take one goal per
+        trajectory and refuse; so does `closed_loop()` unless it is told to
+        follow the reference (`track=True`).  The nominal rollout reads no
         goal: the current nominal stays as it is."""
         if not self._batch_problem_possible():
             raise _native.NativeError(
@@ -768,7 +769,7 @@ class ILQRSolver(object):
     def closed_loop(self, samples=None, z0=None, params=None, x_goal=None,
                     u_goal=None, feedback=True, accepted=True, keep=False,
                     active=None, events=None, process_std=None, obs_std=None,
-                    seed=0, sample_offset=0):
+                    seed=0, sample_offset=0, track=False):
         """Runs every trajectory's policy in closed loop, S rollouts each
         (pddp_closed_loop_*: the batched `_apply_controller`, pddp.py:209-245,
         with the sample models as the plant): rollout (b, s) starts at
@@ -799,9 +800,30 @@ class ILQRSolver(object):
         the finite costs, their number) and, with `keep`, `X` [B][N+1][S][n],
         `U` [B][N][S][m] (None otherwise: only costs leave the chip).
         Stream-ordered on the solver's stream; the controller state, the
-        nominal, the plan and a captured graph are not touched.  Refused
-        while a reference is set: the rollouts are costed under one goal."""
-        self._one_goal("closed_loop")
+        nominal, the plan and a captured graph are not touched.
+
+        While a reference is set (`set_reference`) the call is refused - the
+        rollouts would be costed under one goal - unless `track=True`: then
+        rollout (b, s) takes the stage cost of step t under reference row
+        min(ref_start + t, L - 1) of trajectory b and the terminal cost under
+        row min(ref_start + N, L - 1) (pddp_closed_loop_track_*), with or
+        without noise; all S rollouts of a trajectory share its reference, and
+        the plant fields supply parameters only: `x_goal` / `u_goal` would not
+        be read and are refused.  `ref_start` is read, not moved."""
+        if track:
+            if self.reference is None:
+                raise _native.NativeError(
+                    "closed_loop(track=True): no reference is set "
+                    "(set_reference)")
+            if x_goal is not None or u_goal is not None:
+                raise _native.NativeError(
+                    "closed_loop(track=True) takes the goals of every step "
+                    "from the reference; x_goal / u_goal would not be read")
+        elif self.reference is not None:
+            raise _native.NativeError(
+                "closed_loop takes ONE goal per trajectory; with a reference "
+                "(set_reference) pass track=True to cost the rollouts along "
+                "it")
         if not self._batch_problem_possible():
             raise _native.NativeError(
                 "closed_loop needs a sample problem under IGNORE_UNCERTAINTY "
@@ -862,16 +884,21 @@ class ILQRSolver(object):
                 p(self.u_min), p(self.u_max))
         tail = (p(active), p(out.X), p(out.U), p(out.J), p(out.stats),
                 self._s())
-        if process_std is None and obs_std is None:
+        w_std = self._noise_std("process_std", process_std)
+        v_std = self._noise_std("obs_std", obs_std)
+        noise = (p(w_std), p(v_std), int(seed), int(sample_offset))
+        if track:  # (with or without noise: one entry point)
+            ref = (p(self.reference), self.reference.shape[1],
+                   self.ref_start)
+            self._launch(events, _native.call, "pddp_closed_loop_track",
+                         self.dtype, *(head[:1] + ref + head[1:] + noise +
+                                       tail))
+        elif process_std is None and obs_std is None:
             self._launch(events, _native.call, "pddp_closed_loop", self.dtype,
                          *(head + tail))
         else:
-            w_std = self._noise_std("process_std", process_std)
-            v_std = self._noise_std("obs_std", obs_std)
             self._launch(events, _native.call, "pddp_closed_loop_noisy",
-                         self.dtype, *(head + (
-                             p(w_std), p(v_std), int(seed),
-                             int(sample_offset)) + tail))
+                         self.dtype, *(head + noise + tail))
         return out
 
     def _noise_std(self, name, std):

@@ -13,7 +13,8 @@
 // output layout differ; the parameter count is model_params.hpp's, the row
 // writer stays written out at its one call site.  That text
 // is closed_loop_body.inc: closed_loop_noise.hip includes it too, with noise
-// drawn at its hooks; here the hooks are empty.
+// drawn at its hooks, and closed_loop_track.hip with the goals
+// of a reference row at its goal hooks as well (3.4h); here the hooks are empty.
 #include <limits>
 #include <type_traits>
 #include "models.hpp"
@@ -36,7 +37,13 @@ __global__ __launch_bounds__(kClosedLoopThreads) void closed_loop_kernel(
 #define PDDP_NOISE_OF_STEP
 #define PDDP_SEEN(c) z[c]
 #define PDDP_NEXT(j) zn[j]
+#define PDDP_GOALS_TAKE_FIRST
+#define PDDP_GOALS_REQUEST_NEXT
+#define PDDP_GOALS_TAKE_NEXT
 #include "closed_loop_body.inc"
+#undef PDDP_GOALS_TAKE_NEXT
+#undef PDDP_GOALS_REQUEST_NEXT
+#undef PDDP_GOALS_TAKE_FIRST
 #undef PDDP_NEXT
 #undef PDDP_SEEN
 #undef PDDP_NOISE_OF_STEP

@@ -1,6 +1,6 @@
-// closed_loop_args.hpp - what closed_loop.hip and closed_loop_noise.hip share
-// besides the kernel text (closed_loop_body.inc): the argument block, the cost
-// statistics and the launch geometry.
+// closed_loop_args.hpp - what closed_loop.hip, closed_loop_noise.hip and
+// closed_loop_track.hip share besides the kernel text (closed_loop_body.inc):
+// the argument block, the cost statistics and the launch geometry.
 #pragma once
 
 #include <limits>

@@ -1,6 +1,7 @@
 // closed_loop_body.inc - the closed-loop rollouts of a lane and the statistics
-// of a controller's costs: the text of closed_loop_kernel (closed_loop.hip) and
-// closed_loop_noisy_kernel (closed_loop_noise.hip).  The including kernel has
+// of a controller's costs: the text of closed_loop_kernel (closed_loop.hip),
+// closed_loop_noisy_kernel (closed_loop_noise.hip) and closed_loop_track_kernel
+// (closed_loop_track.hip).  The including kernel has
 // `shared`, `a` (ClosedLoopArgs), `Znom`, `Unom`, `gains` and defines
 //   PDDP_NOISE_LEVELS      after the bounds: empty, or the launch's noise levels
 //   PDDP_NOISE_OF_ROLLOUT  before the time loop: empty, or what rollout (b, s)
@@ -11,6 +12,14 @@
 //                          step: z[c], or with measurement noise
 //   PDDP_NEXT(j)           component j of the next state: zn[j], or with process
 //                          noise
+// and, for the goals of `P` (empty where a rollout has ONE goal: the plant
+// row's or the shared problem's; closed_loop_track.hip takes them from a
+// reference row, as tracking.hip does at line_search_body.inc's hooks)
+//   PDDP_GOALS_TAKE_FIRST    ahead of the time loop: row 0's over P's
+//   PDDP_GOALS_REQUEST_NEXT  behind the step's draws: row t + 1, ahead of the
+//                            dependent chain
+//   PDDP_GOALS_TAKE_NEXT     at the end of the step: the requested row over P's
+//                            (up to row N, the terminal cost's)
 // An included text, not a device function: each kernel compiles to the
 // instructions it would have typed out (DESIGN.md 3.4f, 3.4g).
   using D = ModelDims<MODEL>;
@@ -82,6 +91,7 @@
         for (int j = 0; j < m * n; ++j) kr[j] = Kb[j];
       }
       PDDP_NOISE_OF_ROLLOUT
+      PDDP_GOALS_TAKE_FIRST
 
       // time-major output [b][t][s][.]: at every step the lanes of a
       // trajectory write one contiguous segment (the note at LineSearchArgs)
@@ -103,6 +113,7 @@
           for (int j = 0; j < m * n; ++j) kr2[j] = Kb[(size_t)tn * GS + j];
         }
         PDDP_NOISE_OF_STEP
+        PDDP_GOALS_REQUEST_NEXT
 
 #pragma unroll
         for (int r = 0; r < m; ++r) {
@@ -134,6 +145,7 @@
         for (int j = 0; j < m; ++j) ur[j] = ur2[j];
 #pragma unroll
         for (int j = 0; j < m * n; ++j) kr[j] = kr2[j];
+        PDDP_GOALS_TAKE_NEXT
       }
       if (keep) {
 #pragma unroll

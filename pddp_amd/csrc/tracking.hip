@@ -25,24 +25,9 @@
 #include "models.hpp"
 #include "problem_args.hpp"
 #include "model_params.hpp"
+#include "ref_args.hpp"
 
 namespace pddp {
-
-// where the goals come from; ref_t0 arrives clamped to ref_len - 1, so that
-// `ref_t0 + min(i, hold)` neither leaves the reference nor overflows
-template <typename T>
-struct RefArgs {
-  const T* table;  // [B][PDDP_BATCH_ROW] or NULL: the model parameters
-  const T* ref;    // [B][ref_len][PDDP_REF_ROW]
-  int ref_len, ref_t0;
-};
-
-template <typename T>
-PDDP_DEV const T* ref_row(const RefArgs<T>& g, int b, int i) {
-  const int hold = g.ref_len - 1 - g.ref_t0;
-  const int row = g.ref_t0 + (i < hold ? i : hold);
-  return g.ref + ((size_t)b * g.ref_len + row) * PDDP_REF_ROW;
-}
 
 // A statement, not a function (problem_kernels.hip's note: the same statements
 // inlined from a function reach the optimiser in another order - here too, the
@@ -205,16 +190,6 @@ static int launch_track_advance(const pddp_problem& p,
   PDDP_LAUNCH((track_mpc_advance_kernel<T, MODEL>), blocks, dim3(kWave), 0, st,
               P, w.a, w.r);
   return launch_status();
-}
-
-// ref_t0 clamped to the last row here (see RefArgs); false: PDDP_E_BADARG
-template <typename T>
-static bool ref_args(const T* table, const T* ref, int ref_len, int ref_t0,
-                     RefArgs<T>* out) {
-  if (ref == nullptr || ref_len < 1 || ref_t0 < 0) return false;
-  *out = RefArgs<T>{table, ref, ref_len,
-                    ref_t0 < ref_len - 1 ? ref_t0 : ref_len - 1};
-  return true;
 }
 
 template <typename T>
