@@ -555,6 +555,63 @@ int pddp_mpc_advance_track_f64(const pddp_problem* problem,
                                int32_t* state, int32_t* iter, uint8_t* active,
                                uint8_t* fresh, int32_t* n_live, void* stream);
 
+/* ---- per-trajectory cost weights (csrc/weights.hip) -------------------------
+ * `weights` [B][PDDP_WEIGHT_ROW], device memory of the run's dtype: row b holds
+ *   [PDDP_WEIGHT_Q      .. +7]  the diagonal of Q      of trajectory b
+ *                               (augmented coordinates, PDDP_MAX_AUG)
+ *   [PDDP_WEIGHT_Q_TERM .. +7]  the diagonal of Q_term
+ *   [PDDP_WEIGHT_R      .. +3]  the diagonal of R      (PDDP_MAX_ACTION)
+ * Trajectory b's cost matrices are `problem`'s with their diagonals REPLACED
+ * by row b; the off-diagonal entries stay `problem`'s.  Entries of a row
+ * beyond the model's aug_size / action_size are never read.  An f32 row is 80
+ * bytes, an f64 row 160: rows are 16-byte aligned when the base is.  Nothing
+ * checks that the matrices of a row are positive (semi-)definite:
+ * ILQRSolver.set_batch_weights does, on the host.
+ * table [B][PDDP_BATCH_ROW], nullable: the model parameters AND goals of
+ * trajectory b are row b's (as pddp_*_batch_*), else `problem`'s.
+ *
+ * pddp_derivs_weighted_* / pddp_line_search_weighted_*: every other argument
+ * and every result as pddp_derivs_batch_* / pddp_line_search_batch_* (one
+ * workgroup per trajectory and one lane per time step; one lane per
+ * (trajectory, step size), any A).  The nominal rollout reads no cost:
+ * pddp_nominal_rollout[_batch]_* serves.
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY.
+ * PDDP_E_BADARG: weights == NULL and everything the siblings answer it for
+ * (B * A > 0x7fffffff included); PDDP_E_UNSUPPORTED: any other encoding or
+ * model; both before any HIP call. */
+#define PDDP_WEIGHT_ROW 20
+#define PDDP_WEIGHT_Q 0
+#define PDDP_WEIGHT_Q_TERM 8
+#define PDDP_WEIGHT_R 16
+int pddp_derivs_weighted_f32(const pddp_problem* problem, const float* table,
+                             const float* weights, int B, int N,
+                             const float* Z, const float* U,
+                             const float* u_min, const float* u_max,
+                             const uint8_t* mask, float* rec, float* L,
+                             float* J, int32_t* state, void* stream);
+int pddp_derivs_weighted_f64(const pddp_problem* problem, const double* table,
+                             const double* weights, int B, int N,
+                             const double* Z, const double* U,
+                             const double* u_min, const double* u_max,
+                             const uint8_t* mask, double* rec, double* L,
+                             double* J, int32_t* state, void* stream);
+int pddp_line_search_weighted_f32(const pddp_problem* problem,
+                                  const float* table, const float* weights,
+                                  int B, int N, int A, const float* Z,
+                                  const float* U, const float* gains,
+                                  const float* alphas, const float* u_min,
+                                  const float* u_max, const uint8_t* active,
+                                  const int32_t* bwd_status, float* Zc,
+                                  float* Uc, float* Jc, void* stream);
+int pddp_line_search_weighted_f64(const pddp_problem* problem,
+                                  const double* table, const double* weights,
+                                  int B, int N, int A, const double* Z,
+                                  const double* U, const double* gains,
+                                  const double* alphas, const double* u_min,
+                                  const double* u_max, const uint8_t* active,
+                                  const int32_t* bwd_status, double* Zc,
+                                  double* Uc, double* Jc, void* stream);
+
 /* ---- pddp_closed_loop_* / pddp_closed_loop_noisy_* ALONG A REFERENCE
  * (csrc/closed_loop_track.hip): the same S rollouts per trajectory, costed
  * under a goal per time step.  Rollout (b, s) takes

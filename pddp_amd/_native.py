@@ -24,6 +24,10 @@ BATCH_ROW, BATCH_PARAMS, BATCH_X_GOAL, BATCH_U_GOAL = 20, 0, 8, 16
 # the reference of the pddp_*_track_* entry points: one row per trajectory and
 # time step (PDDP_REF_* of include/pddp_hip.h)
 REF_ROW, REF_X_GOAL, REF_U_GOAL = 12, 0, 8
+# the cost weights of the pddp_*_weighted_* entry points: one row per
+# trajectory, the diagonals of Q, Q_term, R (PDDP_WEIGHT_* of
+# include/pddp_hip.h)
+WEIGHT_ROW, WEIGHT_Q, WEIGHT_Q_TERM, WEIGHT_R = 20, 0, 8, 16
 
 c_int, c_double, c_void_p = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 c_uint64 = ctypes.c_uint64
@@ -92,6 +96,8 @@ _SIGS = {
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
     "pddp_mpc_advance_track": [_P, _P, _P] + [c_int] * 6 + [_P] * 21,
+    "pddp_derivs_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] * 10,
+    "pddp_line_search_weighted": [_P, _P, _P] + [c_int] * 3 + [_P] * 12,
     "pddp_search_accept": [_P, c_int, c_int, c_int] + [_P] * 11 +
                           [c_double, c_double, c_int] +
                           [_P] * 11,
@@ -155,6 +161,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_closed_loop_track",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
+          "pddp_derivs_weighted", "pddp_line_search_weighted",
           "pddp_pack_best", "pddp_sweep_nominal", "pddp_gp_step",
           "pddp_gp_step_masked",
           "pddp_gp_rollout")

@@ -327,6 +327,21 @@ class iLQRController(Controller):
             raise RuntimeError("You need to call fit or step first")
         self._solver.clear_reference()
 
+    def set_batch_weights(self, q=None, q_term=None, r=None, check=True):
+        """Per-trajectory diagonals of Q, Q_term, R for the solver of the last
+        fit / step: `ILQRSolver.set_batch_weights` (its arguments; with a fit
+        without batch axis, [1][.])."""
+        if self._solver is None:
+            raise RuntimeError("You need to call fit or step first")
+        self._solver.set_batch_weights(q, q_term, r, check)
+
+    def clear_batch_weights(self):
+        """`ILQRSolver.clear_batch_weights` of the solver of the last fit /
+        step."""
+        if self._solver is None:
+            raise RuntimeError("You need to call fit or step first")
+        self._solver.clear_batch_weights()
+
     def mpc_closed_loop(self, steps, rounds_per_step=10, **kwargs):
         """A receding-horizon trial of every trajectory on the device:
         `ILQRSolver.mpc_closed_loop` (its arguments) of the solver of the last

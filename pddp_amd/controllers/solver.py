@@ -49,6 +49,11 @@ pddp_*_batch_* entry points, and every round is records+separate.
 read from row `ref_start` on): derivs and line search are then the
 pddp_*_track_* entry points, every round is records+separate, and
 `mpc_closed_loop()` moves the window by one row per control step.
+
+`set_batch_weights()` gives every trajectory its own diagonals of Q, Q_term
+and R (`batch_weights`): derivs and line search are then the pddp_*_weighted_*
+entry points, with the table's address or NULL, and every round is
+records+separate.  Weights and a reference refuse each other.
 """
 import ctypes
 import functools
@@ -184,6 +189,9 @@ class ILQRSolver(object):
         # horizon index 0 reads: set_reference()
         self.reference = None
         self.ref_start = 0
+        # [B][_native.WEIGHT_ROW] per-trajectory diagonals of Q, Q_term, R, or
+        # None: set_batch_weights()
+        self.batch_weights = None
 
     def _nominal_sweep_possible(self):
         """pddp_sweep_nominal_*'s domain (include/pddp_hip.h).  At every
@@ -303,9 +311,11 @@ class ILQRSolver(object):
         self._restore_plan()
 
     def _restore_plan(self):
-        """After a table or a reference went: the plan's inputs as the
-        constructor leaves them, unless the other one is still set."""
-        if self.batch_table is None and self.reference is None:
+        """After a table, a reference or the weights went: the plan's inputs
+        as the constructor leaves them, unless another of them is still
+        set."""
+        if self.batch_table is None and self.reference is None and \
+                self.batch_weights is None:
             self._fused = self._one_launch = None
             self._nominal_sweep = None if (
                 self._nominal_sweep_possible() and
@@ -339,6 +349,11 @@ class ILQRSolver(object):
                 "set_reference needs a sample problem under "
                 "IGNORE_UNCERTAINTY on the native path (no plugin, no "
                 "Gaussian encoding)")
+        if self.batch_weights is not None:
+            raise _native.NativeError(
+                "set_reference: per-trajectory cost weights are set "
+                "(set_batch_weights); weights together with a reference are "
+                "not supported - clear_batch_weights() first")
         N_ = _native
         B, na, m = self.B, self.problem.aug_size, self.m
         opts = dict(dtype=self.dtype, device=self.device)
@@ -400,6 +415,125 @@ class ILQRSolver(object):
         self.ref_start = 0
         self._restore_plan()
 
+    @_on_device
+    def set_batch_weights(self, q=None, q_term=None, r=None, check=True):
+        """Per-trajectory cost weights: `q`, `q_term` [B][na] (augmented
+        coordinates) and `r` [B][m] REPLACE the diagonals of Q, Q_term and R
+        for trajectory b; a block not given keeps the shared diagonal.  The
+        off-diagonal entries, the model, the encoding and the action bounds
+        stay shared; parameters and goals stay the table's where one is set.
+
+        Builds `batch_weights` ([B][20], include/pddp_hip.h); from then on the
+        derivative records and the line search are the pddp_*_weighted_* entry
+        points and every round is derivs, backward, line_search, accept
+        (`records+separate`): the sweep from the nominal, the one-launch round
+        and the fused search take one cost for the batch and refuse.  The
+        nominal rollout reads no cost: the current nominal stays as it is.
+        `closed_loop()`, `closed_loop_draws()` and `mpc_closed_loop()` stay
+        available; the costs they REPORT are under the shared problem's Q,
+        Q_term, R.  Weights and a reference (`set_reference`) refuse each
+        other.
+
+        `check` (default): every trajectory's matrices are tested on the
+        host, in float64, once - one copy of [B][20] numbers.  The symmetrised
+        Q_b and Q_term_b must have no eigenvalue below -1e-9 max |entry| (nor
+        below the shared matrix's own lowest, where that is lower: the shared
+        cost is never refused), R_b only positive ones; otherwise NativeError
+        names the first offending trajectory and matrix.  (A diagonal lowered
+        under an off-diagonal entry makes the cost indefinite, and the solver
+        then answers with NOT_PD / MAX_REG states that look like a tuning
+        result.)"""
+        if not self._batch_problem_possible():
+            raise _native.NativeError(
+                "set_batch_weights needs a sample problem under "
+                "IGNORE_UNCERTAINTY on the native path (no plugin, no "
+                "Gaussian encoding)")
+        if self.reference is not None:
+            raise _native.NativeError(
+                "set_batch_weights: a reference is set (set_reference); "
+                "weights together with a reference are not supported - "
+                "clear_reference() first")
+        N_ = _native
+        prob = self.problem
+        na, m = prob.aug_size, self.m
+        # (the shared diagonals: double -> T as convert_problem, _shared_row)
+        row = torch.zeros(N_.WEIGHT_ROW, dtype=torch.float64)
+        for off, mat, ld, k in ((N_.WEIGHT_Q, prob.Q, N_.MAX_AUG, na),
+                                (N_.WEIGHT_Q_TERM, prob.Q_term, N_.MAX_AUG,
+                                 na),
+                                (N_.WEIGHT_R, prob.R, N_.MAX_ACTION, m)):
+            row[off:off + k] = torch.tensor(
+                [mat[i * ld + i] for i in range(k)], dtype=torch.float64)
+        weights = row.to(self.dtype).to(self.device).repeat(self.B, 1)
+        for name, block, off, width in (("q", q, N_.WEIGHT_Q, na),
+                                        ("q_term", q_term, N_.WEIGHT_Q_TERM,
+                                         na),
+                                        ("r", r, N_.WEIGHT_R, m)):
+            if block is None:
+                continue
+            block = torch.as_tensor(block)
+            if tuple(block.shape) != (self.B, width):
+                raise _native.NativeError(
+                    "set_batch_weights: %s has shape %s, expected (%d, %d)" % (
+                        name, tuple(block.shape), self.B, width))
+            weights[:, off:off + width] = block.to(dtype=self.dtype,
+                                                   device=self.device)
+        if check:
+            self._check_weights(weights)
+        self.batch_weights = weights.contiguous()
+        self._one_launch = self._nominal_sweep = self._fused = False
+        self._derivs_due = True
+        self._rec_stale = True  # (the records in `_rec`: another cost's)
+        self._graph = None
+
+    def _check_weights(self, weights):
+        """set_batch_weights(check=True): the eigenvalues of every
+        trajectory's Q, Q_term (symmetrised, >= -1e-9 max |entry| or the
+        shared matrix's own lowest) and R (> 0), on the host in float64."""
+        N_ = _native
+        prob = self.problem
+        w = weights.to(dtype=torch.float64, device="cpu")
+        found = None  # (trajectory, matrix) of the first offender
+        for name, mat, ld, k, off, positive in (
+                ("Q", prob.Q, N_.MAX_AUG, prob.aug_size, N_.WEIGHT_Q, False),
+                ("Q_term", prob.Q_term, N_.MAX_AUG, prob.aug_size,
+                 N_.WEIGHT_Q_TERM, False),
+                ("R", prob.R, N_.MAX_ACTION, self.m, N_.WEIGHT_R, True)):
+            M = torch.tensor(list(mat), dtype=torch.float64).reshape(
+                ld, ld)[:k, :k]
+            M = 0.5 * (M + M.T)
+            # (the shared matrix's own lowest eigenvalue is allowed: the
+            # double cartpole's Q, rank one in exact arithmetic, has one of
+            # -1e-8 from the float32 rounding of its entries)
+            slack = max(0.0, -float(torch.linalg.eigvalsh(M)[0]))
+            M = M.repeat(self.B, 1, 1)
+            idx = torch.arange(k)
+            M[:, idx, idx] = w[:, off:off + k]
+            finite = torch.isfinite(M).flatten(1).all(1)
+            M[~finite] = 0.0  # (a row with inf / NaN offends as it is)
+            low = torch.linalg.eigvalsh(M)[:, 0]
+            bad = ~finite | ((low <= 0) if positive else (
+                low < -torch.clamp(
+                    1e-9 * M.abs().flatten(1).max(1).values, min=slack)))
+            if bool(bad.any()):
+                b = int(torch.nonzero(bad)[0])
+                if found is None or b < found[0]:
+                    found = (b, name, "" if positive else "semi-")
+        if found is not None:
+            raise _native.NativeError(
+                "set_batch_weights: %s of trajectory %d is not positive "
+                "%sdefinite with these weights (check=False skips this "
+                "test)" % (found[1], found[0], found[2]))
+
+    def clear_batch_weights(self):
+        """Back to the shared cost: what `clear_batch_problem()` restores;
+        with a table still set its plan stays.  (Nothing to do without
+        weights.)"""
+        if self.batch_weights is None:
+            return
+        self.batch_weights = None
+        self._restore_plan()
+
     def _one_goal(self, what):
         if self.reference is not None:
             raise _native.NativeError(
@@ -409,6 +543,11 @@ class ILQRSolver(object):
 
     def _one_problem(self, what):
         self._one_goal(what)
+        if self.batch_weights is not None:
+            raise _native.NativeError(
+                "%s evaluates ONE cost for the whole batch; with "
+                "set_batch_weights() a round is derivs, backward, line_search, "
+                "accept" % what)
         if self.batch_table is not None:
             raise _native.NativeError(
                 "%s evaluates ONE problem for the whole batch; with "
@@ -427,7 +566,13 @@ class ILQRSolver(object):
     def _goal_call(self, name, *args):
         """A problem kernel that reads the goals (records, line search): the
         `_track` entry point, with the table's address or NULL, while a
-        reference is set."""
+        reference is set; the `_weighted` one, likewise, while weights are
+        (the two exclude each other; the addresses are looked up at the
+        call)."""
+        if self.batch_weights is not None:
+            return _native.call(name + "_weighted", self.dtype, self._pp,
+                                _native.ptr(self.batch_table),
+                                _native.ptr(self.batch_weights), *args)
         if self.reference is None:
             return self._problem_call(name, *args)
         return _native.call(name + "_track", self.dtype, self._pp,
@@ -588,7 +733,8 @@ class ILQRSolver(object):
     # -- the round's launch plan ----------------------------------------------
     def _plan(self, variant, search_events=None):
         """The sequence a round tries first (module docstring)."""
-        if self.batch_table is not None or self.reference is not None:
+        if self.batch_table is not None or self.reference is not None or \
+                self.batch_weights is not None:
             # (the other sequences' kernels take one problem for the batch)
             return RECORDS_SEPARATE
         if variant == 0 and self._nominal_sweep is not False and \
@@ -599,7 +745,8 @@ class ILQRSolver(object):
 
     def _fused_allowed(self):
         return self.plugin is None and self._fused is not False and \
-            self.batch_table is None and self.reference is None
+            self.batch_table is None and self.reference is None and \
+            self.batch_weights is None
 
     def _one_launch_applied(self):
         return self._one_launch is True
@@ -809,7 +956,12 @@ class ILQRSolver(object):
         row min(ref_start + N, L - 1) (pddp_closed_loop_track_*), with or
         without noise; all S rollouts of a trajectory share its reference, and
         the plant fields supply parameters only: `x_goal` / `u_goal` would not
-        be read and are refused.  `ref_start` is read, not moved."""
+        be read and are refused.  `ref_start` is read, not moved.
+
+        With per-trajectory cost weights (`set_batch_weights`) the call is
+        NOT refused and its kernels are unchanged: `J` and `stats` are under
+        the shared problem's Q, Q_term, R and the plant row's goals, whatever
+        weights each policy was fitted under - the common yardstick."""
         if track:
             if self.reference is None:
                 raise _native.NativeError(
@@ -922,7 +1074,10 @@ class ILQRSolver(object):
         draws, W [B][N][S][n] (pddp_closed_loop_draws_*; time-major like X):
         `which` "process" for w_t, "obs" for v_t.  To look at, or to replay,
         the noise of a rollout - e.g. process_std * W[b, :T, s] as
-        `mpc_closed_loop`'s disturbance."""
+        `mpc_closed_loop`'s disturbance.  (No cost is read: per-trajectory
+        cost weights, `set_batch_weights`, change nothing here; the costs
+        `closed_loop` reports for these draws are under the shared problem's
+        Q, Q_term, R and the plant row's goals - the common yardstick.)"""
         if which not in ("process", "obs"):
             raise _native.NativeError(
                 "closed_loop_draws: which is %r, expected 'process' or 'obs'"
@@ -1007,7 +1162,13 @@ class ILQRSolver(object):
         row, the terminal cost under the next - and the plant fields supply
         parameters only (`x_goal`, `u_goal` are not read).  Only the integer
         offset changes from step to step; afterwards `ref_start` has advanced
-        by `steps`, so that a continued trial continues the reference."""
+        by `steps`, so that a continued trial continues the reference.
+
+        With per-trajectory cost weights (`set_batch_weights`) the rounds
+        inside the trial optimise under each trajectory's weights; the cost
+        the trial reports (`J`) is under the shared problem's Q, Q_term, R
+        and the plant row's goals - the common yardstick.  The advance kernel
+        is unchanged."""
         if not self._batch_problem_possible():
             raise _native.NativeError(
                 "mpc_closed_loop needs a sample problem under "
@@ -1169,7 +1330,8 @@ class ILQRSolver(object):
                self.kernel_variant)
         if self._graph is not None and self._graph[0] == key:
             return self._graph[1]
-        if self.batch_table is not None or self.reference is not None:
+        if self.batch_table is not None or self.reference is not None or \
+                self.batch_weights is not None:
             self.sync_records()  # (a launch that belongs to no round)
         torch.cuda.synchronize(self.device)
         if self.plugin is None:
