@@ -293,6 +293,12 @@ class iLQRController(Controller):
         self._U_nominal = torch.cat([Un[..., 1:, :], Un[..., -1:, :]], -2)
         return u
 
+    def _fitted_solver(self):
+        """The solver of the last fit / step."""
+        if self._solver is None:
+            raise RuntimeError("You need to call fit or step first")
+        return self._solver
+
     def closed_loop(self, **kwargs):
         """The fitted policy of every trajectory run in closed loop on the
         device, S rollouts each: `ILQRSolver.closed_loop` (its arguments) of
@@ -304,9 +310,7 @@ class iLQRController(Controller):
         `track=True` costs the rollouts along the reference (from the row the
         window stands at); without it the call is refused while a reference
         is set."""
-        if self._solver is None:
-            raise RuntimeError("You need to call fit or step first")
-        r = self._solver.closed_loop(keep=True, **kwargs)
+        r = self._fitted_solver().closed_loop(keep=True, **kwargs)
         X, U, J = r.X, r.U, r.J
         if not self._batched:
             X, U, J = X[0], U[0], J[0]
@@ -317,30 +321,22 @@ class iLQRController(Controller):
         """A goal per time step for the solver of the last fit / step:
         `ILQRSolver.set_reference` (its arguments; with a fit without batch
         axis, [1][L][.]).  `mpc_closed_loop` then follows the reference."""
-        if self._solver is None:
-            raise RuntimeError("You need to call fit or step first")
-        self._solver.set_reference(x_ref, u_ref, start)
+        self._fitted_solver().set_reference(x_ref, u_ref, start)
 
     def clear_reference(self):
         """`ILQRSolver.clear_reference` of the solver of the last fit / step."""
-        if self._solver is None:
-            raise RuntimeError("You need to call fit or step first")
-        self._solver.clear_reference()
+        self._fitted_solver().clear_reference()
 
     def set_batch_weights(self, q=None, q_term=None, r=None, check=True):
         """Per-trajectory diagonals of Q, Q_term, R for the solver of the last
         fit / step: `ILQRSolver.set_batch_weights` (its arguments; with a fit
         without batch axis, [1][.])."""
-        if self._solver is None:
-            raise RuntimeError("You need to call fit or step first")
-        self._solver.set_batch_weights(q, q_term, r, check)
+        self._fitted_solver().set_batch_weights(q, q_term, r, check)
 
     def clear_batch_weights(self):
         """`ILQRSolver.clear_batch_weights` of the solver of the last fit /
         step."""
-        if self._solver is None:
-            raise RuntimeError("You need to call fit or step first")
-        self._solver.clear_batch_weights()
+        self._fitted_solver().clear_batch_weights()
 
     def mpc_closed_loop(self, steps, rounds_per_step=10, **kwargs):
         """A receding-horizon trial of every trajectory on the device:
@@ -351,9 +347,8 @@ class iLQRController(Controller):
         returns, ((X[:-1], U, X[1:] - X[:-1]), J) with X [steps+1][n] and J a
         scalar per trajectory; after a fit without batch axis the one
         trajectory's, otherwise with the leading B."""
-        if self._solver is None:
-            raise RuntimeError("You need to call fit or step first")
-        r = self._solver.mpc_closed_loop(steps, rounds_per_step, **kwargs)
+        r = self._fitted_solver().mpc_closed_loop(steps, rounds_per_step,
+                                                  **kwargs)
         X, U, J = r.X, r.U, r.J
         if not self._batched:
             X, U, J = X[0], U[0], J[0]

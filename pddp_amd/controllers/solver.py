@@ -254,28 +254,75 @@ class ILQRSolver(object):
         one-launch round and the fused search take one problem for the batch.
         The current nominal `Z` is NOT rolled out again: call
         `nominal_rollout()` / `set_nominal()` after changing the table."""
+        self._need_sample_problem("set_batch_problem")
+        self.batch_table = self._write_fields(
+            "set_batch_problem", self._shared_row().repeat(self.B, 1),
+            self._row_blocks(params, x_goal, u_goal)).contiguous()
+        self._problem_changed(separate=True)
+
+    def _need_sample_problem(self, what):
         if not self._batch_problem_possible():
             raise _native.NativeError(
-                "set_batch_problem needs a sample problem under "
-                "IGNORE_UNCERTAINTY on the native path (no plugin, no "
-                "Gaussian encoding)")
-        table = self._shared_row().repeat(self.B, 1)
-        for name, block, off, width in self._row_blocks(params, x_goal,
-                                                        u_goal):
+                "%s needs a sample problem under IGNORE_UNCERTAINTY on the "
+                "native path (no plugin, no Gaussian encoding)" % what)
+
+    def _check_active(self, what, active):
+        if active is not None and not (
+                torch.is_tensor(active) and active.dtype == torch.uint8 and
+                active.device == self.device and
+                tuple(active.shape) == (self.B,)):
+            raise _native.NativeError(
+                "%s: active must be a uint8 tensor of shape (%d,) on %s" % (
+                    what, self.B, self.device))
+
+    def _out(self, masked, *shape, dtype=None, fill=float("nan")):
+        """An output the kernels write: `fill`ed ahead of the launch where a
+        mask leaves rows of it unwritten."""
+        opts = dict(dtype=dtype or self.dtype, device=self.device)
+        return torch.full(shape, fill, **opts) if masked else \
+            torch.empty(shape, **opts)
+
+    def _write_fields(self, what, rows, blocks, over_samples=False):
+        """Writes the fields the user gave - `blocks`: (name, block or None,
+        offset, width), `_row_blocks` / `_weight_blocks` - into `rows`
+        ([B][row], or [B][S][row]; `over_samples`: a [B][width] block is then
+        the same for every s) and returns `rows`; a field of another shape is
+        `what`'s NativeError."""
+        lead = tuple(rows.shape[:-1])
+        for name, block, off, width in blocks:
             if block is None:
                 continue
             block = torch.as_tensor(block)
-            if tuple(block.shape) != (self.B, width):
-                raise _native.NativeError(
-                    "set_batch_problem: %s has shape %s, expected (%d, %d)" % (
-                        name, tuple(block.shape), self.B, width))
-            table[:, off:off + width] = block.to(dtype=self.dtype,
-                                                 device=self.device)
-        self.batch_table = table.contiguous()
-        self._one_launch = self._nominal_sweep = self._fused = False
+            if over_samples and block.dim() == 2:
+                block = block.unsqueeze(1).expand(-1, lead[1], -1)
+            if tuple(block.shape) != lead + (width,):
+                want = "(%d, [%d, ]%d)" if over_samples else "(%d, %d)"
+                raise _native.NativeError("%s: %s has shape %s, expected %s" % (
+                    what, name, tuple(block.shape), want % (lead + (width,))))
+            rows[..., off:off + width] = block.to(dtype=self.dtype,
+                                                  device=self.device)
+        return rows
+
+    def _problem_changed(self, separate=False):
+        """The records in `_rec` are another problem's and a captured round is
+        dropped; `separate`: per-trajectory data was set, every round is
+        records+separate from now on."""
+        if separate:
+            self._one_launch = self._nominal_sweep = self._fused = False
         self._derivs_due = True
-        self._rec_stale = True  # (the records in `_rec`: another problem's)
+        self._rec_stale = True
         self._graph = None
+
+    def _per_trajectory(self):
+        """Is any per-trajectory data set?  (Its kernels are the only ones that
+        read it: every other sequence takes one problem for the batch.)"""
+        return self.batch_table is not None or self.reference is not None or \
+            self.batch_weights is not None
+
+    def _base_table(self):
+        """`batch_table`, or the shared problem in every row."""
+        return self.batch_table if self.batch_table is not None else \
+            self._shared_row().repeat(self.B, 1)
 
     def _shared_row(self):
         """The shared problem as one row of the table's layout
@@ -301,6 +348,31 @@ class ILQRSolver(object):
                 ("x_goal", x_goal, N_.BATCH_X_GOAL, prob.aug_size),
                 ("u_goal", u_goal, N_.BATCH_U_GOAL, self.m))
 
+    def _weight_matrices(self):
+        """(name, matrix, leading dimension, size, offset of its diagonal in a
+        row of the weights) of the shared Q, Q_term, R."""
+        N_ = _native
+        prob = self.problem
+        return (("Q", prob.Q, N_.MAX_AUG, prob.aug_size, N_.WEIGHT_Q),
+                ("Q_term", prob.Q_term, N_.MAX_AUG, prob.aug_size,
+                 N_.WEIGHT_Q_TERM),
+                ("R", prob.R, N_.MAX_ACTION, self.m, N_.WEIGHT_R))
+
+    def _shared_weights_row(self):
+        """The shared diagonals as one row of the weights' layout: double -> T
+        as convert_problem (`_shared_row`)."""
+        row = torch.zeros(_native.WEIGHT_ROW, dtype=torch.float64)
+        for _, mat, ld, k, off in self._weight_matrices():
+            row[off:off + k] = torch.tensor(
+                [mat[i * ld + i] for i in range(k)], dtype=torch.float64)
+        return row.to(self.dtype).to(self.device)
+
+    def _weight_blocks(self, q, q_term, r):
+        """(name, block, offset in a row, width) of a row's three fields."""
+        return tuple((name.lower(), block, off, k) for block, (
+            name, _, _, k, off) in zip((q, q_term, r),
+                                       self._weight_matrices()))
+
     def clear_batch_problem(self):
         """Back to one problem for the whole batch: the plan's inputs as the
         constructor leaves them (while a reference is set, once that is
@@ -314,15 +386,12 @@ class ILQRSolver(object):
         """After a table, a reference or the weights went: the plan's inputs
         as the constructor leaves them, unless another of them is still
         set."""
-        if self.batch_table is None and self.reference is None and \
-                self.batch_weights is None:
+        if not self._per_trajectory():
             self._fused = self._one_launch = None
             self._nominal_sweep = None if (
                 self._nominal_sweep_possible() and
                 self._nominal_sweep_pays()) else False
-        self._derivs_due = True
-        self._rec_stale = True
-        self._graph = None
+        self._problem_changed()
 
     @_on_device
     def set_reference(self, x_ref, u_ref=None, start=0):
@@ -344,11 +413,7 @@ class ILQRSolver(object):
         trajectory and refuse; so does `closed_loop()` unless it is told to
         follow the reference (`track=True`).  The nominal rollout reads no
         goal: the current nominal stays as it is."""
-        if not self._batch_problem_possible():
-            raise _native.NativeError(
-                "set_reference needs a sample problem under "
-                "IGNORE_UNCERTAINTY on the native path (no plugin, no "
-                "Gaussian encoding)")
+        self._need_sample_problem("set_reference")
         if self.batch_weights is not None:
             raise _native.NativeError(
                 "set_reference: per-trajectory cost weights are set "
@@ -371,20 +436,16 @@ class ILQRSolver(object):
                     "set_reference: u_ref has shape %s, expected (%d, %d, "
                     "%d)" % (tuple(u_ref.shape), B, L, m))
         start = self._ref_start_of(start)
-        base = self.batch_table if self.batch_table is not None else \
-            self._shared_row().repeat(B, 1)
         ref = torch.zeros(B, L, N_.REF_ROW, **opts)
         ref[:, :, N_.REF_U_GOAL:N_.REF_U_GOAL + N_.MAX_ACTION] = \
-            base[:, None, N_.BATCH_U_GOAL:N_.BATCH_U_GOAL + N_.MAX_ACTION]
+            self._base_table()[:, None, N_.BATCH_U_GOAL:N_.BATCH_U_GOAL +
+                               N_.MAX_ACTION]
         ref[:, :, N_.REF_X_GOAL:N_.REF_X_GOAL + na] = x_ref.to(**opts)
         if u_ref is not None:
             ref[:, :, N_.REF_U_GOAL:N_.REF_U_GOAL + m] = u_ref.to(**opts)
         self.reference = ref.contiguous()
         self.ref_start = start
-        self._one_launch = self._nominal_sweep = self._fused = False
-        self._derivs_due = True
-        self._rec_stale = True  # (the records in `_rec`: another goal's)
-        self._graph = None
+        self._problem_changed(separate=True)
 
     def _ref_start_of(self, start):
         if int(start) != start or int(start) < 0 or int(start) > 0x7fffffff:
@@ -401,9 +462,7 @@ class ILQRSolver(object):
             raise _native.NativeError(
                 "set_reference_start: no reference is set")
         self.ref_start = self._ref_start_of(start)
-        self._derivs_due = True
-        self._rec_stale = True
-        self._graph = None
+        self._problem_changed()
 
     def clear_reference(self):
         """Back to one goal per trajectory: what `clear_batch_problem()`
@@ -443,62 +502,28 @@ class ILQRSolver(object):
         under an off-diagonal entry makes the cost indefinite, and the solver
         then answers with NOT_PD / MAX_REG states that look like a tuning
         result.)"""
-        if not self._batch_problem_possible():
-            raise _native.NativeError(
-                "set_batch_weights needs a sample problem under "
-                "IGNORE_UNCERTAINTY on the native path (no plugin, no "
-                "Gaussian encoding)")
+        self._need_sample_problem("set_batch_weights")
         if self.reference is not None:
             raise _native.NativeError(
                 "set_batch_weights: a reference is set (set_reference); "
                 "weights together with a reference are not supported - "
                 "clear_reference() first")
-        N_ = _native
-        prob = self.problem
-        na, m = prob.aug_size, self.m
-        # (the shared diagonals: double -> T as convert_problem, _shared_row)
-        row = torch.zeros(N_.WEIGHT_ROW, dtype=torch.float64)
-        for off, mat, ld, k in ((N_.WEIGHT_Q, prob.Q, N_.MAX_AUG, na),
-                                (N_.WEIGHT_Q_TERM, prob.Q_term, N_.MAX_AUG,
-                                 na),
-                                (N_.WEIGHT_R, prob.R, N_.MAX_ACTION, m)):
-            row[off:off + k] = torch.tensor(
-                [mat[i * ld + i] for i in range(k)], dtype=torch.float64)
-        weights = row.to(self.dtype).to(self.device).repeat(self.B, 1)
-        for name, block, off, width in (("q", q, N_.WEIGHT_Q, na),
-                                        ("q_term", q_term, N_.WEIGHT_Q_TERM,
-                                         na),
-                                        ("r", r, N_.WEIGHT_R, m)):
-            if block is None:
-                continue
-            block = torch.as_tensor(block)
-            if tuple(block.shape) != (self.B, width):
-                raise _native.NativeError(
-                    "set_batch_weights: %s has shape %s, expected (%d, %d)" % (
-                        name, tuple(block.shape), self.B, width))
-            weights[:, off:off + width] = block.to(dtype=self.dtype,
-                                                   device=self.device)
+        weights = self._write_fields(
+            "set_batch_weights", self._shared_weights_row().repeat(self.B, 1),
+            self._weight_blocks(q, q_term, r))
         if check:
             self._check_weights(weights)
         self.batch_weights = weights.contiguous()
-        self._one_launch = self._nominal_sweep = self._fused = False
-        self._derivs_due = True
-        self._rec_stale = True  # (the records in `_rec`: another cost's)
-        self._graph = None
+        self._problem_changed(separate=True)
 
     def _check_weights(self, weights):
         """set_batch_weights(check=True): the eigenvalues of every
         trajectory's Q, Q_term (symmetrised, >= -1e-9 max |entry| or the
         shared matrix's own lowest) and R (> 0), on the host in float64."""
-        N_ = _native
-        prob = self.problem
         w = weights.to(dtype=torch.float64, device="cpu")
         found = None  # (trajectory, matrix) of the first offender
-        for name, mat, ld, k, off, positive in (
-                ("Q", prob.Q, N_.MAX_AUG, prob.aug_size, N_.WEIGHT_Q, False),
-                ("Q_term", prob.Q_term, N_.MAX_AUG, prob.aug_size,
-                 N_.WEIGHT_Q_TERM, False),
-                ("R", prob.R, N_.MAX_ACTION, self.m, N_.WEIGHT_R, True)):
+        for name, mat, ld, k, off in self._weight_matrices():
+            positive = name == "R"
             M = torch.tensor(list(mat), dtype=torch.float64).reshape(
                 ld, ld)[:k, :k]
             M = 0.5 * (M + M.T)
@@ -542,7 +567,8 @@ class ILQRSolver(object):
                 "accept" % what)
 
     def _one_problem(self, what):
-        self._one_goal(what)
+        if self.reference is not None:  # (no call on the one-launch path)
+            self._one_goal(what)
         if self.batch_weights is not None:
             raise _native.NativeError(
                 "%s evaluates ONE cost for the whole batch; with "
@@ -554,31 +580,32 @@ class ILQRSolver(object):
                 "set_batch_problem() a round is derivs, backward, line_search, "
                 "accept" % what)
 
-    def _problem_call(self, name, *args):
-        """A problem kernel's entry point: the `_batch` one, with the table
-        (its address looked up at the call: the tensor may be replaced between
-        two calls), while a table is set."""
-        if self.batch_table is None:
-            return _native.call(name, self.dtype, self._pp, *args)
-        return _native.call(name + "_batch", self.dtype, self._pp,
-                            _native.ptr(self.batch_table), *args)
+    def _problem_call(self, name, *args, goals=False):
+        """A problem kernel's entry point, by the per-trajectory data set: the
+        `_batch` one, with the table, while a table is set; for a kernel that
+        reads the `goals` (records, line search) the `_weighted` one, with the
+        table's address or NULL and the weights, while weights are set, and
+        the `_track` one, likewise with `_ref_window()`, while a reference is
+        (the two exclude each other).  The addresses are looked up at the
+        call: a tensor may be replaced between two calls."""
+        p = _native.ptr
+        if goals and self.batch_weights is not None:
+            suffix, lead = "_weighted", (p(self.batch_table),
+                                         p(self.batch_weights))
+        elif goals and self.reference is not None:
+            suffix, lead = "_track", (p(self.batch_table),) + \
+                self._ref_window()
+        elif self.batch_table is not None:
+            suffix, lead = "_batch", (p(self.batch_table),)
+        else:
+            suffix, lead = "", ()
+        return _native.call(name + suffix, self.dtype, self._pp, *lead, *args)
 
-    def _goal_call(self, name, *args):
-        """A problem kernel that reads the goals (records, line search): the
-        `_track` entry point, with the table's address or NULL, while a
-        reference is set; the `_weighted` one, likewise, while weights are
-        (the two exclude each other; the addresses are looked up at the
-        call)."""
-        if self.batch_weights is not None:
-            return _native.call(name + "_weighted", self.dtype, self._pp,
-                                _native.ptr(self.batch_table),
-                                _native.ptr(self.batch_weights), *args)
-        if self.reference is None:
-            return self._problem_call(name, *args)
-        return _native.call(name + "_track", self.dtype, self._pp,
-                            _native.ptr(self.batch_table),
-                            _native.ptr(self.reference),
-                            self.reference.shape[1], self.ref_start, *args)
+    def _ref_window(self):
+        """(address, rows, first row) of the reference, as every pddp_*_track_*
+        entry point takes them after the table."""
+        return (_native.ptr(self.reference), self.reference.shape[1],
+                self.ref_start)
 
     @property
     def rec(self):
@@ -596,10 +623,10 @@ class ILQRSolver(object):
 
     def _derivs(self, mask, J, state):
         p = _native.ptr
-        self._goal_call("pddp_derivs", self.B, self.N,
-                        p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
-                        p(mask), p(self._rec), p(self.L), p(J), p(state),
-                        self._s())
+        self._problem_call("pddp_derivs", self.B, self.N,
+                           p(self.Z), p(self.U), p(self.u_min), p(self.u_max),
+                           p(mask), p(self._rec), p(self.L), p(J), p(state),
+                           self._s(), goals=True)
 
     # -- views in the reference's tensor layout -----------------------------
     def record_views(self):
@@ -733,8 +760,7 @@ class ILQRSolver(object):
     # -- the round's launch plan ----------------------------------------------
     def _plan(self, variant, search_events=None):
         """The sequence a round tries first (module docstring)."""
-        if self.batch_table is not None or self.reference is not None or \
-                self.batch_weights is not None:
+        if self._per_trajectory():
             # (the other sequences' kernels take one problem for the batch)
             return RECORDS_SEPARATE
         if variant == 0 and self._nominal_sweep is not False and \
@@ -745,8 +771,7 @@ class ILQRSolver(object):
 
     def _fused_allowed(self):
         return self.plugin is None and self._fused is not False and \
-            self.batch_table is None and self.reference is None and \
-            self.batch_weights is None
+            not self._per_trajectory()
 
     def _one_launch_applied(self):
         return self._one_launch is True
@@ -865,11 +890,11 @@ class ILQRSolver(object):
         if self.plugin is not None:
             return self.plugin.line_search(self, active, use_status)
         b = self._buffers()
-        self._goal_call(
+        self._problem_call(
             "pddp_line_search", self.B, self.N,
             self.A, b.Z, b.U, b.gains, b.alphas, b.u_min, b.u_max,
             _native.ptr(active), b.bwd_status if use_status else None,
-            b.Zc, b.Uc, b.Jc, self._s())
+            b.Zc, b.Uc, b.Jc, self._s(), goals=True)
 
     @_on_device
     def accept(self, tol, max_reg, n_iterations):
@@ -976,10 +1001,7 @@ class ILQRSolver(object):
                 "closed_loop takes ONE goal per trajectory; with a reference "
                 "(set_reference) pass track=True to cost the rollouts along "
                 "it")
-        if not self._batch_problem_possible():
-            raise _native.NativeError(
-                "closed_loop needs a sample problem under IGNORE_UNCERTAINTY "
-                "on the native path (no plugin, no Gaussian encoding)")
+        self._need_sample_problem("closed_loop")
         B, N, n, m = self.B, self.N, self.n, self.m
         opts = dict(dtype=self.dtype, device=self.device)
         if z0 is not None:
@@ -995,41 +1017,19 @@ class ILQRSolver(object):
                 "closed_loop: %d samples, z0 of shape %s" % (
                     S, None if z0 is None else tuple(z0.shape)))
         plant = None
-        if self.batch_table is not None or not (
-                params is None and x_goal is None and u_goal is None):
-            base = self.batch_table if self.batch_table is not None else \
-                self._shared_row().repeat(B, 1)
-            plant = base.unsqueeze(1).repeat(1, S, 1)
-            for name, block, off, width in self._row_blocks(params, x_goal,
-                                                            u_goal):
-                if block is None:
-                    continue
-                block = torch.as_tensor(block).to(**opts)
-                if block.dim() == 2:
-                    block = block.unsqueeze(1).expand(-1, S, -1)
-                if tuple(block.shape) != (B, S, width):
-                    raise _native.NativeError(
-                        "closed_loop: %s has shape %s, expected (%d, [%d, ]"
-                        "%d)" % (name, tuple(torch.as_tensor(block).shape), B,
-                                 S, width))
-                plant[:, :, off:off + width] = block
-        if active is not None and not (
-                torch.is_tensor(active) and active.dtype == torch.uint8 and
-                active.device == self.device and
-                tuple(active.shape) == (B,)):
-            raise _native.NativeError(
-                "closed_loop: active must be a uint8 tensor of shape (%d,) on "
-                "%s" % (B, self.device))
+        if not (self.batch_table is None and params is None and
+                x_goal is None and u_goal is None):
+            plant = self._write_fields(
+                "closed_loop", self._base_table().unsqueeze(1).repeat(1, S, 1),
+                self._row_blocks(params, x_goal, u_goal), over_samples=True)
+        self._check_active("closed_loop", active)
         gains = None if not feedback else \
             (self.gains_acc if accepted else self.gains)
-        fill = float("nan")
+        masked = active is not None
         out = types.SimpleNamespace(
-            J=torch.full((B, S), fill, **opts) if active is not None
-            else torch.empty(B, S, **opts),
-            stats=torch.full((B, 4), fill, **opts) if active is not None
-            else torch.empty(B, 4, **opts),
-            X=torch.empty(B, N + 1, S, n, **opts) if keep else None,
-            U=torch.empty(B, N, S, m, **opts) if keep else None)
+            J=self._out(masked, B, S), stats=self._out(masked, B, 4),
+            X=self._out(False, B, N + 1, S, n) if keep else None,
+            U=self._out(False, B, N, S, m) if keep else None)
         p = _native.ptr
         head = (self._pp, B, N, S, p(self.Z), p(self.U), p(gains),
                 p(None if z0 is None else z0.contiguous()), p(plant),
@@ -1040,11 +1040,9 @@ class ILQRSolver(object):
         v_std = self._noise_std("obs_std", obs_std)
         noise = (p(w_std), p(v_std), int(seed), int(sample_offset))
         if track:  # (with or without noise: one entry point)
-            ref = (p(self.reference), self.reference.shape[1],
-                   self.ref_start)
             self._launch(events, _native.call, "pddp_closed_loop_track",
-                         self.dtype, *(head[:1] + ref + head[1:] + noise +
-                                       tail))
+                         self.dtype, *(head[:1] + self._ref_window() +
+                                       head[1:] + noise + tail))
         elif process_std is None and obs_std is None:
             self._launch(events, _native.call, "pddp_closed_loop", self.dtype,
                          *(head + tail))
@@ -1097,21 +1095,8 @@ class ILQRSolver(object):
         problem's; None when that leaves the controller's own model."""
         if params is None and x_goal is None and u_goal is None:
             return None
-        B = self.B
-        plant = (self.batch_table.clone() if self.batch_table is not None
-                 else self._shared_row().repeat(B, 1))
-        for name, block, off, width in self._row_blocks(params, x_goal,
-                                                        u_goal):
-            if block is None:
-                continue
-            block = torch.as_tensor(block)
-            if tuple(block.shape) != (B, width):
-                raise _native.NativeError(
-                    "%s: %s has shape %s, expected (%d, %d)" % (
-                        what, name, tuple(block.shape), B, width))
-            plant[:, off:off + width] = block.to(dtype=self.dtype,
-                                                 device=self.device)
-        return plant.contiguous()
+        return self._write_fields(what, self._base_table().clone(),
+                                  self._row_blocks(params, x_goal, u_goal))
 
     @_on_device
     def mpc_closed_loop(self, steps, rounds_per_step, z0=None, params=None,
@@ -1169,11 +1154,7 @@ class ILQRSolver(object):
         the trial reports (`J`) is under the shared problem's Q, Q_term, R
         and the plant row's goals - the common yardstick.  The advance kernel
         is unchanged."""
-        if not self._batch_problem_possible():
-            raise _native.NativeError(
-                "mpc_closed_loop needs a sample problem under "
-                "IGNORE_UNCERTAINTY on the native path (no plugin, no Gaussian "
-                "encoding)")
+        self._need_sample_problem("mpc_closed_loop")
         B, N, n, m = self.B, self.N, self.n, self.m
         T, R = int(steps), int(rounds_per_step)
         if T < 1 or R < 1:
@@ -1192,29 +1173,14 @@ class ILQRSolver(object):
                 raise _native.NativeError(
                     "mpc_closed_loop: disturbance has shape %s, expected "
                     "(%d, %d, %d)" % (tuple(disturbance.shape), B, T, n))
-        if active is not None and not (
-                torch.is_tensor(active) and active.dtype == torch.uint8 and
-                active.device == self.device and
-                tuple(active.shape) == (B,)):
-            raise _native.NativeError(
-                "mpc_closed_loop: active must be a uint8 tensor of shape "
-                "(%d,) on %s" % (B, self.device))
+        self._check_active("mpc_closed_loop", active)
         plant = self._plant_table("mpc_closed_loop", params, x_goal, u_goal)
         masked = active is not None
-        fill = float("nan")
-        i32 = dict(dtype=torch.int32, device=self.device)
-        u8 = dict(dtype=torch.uint8, device=self.device)
         out = types.SimpleNamespace(
-            X=torch.full((B, T + 1, n), fill, **opts) if masked
-            else torch.empty(B, T + 1, n, **opts),
-            U=torch.full((B, T, m), fill, **opts) if masked
-            else torch.empty(B, T, m, **opts),
-            J=torch.full((B,), fill, **opts) if masked
-            else torch.empty(B, **opts),
-            states=torch.zeros(B, T, **i32) if masked
-            else torch.empty(B, T, **i32),
-            unfinished=torch.zeros(B, T, **u8) if masked
-            else torch.empty(B, T, **u8))
+            X=self._out(masked, B, T + 1, n), U=self._out(masked, B, T, m),
+            J=self._out(masked, B),
+            states=self._out(masked, B, T, dtype=torch.int32, fill=0),
+            unfinished=self._out(masked, B, T, dtype=torch.uint8, fill=0))
         record = _native.lib().pddp_event_record
         if events is not None:
             _native.check(record(events[0], self._s()), "pddp_event_record")
@@ -1234,8 +1200,7 @@ class ILQRSolver(object):
                           name + "_" + _native.suffix(self.dtype))
         for t in range(T):
             self.rounds(R, tol, max_reg, n_iterations=1)
-            ref = () if not tracking else (
-                p(self.reference), self.reference.shape[1], self.ref_start)
+            ref = self._ref_window() if tracking else ()
             _native.check(
                 advance(self._pp, p(self.batch_table), *ref, B, N, T, t,
                         *tail, self._s()), name)
@@ -1330,8 +1295,7 @@ class ILQRSolver(object):
                self.kernel_variant)
         if self._graph is not None and self._graph[0] == key:
             return self._graph[1]
-        if self.batch_table is not None or self.reference is not None or \
-                self.batch_weights is not None:
+        if self._per_trajectory():
             self.sync_records()  # (a launch that belongs to no round)
         torch.cuda.synchronize(self.device)
         if self.plugin is None:

@@ -67,6 +67,34 @@ struct LineSearchArgs {
   int drop_candidates = 0;
 };
 
+// Host side of every entry point that takes one of the blocks above
+// (problem_kernels.hip, tracking.hip, weights.hip): the argument test, the grid
+// of the per-candidate line search, and the carrier of a block together with
+// a form's per-trajectory data through PDDP_DISPATCH_MODEL.
+template <typename T>
+inline bool args_ok(const DerivArgs<T>& a) {
+  return !(a.B <= 0 || a.N <= 0 || !a.Z || !a.U || !a.rec || !a.L || !a.J);
+}
+// `int_lanes`: the kernel indexes its B * A lanes with an int (the forms with
+// per-trajectory data; the uniform entry points never checked)
+template <typename T>
+inline bool args_ok(const LineSearchArgs<T>& a, bool int_lanes) {
+  if (a.B <= 0 || a.N <= 0 || a.A <= 0 || !a.Z || !a.U || !a.gains ||
+      !a.alphas || !a.Zc || !a.Uc || !a.Jc)
+    return false;
+  return !(int_lanes && (long long)a.B * a.A > 0x7fffffffLL);
+}
+// one lane per (trajectory, step size) candidate
+template <typename T>
+inline dim3 search_lanes(const LineSearchArgs<T>& a) {
+  return dim3((unsigned)(((long long)a.B * a.A + kWave - 1) / kWave));
+}
+template <typename Args, typename Extra>
+struct With {
+  Args a;
+  Extra x;
+};
+
 // The domain of the IGNORE_UNCERTAINTY problem kernels (problem_kernels.hip,
 // both forms) and their dispatch on the model.
 inline int check_problem(const pddp_problem* p) {

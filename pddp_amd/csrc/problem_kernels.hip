@@ -156,33 +156,29 @@ static bool stage_cost_on(const pddp_problem& p) {
   if (QM == kFullMask<MODEL>) return false;
   return (live_mask(p.Q, ModelDims<MODEL>::na) & ~QM) == 0;
 }
-// an argument block and the per-trajectory table of the batch entry points,
-// nullptr from the uniform ones
-template <typename Args, typename T>
-struct WithTable {
-  Args a;
-  const T* table;
-};
+// (With<Args, const T*>, problem_args.hpp: an argument block and the
+// per-trajectory table of the batch entry points, nullptr from the uniform
+// ones)
 template <typename T, int MODEL>
 static int launch_rollout(const pddp_problem& p,
-                          WithTable<RolloutArgs<T>, T> w, hipStream_t st) {
+                          With<RolloutArgs<T>, const T*> w, hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
   const dim3 blocks((w.a.B + kWave - 1) / kWave);
-  if (w.table != nullptr)
+  if (w.x != nullptr)
     PDDP_LAUNCH((batch_rollout_kernel<T, MODEL>), blocks, dim3(kWave), 0, st,
-                P, w.a, w.table);
+                P, w.a, w.x);
   else
     PDDP_LAUNCH((nominal_rollout_kernel<T, MODEL>), blocks, dim3(kWave), 0, st,
                 P, w.a);
   return launch_status();
 }
 template <typename T, int MODEL>
-static int launch_derivs(const pddp_problem& p, WithTable<DerivArgs<T>, T> w,
-                         hipStream_t st) {
+static int launch_derivs(const pddp_problem& p,
+                         With<DerivArgs<T>, const T*> w, hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  if (w.table != nullptr)
+  if (w.x != nullptr)
     PDDP_LAUNCH((batch_derivs_kernel<T, MODEL>), dim3(w.a.B),
-                dim3(kDerivThreads), 0, st, P, w.a, w.table);
+                dim3(kDerivThreads), 0, st, P, w.a, w.x);
   else
     PDDP_LAUNCH((derivs_kernel<T, MODEL>), dim3(w.a.B), dim3(kDerivThreads), 0,
                 st, P, w.a);
@@ -190,14 +186,14 @@ static int launch_derivs(const pddp_problem& p, WithTable<DerivArgs<T>, T> w,
 }
 template <typename T, int MODEL>
 static int launch_line_search(const pddp_problem& p,
-                              WithTable<LineSearchArgs<T>, T> w,
+                              With<LineSearchArgs<T>, const T*> w,
                               hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
   const LineSearchArgs<T>& a = w.a;
-  const dim3 lanes((unsigned)(((long long)a.B * a.A + kWave - 1) / kWave));
-  if (w.table != nullptr) {  // (the LDS kernels take one problem)
+  const dim3 lanes = search_lanes(a);
+  if (w.x != nullptr) {  // (the LDS kernels take one problem)
     PDDP_LAUNCH((batch_line_search_kernel<T, MODEL>), lanes, dim3(kWave), 0,
-                st, P, a, w.table);
+                st, P, a, w.x);
     return launch_status();
   }
   using D = ModelDims<MODEL>;
@@ -324,7 +320,8 @@ static int nominal_rollout_impl(const pddp_problem* p, bool batch,
                                 const uint8_t* mask, T* Z, void* stream) {
   if (B <= 0 || N <= 0 || (batch && !table) || !z0 || !U || !Z)
     return PDDP_E_BADARG;
-  WithTable<RolloutArgs<T>, T> w{{B, N, z0, U, u_min, u_max, mask, Z}, table};
+  With<RolloutArgs<T>, const T*> w{{B, N, z0, U, u_min, u_max, mask, Z},
+                                   table};
   if (!batch && is_default_encoding(p))
     return default_rollout<T>(*p, w.a, (hipStream_t)stream);
   if (int rc = check_problem(p)) return rc;
@@ -336,10 +333,9 @@ static int derivs_impl(const pddp_problem* p, bool batch, const T* table,
                        int B, int N, const T* Z, const T* U, const T* u_min,
                        const T* u_max, const uint8_t* mask, T* rec, T* L, T* J,
                        int32_t* state, void* stream) {
-  if (B <= 0 || N <= 0 || (batch && !table) || !Z || !U || !rec || !L || !J)
-    return PDDP_E_BADARG;
-  WithTable<DerivArgs<T>, T> w{
+  With<DerivArgs<T>, const T*> w{
       {B, N, Z, U, u_min, u_max, mask, rec, L, J, state}, table};
+  if (!args_ok(w.a) || (batch && !table)) return PDDP_E_BADARG;
   if (!batch && is_default_encoding(p))
     return default_derivs<T>(*p, w.a, (hipStream_t)stream);
   if (int rc = check_problem(p)) return rc;
@@ -353,14 +349,10 @@ static int line_search_impl(const pddp_problem* p, bool batch, const T* table,
                             const T* u_max, const uint8_t* active,
                             const int32_t* bwd_status, T* Zc, T* Uc, T* Jc,
                             void* stream) {
-  if (B <= 0 || N <= 0 || A <= 0 || (batch && !table) || !Z || !U || !gains ||
-      !alphas || !Zc || !Uc || !Jc)
-    return PDDP_E_BADARG;
-  // (the batch kernel's int lane index; the uniform entry points never checked)
-  if (batch && (long long)B * A > 0x7fffffffLL) return PDDP_E_BADARG;
-  WithTable<LineSearchArgs<T>, T> w{{B, N, A, Z, U, gains, alphas, u_min,
-                                     u_max, active, bwd_status, Zc, Uc, Jc},
-                                    table};
+  With<LineSearchArgs<T>, const T*> w{{B, N, A, Z, U, gains, alphas, u_min,
+                                       u_max, active, bwd_status, Zc, Uc, Jc},
+                                      table};
+  if (!args_ok(w.a, batch) || (batch && !table)) return PDDP_E_BADARG;
   if (!batch && is_default_encoding(p))
     return default_line_search<T>(*p, w.a, (hipStream_t)stream);
   if (int rc = check_problem(p)) return rc;

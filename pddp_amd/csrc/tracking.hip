@@ -157,38 +157,34 @@ __global__ __launch_bounds__(kWave) void track_mpc_advance_kernel(
 // launchers and entry points
 // --------------------------------------------------------------------------
 
-template <typename Args, typename T>
-struct WithRef {
-  Args a;
-  RefArgs<T> r;
-};
-
+// (With<Args, RefArgs<T>>, problem_args.hpp: an argument block and the
+// reference of its launch)
 template <typename T, int MODEL>
 static int launch_track_derivs(const pddp_problem& p,
-                               WithRef<DerivArgs<T>, T> w, hipStream_t st) {
+                               With<DerivArgs<T>, RefArgs<T>> w,
+                               hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
   PDDP_LAUNCH((track_derivs_kernel<T, MODEL>), dim3(w.a.B),
-              dim3(kDerivThreads), 0, st, P, w.a, w.r);
+              dim3(kDerivThreads), 0, st, P, w.a, w.x);
   return launch_status();
 }
 template <typename T, int MODEL>
 static int launch_track_line_search(const pddp_problem& p,
-                                    WithRef<LineSearchArgs<T>, T> w,
+                                    With<LineSearchArgs<T>, RefArgs<T>> w,
                                     hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  const dim3 lanes((unsigned)(((long long)w.a.B * w.a.A + kWave - 1) / kWave));
-  PDDP_LAUNCH((track_line_search_kernel<T, MODEL>), lanes, dim3(kWave), 0, st,
-              P, w.a, w.r);
+  PDDP_LAUNCH((track_line_search_kernel<T, MODEL>), search_lanes(w.a),
+              dim3(kWave), 0, st, P, w.a, w.x);
   return launch_status();
 }
 template <typename T, int MODEL>
 static int launch_track_advance(const pddp_problem& p,
-                                WithRef<TrackAdvanceArgs<T>, T> w,
+                                With<TrackAdvanceArgs<T>, RefArgs<T>> w,
                                 hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
   const dim3 blocks((w.a.B + kWave - 1) / kWave);
   PDDP_LAUNCH((track_mpc_advance_kernel<T, MODEL>), blocks, dim3(kWave), 0, st,
-              P, w.a, w.r);
+              P, w.a, w.x);
   return launch_status();
 }
 
@@ -198,10 +194,9 @@ static int track_derivs_impl(const pddp_problem* p, const T* table,
                              int N, const T* Z, const T* U, const T* u_min,
                              const T* u_max, const uint8_t* mask, T* rec, T* L,
                              T* J, int32_t* state, void* stream) {
-  WithRef<DerivArgs<T>, T> w{
+  With<DerivArgs<T>, RefArgs<T>> w{
       {B, N, Z, U, u_min, u_max, mask, rec, L, J, state}, {}};
-  if (B <= 0 || N <= 0 || !Z || !U || !rec || !L || !J ||
-      !ref_args(table, ref, ref_len, ref_t0, &w.r))
+  if (!args_ok(w.a) || !ref_args(table, ref, ref_len, ref_t0, &w.x))
     return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
   PDDP_DISPATCH_MODEL(launch_track_derivs, T, p, w, (hipStream_t)stream)
@@ -216,14 +211,12 @@ static int track_line_search_impl(const pddp_problem* p, const T* table,
                                   const uint8_t* active,
                                   const int32_t* bwd_status, T* Zc, T* Uc,
                                   T* Jc, void* stream) {
-  WithRef<LineSearchArgs<T>, T> w{{B, N, A, Z, U, gains, alphas, u_min, u_max,
-                                   active, bwd_status, Zc, Uc, Jc},
-                                  {}};
-  if (B <= 0 || N <= 0 || A <= 0 || !Z || !U || !gains || !alphas || !Zc ||
-      !Uc || !Jc || !ref_args(table, ref, ref_len, ref_t0, &w.r))
+  With<LineSearchArgs<T>, RefArgs<T>> w{
+      {B, N, A, Z, U, gains, alphas, u_min, u_max, active, bwd_status, Zc, Uc,
+       Jc},
+      {}};
+  if (!args_ok(w.a, true) || !ref_args(table, ref, ref_len, ref_t0, &w.x))
     return PDDP_E_BADARG;
-  // (the kernel's int lane index)
-  if ((long long)B * A > 0x7fffffffLL) return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
   PDDP_DISPATCH_MODEL(launch_track_line_search, T, p, w, (hipStream_t)stream)
 }
@@ -238,7 +231,7 @@ static int track_advance_impl(const pddp_problem* p, const T* table,
                               uint8_t* live_log, double* mu, double* delta,
                               int32_t* state, int32_t* iter, uint8_t* active,
                               uint8_t* fresh, int32_t* n_live, void* stream) {
-  WithRef<TrackAdvanceArgs<T>, T> w{
+  With<TrackAdvanceArgs<T>, RefArgs<T>> w{
       {B,     N,      TT,        t,        plant, z0,    U,
        Z,     u_min,  u_max,     disturbance,     mask,  Xlog,
        Ulog,  Jcl,    state_log, live_log, mu,    delta, state,
@@ -247,7 +240,7 @@ static int track_advance_impl(const pddp_problem* p, const T* table,
   if (B <= 0 || N <= 0 || TT <= 0 || t < 0 || t >= TT || !z0 || !U || !Z ||
       !Xlog || !Ulog || !Jcl || !state_log || !live_log || !mu || !delta ||
       !state || !iter || !active || !fresh ||
-      !ref_args(table, ref, ref_len, ref_t0, &w.r))
+      !ref_args(table, ref, ref_len, ref_t0, &w.x))
     return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
   PDDP_DISPATCH_MODEL(launch_track_advance, T, p, w, (hipStream_t)stream)

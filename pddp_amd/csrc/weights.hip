@@ -83,29 +83,24 @@ __global__ __launch_bounds__(kWave) void weighted_line_search_kernel(
 // launchers and entry points
 // --------------------------------------------------------------------------
 
-template <typename Args, typename T>
-struct WithWeights {
-  Args a;
-  WeightArgs<T> w;
-};
-
+// (With<Args, WeightArgs<T>>, problem_args.hpp: an argument block and the two
+// tables of its launch)
 template <typename T, int MODEL>
 static int launch_weighted_derivs(const pddp_problem& p,
-                                  WithWeights<DerivArgs<T>, T> x,
+                                  With<DerivArgs<T>, WeightArgs<T>> w,
                                   hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  PDDP_LAUNCH((weighted_derivs_kernel<T, MODEL>), dim3(x.a.B),
-              dim3(kDerivThreads), 0, st, P, x.a, x.w);
+  PDDP_LAUNCH((weighted_derivs_kernel<T, MODEL>), dim3(w.a.B),
+              dim3(kDerivThreads), 0, st, P, w.a, w.x);
   return launch_status();
 }
 template <typename T, int MODEL>
 static int launch_weighted_line_search(const pddp_problem& p,
-                                       WithWeights<LineSearchArgs<T>, T> x,
+                                       With<LineSearchArgs<T>, WeightArgs<T>> w,
                                        hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  const dim3 lanes((unsigned)(((long long)x.a.B * x.a.A + kWave - 1) / kWave));
-  PDDP_LAUNCH((weighted_line_search_kernel<T, MODEL>), lanes, dim3(kWave), 0,
-              st, P, x.a, x.w);
+  PDDP_LAUNCH((weighted_line_search_kernel<T, MODEL>), search_lanes(w.a),
+              dim3(kWave), 0, st, P, w.a, w.x);
   return launch_status();
 }
 
@@ -115,12 +110,11 @@ static int weighted_derivs_impl(const pddp_problem* p, const T* table,
                                 const T* U, const T* u_min, const T* u_max,
                                 const uint8_t* mask, T* rec, T* L, T* J,
                                 int32_t* state, void* stream) {
-  if (B <= 0 || N <= 0 || !weights || !Z || !U || !rec || !L || !J)
-    return PDDP_E_BADARG;
-  WithWeights<DerivArgs<T>, T> x{
+  With<DerivArgs<T>, WeightArgs<T>> w{
       {B, N, Z, U, u_min, u_max, mask, rec, L, J, state}, {table, weights}};
+  if (!args_ok(w.a) || !weights) return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
-  PDDP_DISPATCH_MODEL(launch_weighted_derivs, T, p, x, (hipStream_t)stream)
+  PDDP_DISPATCH_MODEL(launch_weighted_derivs, T, p, w, (hipStream_t)stream)
 }
 
 template <typename T>
@@ -131,16 +125,13 @@ static int weighted_line_search_impl(const pddp_problem* p, const T* table,
                                      const T* u_max, const uint8_t* active,
                                      const int32_t* bwd_status, T* Zc, T* Uc,
                                      T* Jc, void* stream) {
-  if (B <= 0 || N <= 0 || A <= 0 || !weights || !Z || !U || !gains ||
-      !alphas || !Zc || !Uc || !Jc)
-    return PDDP_E_BADARG;
-  // (the kernel's int lane index)
-  if ((long long)B * A > 0x7fffffffLL) return PDDP_E_BADARG;
-  WithWeights<LineSearchArgs<T>, T> x{{B, N, A, Z, U, gains, alphas, u_min,
-                                       u_max, active, bwd_status, Zc, Uc, Jc},
-                                      {table, weights}};
+  With<LineSearchArgs<T>, WeightArgs<T>> w{
+      {B, N, A, Z, U, gains, alphas, u_min, u_max, active, bwd_status, Zc, Uc,
+       Jc},
+      {table, weights}};
+  if (!args_ok(w.a, true) || !weights) return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
-  PDDP_DISPATCH_MODEL(launch_weighted_line_search, T, p, x,
+  PDDP_DISPATCH_MODEL(launch_weighted_line_search, T, p, w,
                       (hipStream_t)stream)
 }
 

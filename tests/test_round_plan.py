@@ -2,8 +2,8 @@
 
 `ILQRSolver._plan()` picks one of five sequences (the table in
 pddp_amd/controllers/solver.py).  A recorder around the C ABI
-(`_native.call`, `_native.call_rc` and the three entry points the solver
-reaches through `_native.lib()` itself) logs, for every call a case makes
+(`_native.call`, `_native.call_rc` and the entry points the solver reaches
+through `_native.lib()` itself, DIRECT) logs, for every call a case makes
 after `set_nominal`, the entry point with its dtype suffix and the positions
 of its NULL arguments; the real call goes through.  Runs of one entry are
 written "count*entry".
@@ -14,7 +14,12 @@ training sets beyond one LDS"), the last one whose `round()` decided its
 launches condition by condition: a change of solver.py that makes other calls,
 in another order, or leaves other flags fails here.  (alphas17: pddp_accept
 takes 16 step sizes at most, so on that commit the nominal+separate fall-back
-ends in a NativeError after its launches; the record holds that too.)"""
+ends in a NativeError after its launches; the record holds that too.)  The
+cases with a table, a reference or weights and those of `closed_loop`,
+`closed_loop_draws` and `mpc_closed_loop` (EXPECTED's second block, with
+`ref_start` among the flags) were recorded on commit f5d44c3 ("Batched solver:
+per-trajectory diagonals of Q, Q_term and R"), the last one whose setters and
+trials each carried their own copy of the host-side plumbing."""
 import ctypes
 
 import numpy as np
@@ -27,10 +32,13 @@ from test_gpu_parity import BOUND, DT, MEAN0
 pytestmark = pytest.mark.gpu
 
 B, N = 32, 20
+S, L_REF = 3, 8  # rollouts per trajectory, rows of a reference (< N: held)
 DIRECT = ("pddp_round_nominal_f32", "pddp_attach_events",
-          "pddp_search_candidates")
+          "pddp_search_candidates", "pddp_event_record",
+          "pddp_mpc_advance_f32", "pddp_mpc_advance_f64",
+          "pddp_mpc_advance_track_f32", "pddp_mpc_advance_track_f64")
 FLAGS = ("_one_launch", "_nominal_sweep", "_fused", "_derivs_due",
-         "_rec_stale", "candidates_kept", "last_search_timed")
+         "_rec_stale", "candidates_kept", "last_search_timed", "ref_start")
 
 
 class Recorder(object):
@@ -152,6 +160,87 @@ def _force(flag):
     return run
 
 
+def _params(s, *lead):
+    """[*lead][P] model parameters: the shared ones, each scaled by up to 5 %."""
+    P = s._PARAM_COUNT[s.problem.model]
+    g = torch.Generator().manual_seed(5)
+    base = torch.tensor(list(s.problem.params)[:P], dtype=torch.float64)
+    scale = 1 + 0.05 * torch.rand(*lead, P, generator=g, dtype=torch.float64)
+    return (base * scale).to(s.dtype)
+
+
+def _x_ref(s):
+    """[B][L_REF][na] goals: the shared goal, moved a little in every row."""
+    na = s.problem.aug_size
+    g = torch.Generator().manual_seed(6)
+    goal = torch.tensor(list(s.problem.x_goal)[:na], dtype=torch.float64)
+    return (goal + 0.05 * torch.randn(B, L_REF, na, generator=g,
+                                      dtype=torch.float64)).to(s.dtype)
+
+
+def _q(s):
+    """[B][na] diagonals of Q: the shared one, each entry raised by up to 10 %
+    (the matrix stays positive semi-definite)."""
+    na = s.problem.aug_size
+    g = torch.Generator().manual_seed(7)
+    diag = torch.tensor([s.problem.Q[i * _native.MAX_AUG + i]
+                         for i in range(na)], dtype=torch.float64)
+    return (diag * (1 + 0.1 * torch.rand(B, na, generator=g,
+                                         dtype=torch.float64))).to(s.dtype)
+
+
+def _table(s):
+    s.set_batch_problem(params=_params(s, B))
+
+
+def _reference(s, start=0):
+    s.set_reference(_x_ref(s), start=start)
+
+
+def _weights(s):
+    s.set_batch_weights(q=_q(s))
+
+
+def _after(*setters, then=_three_rounds):
+    def run(s):
+        for setter in setters:
+            setter(s)
+        then(s)
+    return run
+
+
+def _reference_moved(s):
+    _reference(s)
+    _three_rounds(s)
+    s.set_reference_start(3)
+    s.round()
+
+
+def _weights_cleared(s):
+    _weights(s)
+    s.round()
+    s.clear_batch_weights()
+    _three_rounds(s)
+
+
+def _cleared_in_turn(s):
+    from pddp_amd.controllers.solver import RECORDS_SEPARATE
+    _table(s)
+    _reference(s)
+    s.clear_reference()
+    assert s._plan(s.kernel_variant) == RECORDS_SEPARATE
+    s.round()
+    s.clear_batch_problem()
+    assert s._plan(s.kernel_variant) != RECORDS_SEPARATE
+    s.round()
+
+
+def _mpc_track(s):
+    _reference(s, start=1)
+    s.mpc_closed_loop(steps=2, rounds_per_step=2)
+    assert s.ref_start == 1 + 2
+
+
 # case -> (arguments of _solver, or None for the GP plugin; what it runs)
 CASES = {}
 for _bounded in (True, False):
@@ -181,6 +270,36 @@ CASES.update({
     "capture_replay": (dict(), _capture_and_replay),
     "gp-round": (None, _three_rounds),
     "gp-capture_replay": (None, _capture_and_replay),
+})
+# per-trajectory data and the trials on a plant (EXPECTED's second block)
+CASES.update({
+    "table": (dict(), _after(_table)),
+    "table-f64": (dict(dtype=torch.float64), _after(_table)),
+    "reference": (dict(), _reference_moved),
+    "table+reference": (dict(), _after(_table, _reference)),
+    "weights": (dict(), _after(_weights)),
+    "table+weights": (dict(), _after(_table, _weights)),
+    "weights-cleared": (dict(), _weights_cleared),
+    "table+reference-cleared-in-turn": (dict(), _cleared_in_turn),
+    "table-capture_replay": (dict(), _after(_table,
+                                            then=_capture_and_replay)),
+    "closed_loop": (dict(), lambda s: s.closed_loop(samples=S)),
+    "closed_loop-plant": (dict(), lambda s: s.closed_loop(
+        samples=S, params=_params(s, B, S))),
+    "closed_loop-noisy": (dict(), lambda s: s.closed_loop(
+        samples=S, process_std=0.01, obs_std=None)),
+    "closed_loop-track": (dict(), _after(_reference, then=lambda s: (
+        s.closed_loop(samples=S, track=True, process_std=None,
+                      obs_std=None)))),
+    "closed_loop-track-noisy": (dict(), _after(_reference, then=lambda s: (
+        s.closed_loop(samples=S, track=True, process_std=0.01,
+                      obs_std=0.02)))),
+    "closed_loop_draws": (dict(), lambda s: s.closed_loop_draws(S)),
+    "mpc": (dict(), lambda s: s.mpc_closed_loop(
+        steps=2, rounds_per_step=2, events=_pair())),
+    "mpc-plant": (dict(), lambda s: s.mpc_closed_loop(
+        steps=2, rounds_per_step=2, params=_params(s, B))),
+    "mpc-track": (dict(), _mpc_track),
 })
 
 
@@ -515,11 +634,180 @@ EXPECTED = {'_fused_off-bounded-chol': (['pddp_derivs_f32',
                     'pddp_search_candidates'],
                    (None, True, True, False, True, True, 'search_accept'))}
 
+# the second block (module docstring): `ref_start` is the last flag
+EXPECTED.update(
+{'closed_loop': (['pddp_closed_loop_f32:7,8,11,12,13'],
+                 (None, None, None, True, False, True, None, 0)),
+ 'closed_loop-noisy': (['pddp_closed_loop_noisy_f32:7,8,12,15,16,17'],
+                       (None, None, None, True, False, True, None, 0)),
+ 'closed_loop-plant': (['pddp_closed_loop_f32:7,11,12,13'],
+                       (None, None, None, True, False, True, None, 0)),
+ 'closed_loop-track': (['pddp_closed_loop_track_f32:10,11,14,15,18,19,20'],
+                       (False, False, False, True, True, True, None, 0)),
+ 'closed_loop-track-noisy': (['pddp_closed_loop_track_f32:10,11,18,19,20'],
+                             (False, False, False, True, True, True, None, 0)),
+ 'closed_loop_draws': (['pddp_closed_loop_draws_f32'],
+                       (None, None, None, True, False, True, None, 0)),
+ 'mpc': (['pddp_event_record',
+          'pddp_nominal_rollout_f32:7',
+          'pddp_round_nominal_f32:30',
+          'pddp_mpc_advance_f32:1,11,12,13',
+          'pddp_round_nominal_f32:30',
+          'pddp_mpc_advance_f32:1,11,12,13',
+          'pddp_event_record'],
+         (True, True, True, True, True, True, None, 0)),
+ 'mpc-plant': (['pddp_nominal_rollout_f32:7',
+                'pddp_round_nominal_f32:30',
+                'pddp_mpc_advance_f32:1,12,13',
+                'pddp_round_nominal_f32:30',
+                'pddp_mpc_advance_f32:1,12,13'],
+               (True, True, True, True, True, True, None, 0)),
+ 'mpc-track': (['pddp_nominal_rollout_f32:7',
+                'pddp_derivs_track_f32:1,11,15',
+                'pddp_derivs_track_f32:1',
+                'pddp_riccati_backward_variant_f32',
+                'pddp_line_search_track_f32:1',
+                'pddp_accept_f32',
+                'pddp_derivs_track_f32:1',
+                'pddp_riccati_backward_variant_f32',
+                'pddp_line_search_track_f32:1',
+                'pddp_accept_f32',
+                'pddp_mpc_advance_track_f32:1,14,15,16',
+                'pddp_derivs_track_f32:1',
+                'pddp_riccati_backward_variant_f32',
+                'pddp_line_search_track_f32:1',
+                'pddp_accept_f32',
+                'pddp_derivs_track_f32:1',
+                'pddp_riccati_backward_variant_f32',
+                'pddp_line_search_track_f32:1',
+                'pddp_accept_f32',
+                'pddp_mpc_advance_track_f32:1,14,15,16'],
+               (False, False, False, True, False, True, None, 3)),
+ 'reference': (['pddp_derivs_track_f32:1,11,15',
+                'pddp_derivs_track_f32:1',
+                'pddp_riccati_backward_variant_f32',
+                'pddp_line_search_track_f32:1',
+                'pddp_accept_f32',
+                'pddp_derivs_track_f32:1',
+                'pddp_riccati_backward_variant_f32',
+                'pddp_line_search_track_f32:1',
+                'pddp_accept_f32',
+                'pddp_derivs_track_f32:1',
+                'pddp_riccati_backward_variant_f32',
+                'pddp_line_search_track_f32:1',
+                'pddp_accept_f32',
+                'pddp_derivs_track_f32:1,11,15',
+                'pddp_derivs_track_f32:1',
+                'pddp_riccati_backward_variant_f32',
+                'pddp_line_search_track_f32:1',
+                'pddp_accept_f32'],
+               (False, False, False, False, False, True, None, 3)),
+ 'table': (['pddp_derivs_batch_f32:8,12',
+            'pddp_derivs_batch_f32',
+            'pddp_riccati_backward_variant_f32',
+            'pddp_line_search_batch_f32',
+            'pddp_accept_f32',
+            'pddp_derivs_batch_f32',
+            'pddp_riccati_backward_variant_f32',
+            'pddp_line_search_batch_f32',
+            'pddp_accept_f32',
+            'pddp_derivs_batch_f32',
+            'pddp_riccati_backward_variant_f32',
+            'pddp_line_search_batch_f32',
+            'pddp_accept_f32'],
+           (False, False, False, False, False, True, None, 0)),
+ 'table+reference': (['pddp_derivs_track_f32:11,15',
+                      'pddp_derivs_track_f32',
+                      'pddp_riccati_backward_variant_f32',
+                      'pddp_line_search_track_f32',
+                      'pddp_accept_f32',
+                      'pddp_derivs_track_f32',
+                      'pddp_riccati_backward_variant_f32',
+                      'pddp_line_search_track_f32',
+                      'pddp_accept_f32',
+                      'pddp_derivs_track_f32',
+                      'pddp_riccati_backward_variant_f32',
+                      'pddp_line_search_track_f32',
+                      'pddp_accept_f32'],
+                     (False, False, False, False, False, True, None, 0)),
+ 'table+reference-cleared-in-turn': (['pddp_derivs_batch_f32:8,12',
+                                      'pddp_derivs_batch_f32',
+                                      'pddp_riccati_backward_variant_f32',
+                                      'pddp_line_search_batch_f32',
+                                      'pddp_accept_f32',
+                                      'pddp_round_nominal_f32:30'],
+                                     (True,
+                                      True,
+                                      True,
+                                      False,
+                                      True,
+                                      True,
+                                      None,
+                                      0)),
+ 'table+weights': (['pddp_derivs_weighted_f32:9,13',
+                    'pddp_derivs_weighted_f32',
+                    'pddp_riccati_backward_variant_f32',
+                    'pddp_line_search_weighted_f32',
+                    'pddp_accept_f32',
+                    'pddp_derivs_weighted_f32',
+                    'pddp_riccati_backward_variant_f32',
+                    'pddp_line_search_weighted_f32',
+                    'pddp_accept_f32',
+                    'pddp_derivs_weighted_f32',
+                    'pddp_riccati_backward_variant_f32',
+                    'pddp_line_search_weighted_f32',
+                    'pddp_accept_f32'],
+                   (False, False, False, False, False, True, None, 0)),
+ 'table-capture_replay': (['pddp_derivs_batch_f32:8,12',
+                           'pddp_derivs_batch_f32',
+                           'pddp_riccati_backward_variant_f32',
+                           'pddp_line_search_batch_f32',
+                           'pddp_accept_f32'],
+                          (False, False, False, False, False, True, None, 0)),
+ 'table-f64': (['pddp_derivs_batch_f64:8,12',
+                'pddp_derivs_batch_f64',
+                'pddp_riccati_backward_variant_f64',
+                'pddp_line_search_batch_f64',
+                'pddp_accept_f64',
+                'pddp_derivs_batch_f64',
+                'pddp_riccati_backward_variant_f64',
+                'pddp_line_search_batch_f64',
+                'pddp_accept_f64',
+                'pddp_derivs_batch_f64',
+                'pddp_riccati_backward_variant_f64',
+                'pddp_line_search_batch_f64',
+                'pddp_accept_f64'],
+               (False, False, False, False, False, True, None, 0)),
+ 'weights': (['pddp_derivs_weighted_f32:1,9,13',
+              'pddp_derivs_weighted_f32:1',
+              'pddp_riccati_backward_variant_f32',
+              'pddp_line_search_weighted_f32:1',
+              'pddp_accept_f32',
+              'pddp_derivs_weighted_f32:1',
+              'pddp_riccati_backward_variant_f32',
+              'pddp_line_search_weighted_f32:1',
+              'pddp_accept_f32',
+              'pddp_derivs_weighted_f32:1',
+              'pddp_riccati_backward_variant_f32',
+              'pddp_line_search_weighted_f32:1',
+              'pddp_accept_f32'],
+             (False, False, False, False, False, True, None, 0)),
+ 'weights-cleared': (['pddp_derivs_weighted_f32:1,9,13',
+                      'pddp_derivs_weighted_f32:1',
+                      'pddp_riccati_backward_variant_f32',
+                      'pddp_line_search_weighted_f32:1',
+                      'pddp_accept_f32',
+                      '3*pddp_round_nominal_f32:30'],
+                     (True, True, True, False, True, True, None, 0))})
+
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_round_makes_the_recorded_calls(case, monkeypatch):
     log, flags = record(case, monkeypatch)
     print(case, log, flags)
     want_log, want_flags = EXPECTED[case]
+    # (the first block was recorded before `ref_start` was a flag: none of its
+    # cases sets a reference, so the constructor's 0 stands)
+    want_flags += (0,) * (len(FLAGS) - len(want_flags))
     assert log == want_log
     assert flags == want_flags
