@@ -555,6 +555,78 @@ int pddp_mpc_advance_track_f64(const pddp_problem* problem,
                                int32_t* state, int32_t* iter, uint8_t* active,
                                uint8_t* fresh, int32_t* n_live, void* stream);
 
+/* ---- pddp_mpc_advance[_track]_* under process and measurement noise drawn on
+ * the device (csrc/mpc_advance_noise.hip; the reference has no counterpart).
+ * Trial b is rollout r = rollout_offset + b of the generator stated for
+ * pddp_closed_loop_noisy_* above (its counter layout with S = 1), control step
+ * t its step step_offset + t, stream 0 the process noise w and stream 1 the
+ * measurement noise v: a trial sees the normals pddp_closed_loop_draws_* writes
+ * for (seed, sample_offset = rollout_offset, S = 1), and a fixed policy run by
+ * pddp_closed_loop_noisy_* with that seed and offset sees the same ones.
+ *
+ * With v_std the plant's state is x_true [B][n], in / out; z0 and Z[b][0] hold
+ * what the controller sees.  Trajectory b at control step t of T, in this
+ * order (everything not named is pddp_mpc_advance_*'s):
+ *
+ *   x = x_true[b]                              (v_std == NULL: x = z0[b])
+ *   u = clamp(U[b][0]);  Xlog[b][t] = x;  Ulog[b][t] = u;  Jcl[b] += l(x, u)
+ *         (the TRUE state, under the plant row's goals, or under reference row
+ *          ref_t0 where ref != NULL)
+ *   x' = plant_b(x, u) + disturbance[b][t] + w_std (.) w(r, step_offset + t)
+ *   t == T-1:  Xlog[b][T] = x';  Jcl[b] += l_f(x')
+ *   x_true[b] = x'                             (v_std == NULL: not written)
+ *   y' = x' + v_std (.) v(r, step_offset + t + 1);  z0[b] = y';
+ *         Ylog[b][t+1] = y' where Ylog != NULL    (v_std == NULL: y' = x',
+ *                                                  Ylog is not written)
+ *   shift U;  Z[b][0..N] = the rollout of the shifted U from y' under the
+ *         CONTROLLER's model;  re-arm the controller
+ *
+ * Each noisy sum is one fused multiply-add per component, a + std * z.
+ * w_std, v_std [n], the launch's, of the run's type, not both NULL (that is
+ * pddp_mpc_advance[_track]_*'s launch); a launch without one of them carries
+ * none of its instructions.  Ylog [B][T+1][n], nullable; row 0 is the caller's.
+ * ref == NULL: no tracking, ref_len / ref_t0 are not read, table and plant
+ * rows supply goals as in pddp_mpc_advance_*; ref != NULL: the goals of
+ * pddp_mpc_advance_track_*.
+ *
+ * pddp_mpc_observe_*: y[b] = x[b] + v_std (.) v(rollout_offset + b, step), one
+ * lane per trajectory, through the device function of the hand-over, so that a
+ * trial's first observation obeys the law of every later one (bit for bit what
+ * the hand-over writes for the same x, r and step).  x, y [B][n] (they may be
+ * the same array), mask [B] nullable: trajectories with 0 are not touched.
+ *
+ * PDDP_E_BADARG: w_std == v_std == NULL; v_std with x_true == NULL; ref != NULL
+ * with ref_len < 1 or ref_t0 < 0; step_offset < 0 (or step_offset + T beyond an
+ * int); everything pddp_mpc_advance_* answers it for; observe: a null x, v_std
+ * or y, B or n < 1, n > PDDP_MAX_STATE, step < 0.  PDDP_E_UNSUPPORTED: any
+ * encoding but PDDP_ENC_IGNORE_UNCERTAINTY.  All before any HIP call. */
+int pddp_mpc_advance_noisy_f32(
+    const pddp_problem* problem, const float* table, const float* ref,
+    int ref_len, int ref_t0, int B, int N, int T, int t, float* z0, float* U,
+    float* Z, const float* u_min, const float* u_max, const float* plant,
+    const float* disturbance, const float* w_std, const float* v_std,
+    uint64_t seed, uint64_t rollout_offset, int step_offset, float* x_true,
+    float* Ylog, const uint8_t* mask, float* Xlog, float* Ulog, float* Jcl,
+    int32_t* state_log, uint8_t* live_log, double* mu, double* delta,
+    int32_t* state, int32_t* iter, uint8_t* active, uint8_t* fresh,
+    int32_t* n_live, void* stream);
+int pddp_mpc_advance_noisy_f64(
+    const pddp_problem* problem, const double* table, const double* ref,
+    int ref_len, int ref_t0, int B, int N, int T, int t, double* z0, double* U,
+    double* Z, const double* u_min, const double* u_max, const double* plant,
+    const double* disturbance, const double* w_std, const double* v_std,
+    uint64_t seed, uint64_t rollout_offset, int step_offset, double* x_true,
+    double* Ylog, const uint8_t* mask, double* Xlog, double* Ulog, double* Jcl,
+    int32_t* state_log, uint8_t* live_log, double* mu, double* delta,
+    int32_t* state, int32_t* iter, uint8_t* active, uint8_t* fresh,
+    int32_t* n_live, void* stream);
+int pddp_mpc_observe_f32(int B, int n, const float* x, const float* v_std,
+                         uint64_t seed, uint64_t rollout_offset, int step,
+                         const uint8_t* mask, float* y, void* stream);
+int pddp_mpc_observe_f64(int B, int n, const double* x, const double* v_std,
+                         uint64_t seed, uint64_t rollout_offset, int step,
+                         const uint8_t* mask, double* y, void* stream);
+
 /* ---- per-trajectory cost weights (csrc/weights.hip) -------------------------
  * `weights` [B][PDDP_WEIGHT_ROW], device memory of the run's dtype: row b holds
  *   [PDDP_WEIGHT_Q      .. +7]  the diagonal of Q      of trajectory b

@@ -96,6 +96,10 @@ _SIGS = {
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
     "pddp_mpc_advance_track": [_P, _P, _P] + [c_int] * 6 + [_P] * 21,
+    "pddp_mpc_advance_noisy": [_P, _P, _P] + [c_int] * 6 + [_P] * 9 +
+                              [c_uint64, c_uint64, c_int] + [_P] * 16,
+    "pddp_mpc_observe": [c_int, c_int, _P, _P, c_uint64, c_uint64, c_int, _P,
+                         _P, _P],
     "pddp_derivs_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] * 10,
     "pddp_line_search_weighted": [_P, _P, _P] + [c_int] * 3 + [_P] * 12,
     "pddp_search_accept": [_P, c_int, c_int, c_int] + [_P] * 11 +
@@ -161,6 +165,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_closed_loop_track",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
+          "pddp_mpc_advance_noisy", "pddp_mpc_observe",
           "pddp_derivs_weighted", "pddp_line_search_weighted",
           "pddp_pack_best", "pddp_sweep_nominal", "pddp_gp_step",
           "pddp_gp_step_masked",

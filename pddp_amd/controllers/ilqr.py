@@ -346,7 +346,13 @@ class iLQRController(Controller):
         Returns what `_apply_controller(..., mpc=True)` (pddp.py:209-245)
         returns, ((X[:-1], U, X[1:] - X[:-1]), J) with X [steps+1][n] and J a
         scalar per trajectory; after a fit without batch axis the one
-        trajectory's, otherwise with the leading B."""
+        trajectory's, otherwise with the leading B.  With the solver's
+        `process_std=`, `obs_std=`, `seed=`, `sample_offset=`, `step_offset=`
+        the trial runs under noise drawn on the device (`closed_loop`'s
+        generator: the same seed gives the fitted policy and the re-planning
+        one the same noise); X and J are then the TRUE states and their cost -
+        the observations the controller re-planned from stay with the
+        solver's own return value (`Y`)."""
         r = self._fitted_solver().mpc_closed_loop(steps, rounds_per_step,
                                                   **kwargs)
         X, U, J = r.X, r.U, r.J

@@ -57,6 +57,7 @@ records+separate.  Weights and a reference refuse each other.
 """
 import ctypes
 import functools
+import numbers
 import types
 
 import torch
@@ -189,6 +190,9 @@ class ILQRSolver(object):
         # horizon index 0 reads: set_reference()
         self.reference = None
         self.ref_start = 0
+        # [B][n] the plant's state behind the observation in z0, while an
+        # mpc_closed_loop(obs_std=) trial can be continued; else None
+        self.x_true = None
         # [B][_native.WEIGHT_ROW] per-trajectory diagonals of Q, Q_term, R, or
         # None: set_batch_weights()
         self.batch_weights = None
@@ -668,7 +672,10 @@ class ILQRSolver(object):
 
     @_on_device
     def set_nominal(self, z0, U):
-        """ilqr.py:274-277: new nominal controls, regularisation reset."""
+        """ilqr.py:274-277: new nominal controls, regularisation reset.
+        (z0 is the plant's state again: a noisy MPC trial's `x_true` is
+        dropped.)"""
+        self.x_true = None
         self.z0.copy_(z0.reshape(self.B, self.n))
         self.U.copy_(U.reshape(self.B, self.N, self.m))
         self.reset_controller_state()
@@ -1051,7 +1058,7 @@ class ILQRSolver(object):
                          self.dtype, *(head + noise + tail))
         return out
 
-    def _noise_std(self, name, std):
+    def _noise_std(self, name, std, what="closed_loop"):
         """[n] device vector of a noise level given as a scalar or [n]."""
         if std is None:
             return None
@@ -1061,13 +1068,13 @@ class ILQRSolver(object):
             std = std.repeat(self.n)
         if tuple(std.shape) != (self.n,):
             raise _native.NativeError(
-                "closed_loop: %s has shape %s, expected a scalar or (%d,)" % (
-                    name, tuple(std.shape), self.n))
+                "%s: %s has shape %s, expected a scalar or (%d,)" % (
+                    what, name, tuple(std.shape), self.n))
         return std.contiguous()
 
     @_on_device
     def closed_loop_draws(self, samples, which="process", seed=0,
-                          sample_offset=0):
+                          sample_offset=0, steps=None):
         """The unit normals `closed_loop(samples, seed=, sample_offset=)`
         draws, W [B][N][S][n] (pddp_closed_loop_draws_*; time-major like X):
         `which` "process" for w_t, "obs" for v_t.  To look at, or to replay,
@@ -1075,14 +1082,22 @@ class ILQRSolver(object):
         `mpc_closed_loop`'s disturbance.  (No cost is read: per-trajectory
         cost weights, `set_batch_weights`, change nothing here; the costs
         `closed_loop` reports for these draws are under the shared problem's
-        Q, Q_term, R and the plant row's goals - the common yardstick.)"""
+        Q, Q_term, R and the plant row's goals - the common yardstick.)
+
+        `steps`: the number of time rows in place of N, W [B][steps][S][n] -
+        the normals of a T-step `mpc_closed_loop(process_std=, obs_std=,
+        seed=)` trial are `closed_loop_draws(1, which, seed, sample_offset,
+        steps=T + 1)[:, :, 0]` (row step_offset + t: w of control step t, v of
+        the observation y_t)."""
         if which not in ("process", "obs"):
             raise _native.NativeError(
                 "closed_loop_draws: which is %r, expected 'process' or 'obs'"
                 % (which,))
-        B, N, S = self.B, self.N, int(samples)
-        if S < 1:
-            raise _native.NativeError("closed_loop_draws: %d samples" % S)
+        B, S = self.B, int(samples)
+        N = self.N if steps is None else int(steps)
+        if S < 1 or N < 1:
+            raise _native.NativeError(
+                "closed_loop_draws: %d samples, %d steps" % (S, N))
         W = torch.empty(B, N, S, self.n, dtype=self.dtype, device=self.device)
         _native.call("pddp_closed_loop_draws", self.dtype, B, N, S, self.n,
                      0 if which == "process" else 1, int(seed),
@@ -1101,7 +1116,9 @@ class ILQRSolver(object):
     @_on_device
     def mpc_closed_loop(self, steps, rounds_per_step, z0=None, params=None,
                         x_goal=None, u_goal=None, disturbance=None, tol=5e-6,
-                        max_reg=1e10, active=None, events=None):
+                        max_reg=1e10, active=None, events=None,
+                        process_std=None, obs_std=None, seed=0,
+                        sample_offset=0, step_offset=0):
         """A receding-horizon trial of every trajectory on its own plant, on
         the device (the batched `_apply_controller(..., mpc=True)`,
         pddp.py:209-245, around `forward(mpc=True)`, ilqr.py:355-362, with the
@@ -1153,13 +1170,45 @@ class ILQRSolver(object):
         inside the trial optimise under each trajectory's weights; the cost
         the trial reports (`J`) is under the shared problem's Q, Q_term, R
         and the plant row's goals - the common yardstick.  The advance kernel
-        is unchanged."""
+        is unchanged.
+
+        `process_std`, `obs_std` (each a scalar or [n]; None: none of it):
+        noise drawn inside the advance (pddp_mpc_advance_noisy_*,
+        csrc/mpc_advance_noise.hip, with the reference window when a reference
+        is set) - the plant steps to x' + disturbance + process_std (.) w_t,
+        and with `obs_std` the controller re-plans from y_t = x_t + obs_std (.)
+        v_t instead of the plant's state.  Trial b is rollout `sample_offset`
+        + b and control step t step `step_offset` + t of `closed_loop`'s
+        generator: `closed_loop(1, process_std=, obs_std=, seed=,
+        sample_offset=)` runs the fitted policy under the very normals this
+        trial re-plans under, and `closed_loop_draws(1, which, seed,
+        sample_offset, steps=)[:, :, 0]` returns them.  With both None the
+        launches are those of the call without these keywords.
+        With `obs_std`, `z0` (or `self.z0`) is the TRUE start: the solver keeps
+        the plant's state in `x_true` [B][n], the first observation y_0 is
+        drawn at step `step_offset` (pddp_mpc_observe_*) and is what
+        `set_nominal` gets, and the returned object has `Y` [B][steps+1][n],
+        the observations (None without `obs_std`); `X` and `J` are the true
+        states and their cost.  After such a trial a call with `z0=None` and
+        `obs_std` continues it: the plant is at `x_true`, the controller at
+        the held `self.z0`, no new first observation is drawn; pass
+        `step_offset` = the steps already done.  `set_nominal` from outside,
+        or a trial without `obs_std`, drops `x_true`."""
         self._need_sample_problem("mpc_closed_loop")
         B, N, n, m = self.B, self.N, self.n, self.m
         T, R = int(steps), int(rounds_per_step)
         if T < 1 or R < 1:
             raise _native.NativeError(
                 "mpc_closed_loop: %d steps of %d rounds" % (T, R))
+        if isinstance(step_offset, bool) or \
+                not isinstance(step_offset, numbers.Integral) or \
+                step_offset < 0:
+            raise _native.NativeError(
+                "mpc_closed_loop: step_offset is %r, expected an integer >= 0"
+                % (step_offset,))
+        step_offset = int(step_offset)
+        w_std = self._noise_std("process_std", process_std, "mpc_closed_loop")
+        v_std = self._noise_std("obs_std", obs_std, "mpc_closed_loop")
         opts = dict(dtype=self.dtype, device=self.device)
         if z0 is not None:
             z0 = torch.as_tensor(z0).to(**opts)
@@ -1180,27 +1229,58 @@ class ILQRSolver(object):
             X=self._out(masked, B, T + 1, n), U=self._out(masked, B, T, m),
             J=self._out(masked, B),
             states=self._out(masked, B, T, dtype=torch.int32, fill=0),
-            unfinished=self._out(masked, B, T, dtype=torch.uint8, fill=0))
+            unfinished=self._out(masked, B, T, dtype=torch.uint8, fill=0),
+            Y=None)
         record = _native.lib().pddp_event_record
         if events is not None:
             _native.check(record(events[0], self._s()), "pddp_event_record")
-        self.set_nominal(self.z0 if z0 is None else z0, self.U)
+        p = _native.ptr
+        x_true = None
+        if v_std is None:
+            self.set_nominal(self.z0 if z0 is None else z0, self.U)
+        elif z0 is None and self.x_true is not None:
+            # the trial goes on: the plant at x_true, the controller at the
+            # observation it holds
+            x_true = self.x_true
+            self.set_nominal(self.z0, self.U)
+        else:
+            # the true start, and the first observation under the law of every
+            # later one (a skipped trajectory keeps its start)
+            x_true = (self.z0 if z0 is None else z0).clone(
+                memory_format=torch.contiguous_format)
+            y0 = x_true.clone()
+            _native.call("pddp_mpc_observe", self.dtype, B, n, p(x_true),
+                         p(v_std), int(seed), int(sample_offset), step_offset,
+                         p(active), p(y0), self._s())
+            self.set_nominal(y0, self.U)
+        self.x_true = x_true  # (set_nominal dropped it)
+        if x_true is not None:
+            out.Y = self._out(masked, B, T + 1, n)
+            out.Y[:, 0] = self.z0 if not masked else torch.where(
+                active.bool().unsqueeze(1), self.z0, out.Y[:, 0])
         if masked:  # (the skipped ones take no part in the rounds either)
             self.active.mul_(active)
             self.fresh.mul_(active)
-        p = _native.ptr
         b = self._buffers()
         tail = (p(self.z0), b.U, b.Z, b.u_min, b.u_max, p(plant),
                 p(disturbance), p(active), p(out.X), p(out.U), p(out.J),
                 p(out.states), p(out.unfinished), b.mu, b.delta, b.state,
                 b.iter, b.active, b.fresh, b.n_live)
         tracking = self.reference is not None
-        name = "pddp_mpc_advance_track" if tracking else "pddp_mpc_advance"
+        noisy = w_std is not None or v_std is not None
+        if noisy:  # (one entry point, with or without a reference)
+            name = "pddp_mpc_advance_noisy"
+            tail = tail[:7] + (p(w_std), p(v_std), int(seed),
+                               int(sample_offset), step_offset, p(x_true),
+                               p(out.Y)) + tail[7:]
+        else:
+            name = "pddp_mpc_advance_track" if tracking else "pddp_mpc_advance"
         advance = getattr(_native.lib(),
                           name + "_" + _native.suffix(self.dtype))
         for t in range(T):
             self.rounds(R, tol, max_reg, n_iterations=1)
-            ref = self._ref_window() if tracking else ()
+            ref = self._ref_window() if tracking else \
+                ((None, 0, 0) if noisy else ())
             _native.check(
                 advance(self._pp, p(self.batch_table), *ref, B, N, T, t,
                         *tail, self._s()), name)

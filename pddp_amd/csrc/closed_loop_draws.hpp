@@ -92,6 +92,43 @@ PDDP_DEV void draw_scaled(uint64_t seed, uint64_t r, int t, int w,
   }
 }
 
+// x += std (.) the n unit normals of (r, t, w), each component ONE explicit
+// fma: no contraction can change it, so two kernels that form the sum from the
+// same x agree bit for bit (the hand-over of an MPC trial and its first
+// observation, mpc_advance_noise.hip).
+PDDP_DEV float fma_of(float a, float b, float c) {
+  return __builtin_fmaf(a, b, c);
+}
+PDDP_DEV double fma_of(double a, double b, double c) {
+  return __builtin_fma(a, b, c);
+}
+// (the two halves: the draws depend on no state and may be made ahead of the
+// chain that ends in the sum)
+template <typename T, int n>
+PDDP_DEV void draw_units(uint64_t seed, uint64_t r, int t, int w, T (&out)[n]) {
+  constexpr int kPer = DrawBlock<T>::kPer;
+#pragma unroll
+  for (int k = 0; k < (n + kPer - 1) / kPer; ++k) {
+    T z[kPer];
+    draw_block(seed, r, t, w, k, z);
+#pragma unroll
+    for (int i = 0; i < kPer; ++i)
+      if (k * kPer + i < n) out[k * kPer + i] = z[i];
+  }
+}
+template <typename T, int n>
+PDDP_DEV void add_scaled(const T* std, const T (&z)[n], T (&x)[n]) {
+#pragma unroll
+  for (int j = 0; j < n; ++j) x[j] = fma_of(std[j], z[j], x[j]);
+}
+template <typename T, int n>
+PDDP_DEV void draw_added(uint64_t seed, uint64_t r, int t, int w, const T* std,
+                         T (&x)[n]) {
+  T z[n];
+  draw_units<T, n>(seed, r, t, w, z);
+  add_scaled<T, n>(std, z, x);
+}
+
 // the noise of a launch of rollouts
 template <typename T>
 struct NoiseArgs {

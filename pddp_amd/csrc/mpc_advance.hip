@@ -63,7 +63,14 @@ __global__ __launch_bounds__(kWave) void mpc_advance_kernel(
   if (a.plant != nullptr)                                                      \
     write_params_and_goals<T, MODEL>(Pl, a.plant + (size_t)b * PDDP_BATCH_ROW);
 #define PDDP_TERMINAL_GOALS
+// (no noise: z0 is the plant's state and the controller's)
+#define PDDP_PLANT_STATE
+#define PDDP_PLANT_STEPPED
+#define PDDP_NOMINAL_START
 #include "mpc_advance_body.inc"
+#undef PDDP_NOMINAL_START
+#undef PDDP_PLANT_STEPPED
+#undef PDDP_PLANT_STATE
 #undef PDDP_TERMINAL_GOALS
 #undef PDDP_PLANT_OF_B
 #undef PDDP_PROBLEM_OF_B

@@ -5,6 +5,13 @@
 // them); PDDP_PLANT_OF_B declares `Pl`, the plant of row b with the goals the
 // step's stage cost is logged under; PDDP_TERMINAL_GOALS, at t == T - 1, is
 // empty or writes the terminal cost's goals over Pl's.
+// Three hooks separate the plant's state from what the controller sees; both
+// kernels above define them empty (z0 is then both), mpc_advance_noisy_kernel
+// (mpc_advance_noise.hip) puts its draws there: PDDP_PLANT_STATE, behind the
+// read of z0 into `z`, may replace z by the plant's true state;
+// PDDP_PLANT_STEPPED, behind the plant step and the disturbance, may add to
+// `zn`; PDDP_NOMINAL_START, ahead of the write of z0 and Z[0], may keep the
+// plant's `z` elsewhere and turn z into the observation.
   using D = ModelDims<MODEL>;
   constexpr int n = D::n, m = D::m;
   if (blockIdx.x == 0 && a.n_live != nullptr) {
@@ -39,6 +46,7 @@
   T z[n], zn[n], u[m], cur[m], nxt[m];
 #pragma unroll
   for (int j = 0; j < n; ++j) z[j] = a.z0[(size_t)b * n + j];
+  PDDP_PLANT_STATE
 #pragma unroll
   for (int j = 0; j < m; ++j) {
     u[j] = Ub[j];
@@ -73,6 +81,7 @@
 #pragma unroll
       for (int j = 0; j < n; ++j) zn[j] = zn[j] + w[j];
     }
+    PDDP_PLANT_STEPPED
 #pragma unroll
     for (int j = 0; j < n; ++j) z[j] = zn[j];
     if (t == TT - 1) {
@@ -89,6 +98,7 @@
   // x' under the controller's model, in one loop over time.  Row i + 2 is read
   // before row i is written; the last row is read for the last time in the
   // iteration before it is written.
+  PDDP_NOMINAL_START
 #pragma unroll
   for (int j = 0; j < n; ++j) {
     a.z0[(size_t)b * n + j] = z[j];

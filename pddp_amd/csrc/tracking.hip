@@ -144,7 +144,14 @@ __global__ __launch_bounds__(kWave) void track_mpc_advance_kernel(
 #define PDDP_TERMINAL_GOALS                                                    \
   const T* row1 = ref_row(goals, b, 1);                                        \
   PDDP_COPY(D::na, Pl.goal, row1 + PDDP_REF_X_GOAL)
+// (no noise: z0 is the plant's state and the controller's)
+#define PDDP_PLANT_STATE
+#define PDDP_PLANT_STEPPED
+#define PDDP_NOMINAL_START
 #include "mpc_advance_body.inc"
+#undef PDDP_NOMINAL_START
+#undef PDDP_PLANT_STEPPED
+#undef PDDP_PLANT_STATE
 #undef PDDP_TERMINAL_GOALS
 #undef PDDP_PLANT_OF_B
 }
