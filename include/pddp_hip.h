@@ -350,7 +350,7 @@ int pddp_closed_loop_f64(const pddp_problem* problem, int B, int N, int S,
                          double* Jc, double* stats, void* stream);
 
 /* ---- pddp_closed_loop_* under process and measurement noise drawn on the
- * device (csrc/closed_loop_noise.hip; the reference has no counterpart).
+ * device (csrc/closed_loop.hip; the reference has no counterpart).
  * Rollout (b, s), t = 0 .. N-1, in this order:
  *
  *   y   = x_t + v_std (.) v_t                (v_std == NULL: y = x_t)
@@ -491,7 +491,7 @@ int pddp_mpc_advance_f64(const pddp_problem* problem, const double* table,
  * every result as pddp_derivs_batch_* / pddp_line_search_batch_* (one
  * workgroup per trajectory and one lane per time step; one lane per
  * (trajectory, step size), any A).
- * pddp_mpc_advance_track_*: pddp_mpc_advance_* with
+ * pddp_mpc_advance_track_* (csrc/mpc_advance.hip): pddp_mpc_advance_* with
  *   Jcl[b] += l(x, u) under row ref_t0;  t == T-1: += l_f(x') under row
  *   ref_t0 + 1 (both clamped to the last row)
  * plant [B][PDDP_BATCH_ROW], nullable: the plant's PARAMETERS only; its goal
@@ -685,7 +685,7 @@ int pddp_line_search_weighted_f64(const pddp_problem* problem,
                                   double* Uc, double* Jc, void* stream);
 
 /* ---- pddp_closed_loop_* / pddp_closed_loop_noisy_* ALONG A REFERENCE
- * (csrc/closed_loop_track.hip): the same S rollouts per trajectory, costed
+ * (csrc/closed_loop.hip): the same S rollouts per trajectory, costed
  * under a goal per time step.  Rollout (b, s) takes
  *
  *   J += l(x_t, u_t)  under row min(ref_t0 + t, ref_len - 1) of trajectory b,

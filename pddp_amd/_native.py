@@ -66,7 +66,10 @@ def build(force=False):
     return LIB_PATH
 
 
-_P = c_void_p
+_P = c_void_p  # (then: pieces of the closed-loop and hand-over signatures)
+_REF, _NOISE = [_P, c_int, c_int], [_P, _P, c_uint64, c_uint64]
+_LOOP, _LOOP_OUT = [c_int] * 3 + [_P] * 7, [_P] * 6
+_STEP, _STEP_OUT = [c_int] * 4 + [_P] * 7, [_P] * 14
 _SIGS = {
     "pddp_hip_abi_version": [],
     "pddp_hip_device_count": [],
@@ -86,18 +89,16 @@ _SIGS = {
     "pddp_nominal_rollout_batch": [_P, _P, c_int, c_int] + [_P] * 7,
     "pddp_derivs_batch": [_P, _P, c_int, c_int] + [_P] * 10,
     "pddp_line_search_batch": [_P, _P, c_int, c_int, c_int] + [_P] * 12,
-    "pddp_closed_loop": [_P, c_int, c_int, c_int] + [_P] * 13,
-    "pddp_closed_loop_noisy": [_P, c_int, c_int, c_int] + [_P] * 9 +
-                              [c_uint64, c_uint64] + [_P] * 6,
+    "pddp_closed_loop": [_P] + _LOOP + _LOOP_OUT,
+    "pddp_closed_loop_noisy": [_P] + _LOOP + _NOISE + _LOOP_OUT,
     "pddp_closed_loop_draws": [c_int] * 5 + [c_uint64, c_uint64, _P, _P],
-    "pddp_closed_loop_track": [_P, _P] + [c_int] * 5 + [_P] * 9 +
-                              [c_uint64, c_uint64] + [_P] * 6,
-    "pddp_mpc_advance": [_P, _P] + [c_int] * 4 + [_P] * 21,
+    "pddp_closed_loop_track": [_P] + _REF + _LOOP + _NOISE + _LOOP_OUT,
+    "pddp_mpc_advance": [_P, _P] + _STEP + _STEP_OUT,
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
-    "pddp_mpc_advance_track": [_P, _P, _P] + [c_int] * 6 + [_P] * 21,
-    "pddp_mpc_advance_noisy": [_P, _P, _P] + [c_int] * 6 + [_P] * 9 +
-                              [c_uint64, c_uint64, c_int] + [_P] * 16,
+    "pddp_mpc_advance_track": [_P, _P] + _REF + _STEP + _STEP_OUT,
+    "pddp_mpc_advance_noisy": [_P, _P] + _REF + _STEP + _NOISE +
+                              [c_int, _P, _P] + _STEP_OUT,
     "pddp_mpc_observe": [c_int, c_int, _P, _P, c_uint64, c_uint64, c_int, _P,
                          _P, _P],
     "pddp_derivs_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] * 10,

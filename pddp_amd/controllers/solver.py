@@ -1038,24 +1038,23 @@ class ILQRSolver(object):
             X=self._out(False, B, N + 1, S, n) if keep else None,
             U=self._out(False, B, N, S, m) if keep else None)
         p = _native.ptr
-        head = (self._pp, B, N, S, p(self.Z), p(self.U), p(gains),
-                p(None if z0 is None else z0.contiguous()), p(plant),
-                p(self.u_min), p(self.u_max))
-        tail = (p(active), p(out.X), p(out.U), p(out.J), p(out.stats),
-                self._s())
         w_std = self._noise_std("process_std", process_std)
         v_std = self._noise_std("obs_std", obs_std)
+        # (in ABI order: problem, [reference,] shapes, nominal, plant, [noise])
+        nominal = (p(self.Z), p(self.U), p(gains))
+        starts = (p(None if z0 is None else z0.contiguous()), p(plant),
+                  p(self.u_min), p(self.u_max))
         noise = (p(w_std), p(v_std), int(seed), int(sample_offset))
+        outputs = (p(active), p(out.X), p(out.U), p(out.J), p(out.stats),
+                   self._s())
         if track:  # (with or without noise: one entry point)
-            self._launch(events, _native.call, "pddp_closed_loop_track",
-                         self.dtype, *(head[:1] + self._ref_window() +
-                                       head[1:] + noise + tail))
+            name, ref = "pddp_closed_loop_track", self._ref_window()
         elif process_std is None and obs_std is None:
-            self._launch(events, _native.call, "pddp_closed_loop", self.dtype,
-                         *(head + tail))
+            name, ref, noise = "pddp_closed_loop", (), ()
         else:
-            self._launch(events, _native.call, "pddp_closed_loop_noisy",
-                         self.dtype, *(head + noise + tail))
+            name, ref = "pddp_closed_loop_noisy", ()
+        self._launch(events, _native.call, name, self.dtype, self._pp, *ref,
+                     B, N, S, *nominal, *starts, *noise, *outputs)
         return out
 
     def _noise_std(self, name, std, what="closed_loop"):
@@ -1262,17 +1261,18 @@ class ILQRSolver(object):
             self.active.mul_(active)
             self.fresh.mul_(active)
         b = self._buffers()
-        tail = (p(self.z0), b.U, b.Z, b.u_min, b.u_max, p(plant),
-                p(disturbance), p(active), p(out.X), p(out.U), p(out.J),
-                p(out.states), p(out.unfinished), b.mu, b.delta, b.state,
-                b.iter, b.active, b.fresh, b.n_live)
+        nominal = (p(self.z0), b.U, b.Z, b.u_min, b.u_max)
+        plants = (p(plant), p(disturbance))
+        outputs = (p(active), p(out.X), p(out.U), p(out.J), p(out.states),
+                   p(out.unfinished), b.mu, b.delta, b.state, b.iter,
+                   b.active, b.fresh, b.n_live)
         tracking = self.reference is not None
-        noisy = w_std is not None or v_std is not None
-        if noisy:  # (one entry point, with or without a reference)
+        noise = ()
+        if w_std is not None or v_std is not None:
+            # (one entry point, with a reference window or a NULL one)
             name = "pddp_mpc_advance_noisy"
-            tail = tail[:7] + (p(w_std), p(v_std), int(seed),
-                               int(sample_offset), step_offset, p(x_true),
-                               p(out.Y)) + tail[7:]
+            noise = (p(w_std), p(v_std), int(seed), int(sample_offset),
+                     step_offset, p(x_true), p(out.Y))
         else:
             name = "pddp_mpc_advance_track" if tracking else "pddp_mpc_advance"
         advance = getattr(_native.lib(),
@@ -1280,10 +1280,10 @@ class ILQRSolver(object):
         for t in range(T):
             self.rounds(R, tol, max_reg, n_iterations=1)
             ref = self._ref_window() if tracking else \
-                ((None, 0, 0) if noisy else ())
-            _native.check(
+                ((None, 0, 0) if noise else ())
+            _native.check(  # (problem, [reference,] shapes, nominal, ...)
                 advance(self._pp, p(self.batch_table), *ref, B, N, T, t,
-                        *tail, self._s()), name)
+                        *nominal, *plants, *noise, *outputs, self._s()), name)
             # (as set_nominal leaves the host flags: every nominal is new)
             self._derivs_due = True
             if tracking:  # the next step's window; its records are all new

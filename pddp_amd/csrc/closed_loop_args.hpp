@@ -1,6 +1,6 @@
-// closed_loop_args.hpp - what closed_loop.hip, closed_loop_noise.hip and
-// closed_loop_track.hip share besides the kernel text (closed_loop_body.inc):
-// the argument block, the cost statistics and the launch geometry.
+// closed_loop_args.hpp - what the three rollout kernels of closed_loop.hip
+// share besides the kernel text (closed_loop_body.inc): the argument block with
+// its test, the cost statistics and the launch geometry.
 #pragma once
 
 #include <limits>
@@ -35,6 +35,14 @@ struct ClosedLoopArgs {
   T* Jc;     // [B][S]
   T* stats;  // [B][4] or NULL
 };
+
+// Host side of every entry point that takes the block: the argument test, with
+// the nominal (Z, U) the launch carries beside it.
+template <typename T>
+inline bool args_ok(const ClosedLoopArgs<T>& a, const T* Z, const T* U) {
+  return !(a.B <= 0 || a.N <= 0 || a.S <= 0 || !Z || !U || !a.Jc ||
+           (a.Xc == nullptr) != (a.Uc == nullptr));
+}
 
 // The statistics of the finite costs a lane (then a lane group) has seen.
 template <typename T>

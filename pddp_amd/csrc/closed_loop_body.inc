@@ -1,7 +1,7 @@
 // closed_loop_body.inc - the closed-loop rollouts of a lane and the statistics
-// of a controller's costs: the text of closed_loop_kernel (closed_loop.hip),
-// closed_loop_noisy_kernel (closed_loop_noise.hip) and closed_loop_track_kernel
-// (closed_loop_track.hip).  The including kernel has
+// of a controller's costs: the text of closed_loop_kernel,
+// closed_loop_noisy_kernel and closed_loop_track_kernel (closed_loop.hip).  The
+// including kernel has
 // `shared`, `a` (ClosedLoopArgs), `Znom`, `Unom`, `gains` and defines
 //   PDDP_NOISE_LEVELS      after the bounds: empty, or the launch's noise levels
 //   PDDP_NOISE_OF_ROLLOUT  before the time loop: empty, or what rollout (b, s)
@@ -13,7 +13,7 @@
 //   PDDP_NEXT(j)           component j of the next state: zn[j], or with process
 //                          noise
 // and, for the goals of `P` (empty where a rollout has ONE goal: the plant
-// row's or the shared problem's; closed_loop_track.hip takes them from a
+// row's or the shared problem's; closed_loop_track_kernel takes them from a
 // reference row, as tracking.hip does at line_search_body.inc's hooks)
 //   PDDP_GOALS_TAKE_FIRST    ahead of the time loop: row 0's over P's
 //   PDDP_GOALS_REQUEST_NEXT  behind the step's draws: row t + 1, ahead of the

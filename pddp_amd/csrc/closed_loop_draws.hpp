@@ -1,7 +1,7 @@
 // closed_loop_draws.hpp - the draws of the closed-loop rollouts under noise:
-// what closed_loop_noise.hip and closed_loop_track.hip share besides the kernel
-// text (closed_loop_body.inc).  include/pddp_hip.h states the draws; DESIGN.md
-// 3.4g.
+// what the noisy and the tracked rollout kernel of closed_loop.hip and the
+// hand-over of mpc_advance_noise.hip share.  include/pddp_hip.h states the
+// draws; DESIGN.md 3.4g.
 #pragma once
 
 #include "pddp_common.hpp"

@@ -1,7 +1,7 @@
 // closed_loop_noise_hooks.inc - closed_loop_body.inc's five noise hooks with
 // the draws of closed_loop_draws.hpp at them: the text closed_loop_noisy_kernel
-// (closed_loop_noise.hip) and closed_loop_track_kernel (closed_loop_track.hip)
-// define ahead of the body and undefine behind it.  The including kernel has
+// and closed_loop_track_kernel (closed_loop.hip) define ahead of the body and
+// undefine behind it.  The including kernel has
 // `noise` (NoiseArgs) and the compile-time flags PROC / OBS: which streams the
 // launch draws (DESIGN.md 3.4g).
 #define PDDP_NOISE_LEVELS /* (the launch's: scalar registers) */               \

@@ -1,7 +1,9 @@
 // mpc_advance.hip - the hand-over between two control steps of a receding-
-// horizon (MPC) trial: apply the first action of every trajectory's re-optimised
-// nominal to its plant, log the trial, shift the warm start, roll out the new
-// nominal and re-arm the controller state machine, in one launch.
+// horizon (MPC) trial: apply the first action of every trajectory's
+// re-optimised nominal to its plant, log the trial, shift the warm start, roll
+// out the new nominal and re-arm the controller state machine, in one launch -
+// with ONE goal (pddp_mpc_advance_*) or a goal PER TIME STEP
+// (pddp_mpc_advance_track_*).
 //
 //   the trial step of the outer loop   pddp/controllers/pddp.py:209-245
 //                                      (_apply_controller, mpc=True, batched:
@@ -9,42 +11,19 @@
 //   emit U[0], shift the nominal       ilqr.py:355-362 (forward, mpc=True)
 //   the regularisation reset           ilqr.py:364-367 (_reset_reg)
 //
-// A translation unit of its own (csrc/Makefile: FLAGS_mpc_advance).  The
-// kernel's loop is an included text, mpc_advance_body.inc, which tracking.hip
-// includes too with a goal per time step; the row writers are
+// A translation unit of its own (csrc/Makefile: FLAGS_mpc_advance).  Both
+// kernels' loop is an included text, mpc_advance_body.inc, with the goal hooks
+// of mpc_advance_goal_hooks.inc; mpc_advance_noise.hip includes the two as
+// well, with draws at the text's state hooks.  The row writers are
 // model_params.hpp's.
 #include <type_traits>
 #include "models.hpp"
 #include "problem_args.hpp"
 #include "model_params.hpp"
+#include "mpc_advance_args.hpp"
+#include "ref_args.hpp"
 
 namespace pddp {
-
-template <typename T>
-struct MpcAdvanceArgs {
-  int B, N, T_, t;   // control step t of T_
-  const T* table;    // [B][PDDP_BATCH_ROW] or NULL: the controller's model
-  const T* plant;    // [B][PDDP_BATCH_ROW] or NULL: the controller's model
-  T* z0;             // [B][n]       in: x_t, out: x_{t+1}
-  T* U;              // [B][N][m]    shifted in place (unclamped)
-  T* Z;              // [B][N+1][n]  out: the rollout of the shifted nominal
-  const T* u_min;
-  const T* u_max;
-  const T* disturbance;  // [B][T_][n] or NULL
-  const uint8_t* mask;   // [B] or NULL
-  T* Xlog;               // [B][T_+1][n]
-  T* Ulog;               // [B][T_][m]
-  T* Jcl;                // [B]
-  int32_t* state_log;    // [B][T_]
-  uint8_t* live_log;     // [B][T_]
-  double* mu;
-  double* delta;
-  int32_t* state;
-  int32_t* iter;
-  uint8_t* active;
-  uint8_t* fresh;
-  int32_t* n_live;  // [PDDP_LIVE_SHARDS] or NULL
-};
 
 // Mapping: one lane per trajectory, as nominal_rollout_kernel; everything of
 // trajectory b is read and written by its lane alone, J in t order, no
@@ -54,15 +33,10 @@ struct MpcAdvanceArgs {
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kWave) void mpc_advance_kernel(
     ProblemT<T> shared, MpcAdvanceArgs<T> a) {
-#define PDDP_PROBLEM_OF_B                                                      \
-  ProblemT<T> P = shared;                                                      \
-  if (a.table != nullptr)                                                      \
-    write_params_and_goals<T, MODEL>(P, a.table + (size_t)b * PDDP_BATCH_ROW);
-#define PDDP_PLANT_OF_B                                                        \
-  ProblemT<T> Pl = P;                                                          \
-  if (a.plant != nullptr)                                                      \
-    write_params_and_goals<T, MODEL>(Pl, a.plant + (size_t)b * PDDP_BATCH_ROW);
-#define PDDP_TERMINAL_GOALS
+  constexpr bool TRACK = false;
+  const RefArgs<T> goals{};
+#define PDDP_TABLE a.table
+#include "mpc_advance_goal_hooks.inc"
 // (no noise: z0 is the plant's state and the controller's)
 #define PDDP_PLANT_STATE
 #define PDDP_PLANT_STEPPED
@@ -74,60 +48,94 @@ __global__ __launch_bounds__(kWave) void mpc_advance_kernel(
 #undef PDDP_TERMINAL_GOALS
 #undef PDDP_PLANT_OF_B
 #undef PDDP_PROBLEM_OF_B
+#undef PDDP_TABLE
+}
+
+// The same along a reference: the stage cost logged at control step t is taken
+// under reference row ref_t0, the terminal cost at t == T - 1 under row
+// ref_t0 + 1 (both clamped).  The plant row supplies the parameters only.
+// Dynamics, shift, rollout and re-arm read no goal.
+template <typename T, int MODEL>
+__global__ __launch_bounds__(kWave) void track_mpc_advance_kernel(
+    ProblemT<T> shared, TrackAdvanceArgs<T> a, RefArgs<T> goals) {
+  constexpr bool TRACK = true;
+#define PDDP_TABLE goals.table
+#include "mpc_advance_goal_hooks.inc"
+#define PDDP_PLANT_STATE
+#define PDDP_PLANT_STEPPED
+#define PDDP_NOMINAL_START
+#include "mpc_advance_body.inc"
+#undef PDDP_NOMINAL_START
+#undef PDDP_PLANT_STEPPED
+#undef PDDP_PLANT_STATE
+#undef PDDP_TERMINAL_GOALS
+#undef PDDP_PLANT_OF_B
+#undef PDDP_PROBLEM_OF_B
+#undef PDDP_TABLE
 }
 
 template <typename T, int MODEL>
 static int launch_mpc_advance(const pddp_problem& p, MpcAdvanceArgs<T> a,
                               hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  const dim3 blocks((a.B + kWave - 1) / kWave);
-  PDDP_LAUNCH((mpc_advance_kernel<T, MODEL>), blocks, dim3(kWave), 0, st, P,
-              a);
+  PDDP_LAUNCH((mpc_advance_kernel<T, MODEL>), advance_blocks(a), dim3(kWave),
+              0, st, P, a);
+  return launch_status();
+}
+// (With<Args, RefArgs<T>>, problem_args.hpp: an argument block and the
+// reference of its launch)
+template <typename T, int MODEL>
+static int launch_track_advance(const pddp_problem& p,
+                                With<TrackAdvanceArgs<T>, RefArgs<T>> w,
+                                hipStream_t st) {
+  const ProblemT<T> P = convert_problem<T>(p);
+  PDDP_LAUNCH((track_mpc_advance_kernel<T, MODEL>), advance_blocks(w.a),
+              dim3(kWave), 0, st, P, w.a, w.x);
   return launch_status();
 }
 
 template <typename T>
-static int mpc_advance_impl(const pddp_problem* p, const T* table, int B,
-                            int N, int TT, int t, T* z0, T* U, T* Z,
-                            const T* u_min, const T* u_max, const T* plant,
-                            const T* disturbance, const uint8_t* mask, T* Xlog,
-                            T* Ulog, T* Jcl, int32_t* state_log,
-                            uint8_t* live_log, double* mu, double* delta,
-                            int32_t* state, int32_t* iter, uint8_t* active,
-                            uint8_t* fresh, int32_t* n_live, void* stream) {
-  if (B <= 0 || N <= 0 || TT <= 0 || t < 0 || t >= TT || !z0 || !U || !Z ||
-      !Xlog || !Ulog || !Jcl || !state_log || !live_log || !mu || !delta ||
-      !state || !iter || !active || !fresh)
+static int mpc_advance_impl(const pddp_problem* p, MpcAdvanceArgs<T> a,
+                            void* stream) {
+  if (!advance_args_ok(a)) return PDDP_E_BADARG;
+  if (int rc = check_problem(p)) return rc;
+  PDDP_DISPATCH_MODEL(launch_mpc_advance, T, p, a, (hipStream_t)stream)
+}
+
+template <typename T>
+static int track_advance_impl(const pddp_problem* p, const T* table,
+                              const T* ref, int ref_len, int ref_t0,
+                              TrackAdvanceArgs<T> a, void* stream) {
+  With<TrackAdvanceArgs<T>, RefArgs<T>> w{a, {}};
+  if (!advance_args_ok(a) || !ref_args(table, ref, ref_len, ref_t0, &w.x))
     return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
-  MpcAdvanceArgs<T> a{B,     N,     TT,        t,        table, plant,
-                      z0,    U,     Z,         u_min,    u_max, disturbance,
-                      mask,  Xlog,  Ulog,      Jcl,      state_log, live_log,
-                      mu,    delta, state,     iter,     active, fresh,
-                      n_live};
-  PDDP_DISPATCH_MODEL(launch_mpc_advance, T, p, a, (hipStream_t)stream)
+  PDDP_DISPATCH_MODEL(launch_track_advance, T, p, w, (hipStream_t)stream)
 }
 
 }  // namespace pddp
 
 extern "C" {
 
-#define PDDP_MPC_ADVANCE_ENTRY_POINT(SUF, T)                                   \
-  int pddp_mpc_advance_##SUF(                                                  \
-      const pddp_problem* p, const T* table, int B, int N, int TT, int t,      \
-      T* z0, T* U, T* Z, const T* u_min, const T* u_max, const T* plant,       \
-      const T* disturbance, const uint8_t* mask, T* Xlog, T* Ulog, T* Jcl,     \
-      int32_t* state_log, uint8_t* live_log, double* mu, double* delta,        \
-      int32_t* state, int32_t* iter, uint8_t* active, uint8_t* fresh,          \
-      int32_t* n_live, void* stream) {                                         \
-    return pddp::mpc_advance_impl<T>(                                          \
-        p, table, B, N, TT, t, z0, U, Z, u_min, u_max, plant, disturbance,     \
-        mask, Xlog, Ulog, Jcl, state_log, live_log, mu, delta, state, iter,    \
-        active, fresh, n_live, stream);                                        \
+#define PDDP_MPC_ADVANCE_ENTRY_POINTS(SUF, T)                                  \
+  int pddp_mpc_advance_##SUF(const pddp_problem* p, const T* table,            \
+                             PDDP_ADVANCE_STEP_PARAMS(T),                      \
+                             PDDP_ADVANCE_LOG_PARAMS(T)) {                     \
+    return pddp::mpc_advance_impl<T>(p, {PDDP_MPC_ADVANCE_ARGS}, stream);      \
+  }                                                                            \
+  int pddp_mpc_advance_track_##SUF(                                            \
+      const pddp_problem* p, const T* table, const T* ref, int ref_len,        \
+      int ref_t0, PDDP_ADVANCE_STEP_PARAMS(T), PDDP_ADVANCE_LOG_PARAMS(T)) {   \
+    return pddp::track_advance_impl<T>(p, table, ref, ref_len, ref_t0,         \
+                                       {PDDP_TRACK_ADVANCE_ARGS}, stream);     \
   }
 
-PDDP_MPC_ADVANCE_ENTRY_POINT(f32, float)
-PDDP_MPC_ADVANCE_ENTRY_POINT(f64, double)
-#undef PDDP_MPC_ADVANCE_ENTRY_POINT
+PDDP_MPC_ADVANCE_ENTRY_POINTS(f32, float)
+PDDP_MPC_ADVANCE_ENTRY_POINTS(f64, double)
+#undef PDDP_MPC_ADVANCE_ENTRY_POINTS
+#undef PDDP_MPC_ADVANCE_ARGS
+#undef PDDP_TRACK_ADVANCE_ARGS
+#undef PDDP_ADVANCE_LOG_PARAMS
+#undef PDDP_ADVANCE_STEP_PARAMS
 
 }  // extern "C"

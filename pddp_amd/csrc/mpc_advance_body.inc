@@ -1,6 +1,7 @@
 // mpc_advance_body.inc - the hand-over between two MPC control steps of one
-// trajectory by its lane: the text of mpc_advance_kernel (mpc_advance.hip) and
-// track_mpc_advance_kernel (tracking.hip).  PDDP_PROBLEM_OF_B declares `P`, the
+// trajectory by its lane: the text of mpc_advance_kernel and
+// track_mpc_advance_kernel (mpc_advance.hip).  The goal hooks are one text,
+// mpc_advance_goal_hooks.inc: PDDP_PROBLEM_OF_B declares `P`, the
 // controller's model (its goals are read only where PDDP_PLANT_OF_B copies
 // them); PDDP_PLANT_OF_B declares `Pl`, the plant of row b with the goals the
 // step's stage cost is logged under; PDDP_TERMINAL_GOALS, at t == T - 1, is

@@ -1,7 +1,7 @@
 // mpc_advance_noise.hip - the hand-over between two control steps of a
 // receding-horizon (MPC) trial under process and measurement noise drawn on the
-// device: pddp_mpc_advance_*'s launch (mpc_advance.hip), with or without the
-// goal per time step of pddp_mpc_advance_track_* (tracking.hip), with
+// device: pddp_mpc_advance_*'s launch, with or without the goal per time step
+// of pddp_mpc_advance_track_* (both mpc_advance.hip), with
 //
 //   x_{t+1} = plant(x_t, u_t) + disturbance + w_std (.) w_t
 //   y_{t+1} = x_{t+1} + v_std (.) v_{t+1}     what the controller re-plans from
@@ -14,47 +14,24 @@
 // plant's state lives in `x_true`; z0 and Z[:, 0] hold what the controller
 // sees.  The trial's logs and its cost are the true states'.
 //
-// A translation unit of its own (csrc/Makefile: FLAGS_mpc_advance_noise).  The
-// kernel is mpc_advance_kernel's text, mpc_advance_body.inc, with the draws at
-// its three state hooks; PROC / OBS / TRACK are compile-time, so that a launch
-// carries the instructions of what it asked for and of nothing else
-// (DESIGN.md 3.4j).  pddp_mpc_observe_* forms the first observation of a trial
-// through the device function the hand-over forms every later one with.
+// A translation unit of its own (csrc/Makefile: FLAGS_mpc_advance_noise, whose
+// scheduling flag is not mpc_advance.hip's).  The kernel is
+// mpc_advance_kernel's text, mpc_advance_body.inc, and argument block, with
+// the goal hooks of mpc_advance_goal_hooks.inc and the draws at the three state
+// hooks; PROC / OBS / TRACK are compile-time, so that a launch carries the
+// instructions of what it asked for and of nothing else.
+// pddp_mpc_observe_* forms the first observation of a trial through the device
+// function the hand-over forms every later one with.
 #include <climits>
 #include <type_traits>
 #include "models.hpp"
 #include "problem_args.hpp"
 #include "model_params.hpp"
 #include "closed_loop_draws.hpp"
+#include "mpc_advance_args.hpp"
 #include "ref_args.hpp"
 
 namespace pddp {
-
-template <typename T>
-struct NoisyAdvanceArgs {
-  int B, N, T_, t;   // control step t of T_
-  const T* table;    // [B][PDDP_BATCH_ROW] or NULL: the controller's model
-  const T* plant;    // [B][PDDP_BATCH_ROW] or NULL: the controller's model
-  T* z0;             // [B][n]       in: y_t, out: y_{t+1}  (!OBS: x_t, x_{t+1})
-  T* U;              // [B][N][m]    shifted in place (unclamped)
-  T* Z;              // [B][N+1][n]  out: the rollout of the shifted nominal
-  const T* u_min;
-  const T* u_max;
-  const T* disturbance;  // [B][T_][n] or NULL
-  const uint8_t* mask;   // [B] or NULL
-  T* Xlog;               // [B][T_+1][n]
-  T* Ulog;               // [B][T_][m]
-  T* Jcl;                // [B]
-  int32_t* state_log;    // [B][T_]
-  uint8_t* live_log;     // [B][T_]
-  double* mu;
-  double* delta;
-  int32_t* state;
-  int32_t* iter;
-  uint8_t* active;
-  uint8_t* fresh;
-  int32_t* n_live;  // [PDDP_LIVE_SHARDS] or NULL
-};
 
 // the noise of one control step of a launch of trials
 template <typename T>
@@ -67,50 +44,16 @@ struct TrialNoise {
   T* Ylog;    // [B][T_+1][n]   OBS, nullable: y_{t+1} at row t + 1
 };
 
-// (tracking.hip's statement, for its reason)
-#define PDDP_COPY(K, dst, src) \
-  _Pragma("unroll") for (int i = 0; i < (K); ++i)(dst)[i] = (src)[i];
-
 // Mapping, ownership and the n_live shards: mpc_advance_kernel's.  The key of
 // the draws (`seed`) is a kernel argument and the step a scalar: both stay in
 // scalar registers; the rollout index is the lane's counter word.  The noise
 // levels are the launch's (scalar loads).
 template <typename T, int MODEL, bool PROC, bool OBS, bool TRACK>
 __global__ __launch_bounds__(kWave) void mpc_advance_noisy_kernel(
-    ProblemT<T> shared, NoisyAdvanceArgs<T> a, TrialNoise<T> noise,
+    ProblemT<T> shared, MpcAdvanceArgs<T> a, TrialNoise<T> noise,
     RefArgs<T> goals) {
-// the controller's model: a tracked one takes its goals step by step in the
-// rounds, the hand-over's rollout reads none
-#define PDDP_PROBLEM_OF_B                                                      \
-  ProblemT<T> P = shared;                                                      \
-  if (a.table != nullptr) {                                                    \
-    if constexpr (TRACK)                                                       \
-      write_params<T, MODEL>(P, a.table + (size_t)b * PDDP_BATCH_ROW);         \
-    else                                                                       \
-      write_params_and_goals<T, MODEL>(P,                                      \
-                                       a.table + (size_t)b * PDDP_BATCH_ROW);  \
-  }
-// the plant with the goals the stage cost is logged under: the plant row's,
-// or reference row ref_t0's (the plant row then supplies parameters only)
-#define PDDP_PLANT_OF_B                                                        \
-  ProblemT<T> Pl = P;                                                          \
-  if (a.plant != nullptr) {                                                    \
-    if constexpr (TRACK)                                                       \
-      write_params<T, MODEL>(Pl, a.plant + (size_t)b * PDDP_BATCH_ROW);        \
-    else                                                                       \
-      write_params_and_goals<T, MODEL>(Pl,                                     \
-                                       a.plant + (size_t)b * PDDP_BATCH_ROW);  \
-  }                                                                            \
-  if constexpr (TRACK) {                                                       \
-    const T* row = ref_row(goals, b, 0);                                       \
-    PDDP_COPY(D::na, Pl.goal, row + PDDP_REF_X_GOAL)                           \
-    PDDP_COPY(m, Pl.ugoal, row + PDDP_REF_U_GOAL)                              \
-  }
-#define PDDP_TERMINAL_GOALS                                                    \
-  if constexpr (TRACK) {                                                       \
-    const T* row1 = ref_row(goals, b, 1);                                      \
-    PDDP_COPY(D::na, Pl.goal, row1 + PDDP_REF_X_GOAL)                          \
-  }
+#define PDDP_TABLE a.table
+#include "mpc_advance_goal_hooks.inc"
 // the plant is at x_true, not at what the controller saw.  The draws of the
 // step depend on no state: they are made here, ahead of the dependent chain
 // and of the two problem copies, and wait as unit normals in vector registers.
@@ -144,9 +87,8 @@ __global__ __launch_bounds__(kWave) void mpc_advance_noisy_kernel(
 #undef PDDP_TERMINAL_GOALS
 #undef PDDP_PLANT_OF_B
 #undef PDDP_PROBLEM_OF_B
+#undef PDDP_TABLE
 }
-
-#undef PDDP_COPY
 
 // y = x + v_std (.) v(r, step): one lane per trajectory, the hand-over's
 // device function (draw_added), so that the first observation of a trial obeys
@@ -176,7 +118,7 @@ __global__ __launch_bounds__(kWave) void mpc_observe_kernel(ObserveArgs<T> a) {
 
 template <typename T>
 struct NoisyAdvanceLaunch {
-  NoisyAdvanceArgs<T> a;
+  MpcAdvanceArgs<T> a;
   TrialNoise<T> noise;
   RefArgs<T> r;
   bool track;
@@ -186,7 +128,7 @@ template <typename T, int MODEL>
 static int launch_noisy_advance(const pddp_problem& p, NoisyAdvanceLaunch<T> w,
                                 hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  const dim3 blocks((w.a.B + kWave - 1) / kWave);
+  const dim3 blocks = advance_blocks(w.a);
 #define PDDP_NOISY(PROC, OBS)                                                  \
   do {                                                                         \
     if (w.track)                                                               \
@@ -206,35 +148,22 @@ static int launch_noisy_advance(const pddp_problem& p, NoisyAdvanceLaunch<T> w,
   return launch_status();
 }
 
+// `noise` as the entry point got it: `step` holds step_offset, x_true and Ylog
+// are taken as given.
 template <typename T>
-static int noisy_advance_impl(
-    const pddp_problem* p, const T* table, const T* ref, int ref_len,
-    int ref_t0, int B, int N, int TT, int t, T* z0, T* U, T* Z, const T* u_min,
-    const T* u_max, const T* plant, const T* disturbance, const T* w_std,
-    const T* v_std, uint64_t seed, uint64_t rollout_offset, int step_offset,
-    T* x_true, T* Ylog, const uint8_t* mask, T* Xlog, T* Ulog, T* Jcl,
-    int32_t* state_log, uint8_t* live_log, double* mu, double* delta,
-    int32_t* state, int32_t* iter, uint8_t* active, uint8_t* fresh,
-    int32_t* n_live, void* stream) {
-  if (B <= 0 || N <= 0 || TT <= 0 || t < 0 || t >= TT || !z0 || !U || !Z ||
-      !Xlog || !Ulog || !Jcl || !state_log || !live_log || !mu || !delta ||
-      !state || !iter || !active || !fresh)
-    return PDDP_E_BADARG;
+static int noisy_advance_impl(const pddp_problem* p, MpcAdvanceArgs<T> a,
+                              TrialNoise<T> noise, const T* ref, int ref_len,
+                              int ref_t0, void* stream) {
+  if (!advance_args_ok(a)) return PDDP_E_BADARG;
   // (no noise at all is pddp_mpc_advance[_track]_*'s launch)
-  if (w_std == nullptr && v_std == nullptr) return PDDP_E_BADARG;
-  if (v_std != nullptr && x_true == nullptr) return PDDP_E_BADARG;
+  if (noise.w_std == nullptr && noise.v_std == nullptr) return PDDP_E_BADARG;
+  if (noise.v_std != nullptr && noise.x_true == nullptr) return PDDP_E_BADARG;
   // (step_offset + t + 1 is a counter word of the draws: an int)
-  if (step_offset < 0 || step_offset > INT_MAX - TT) return PDDP_E_BADARG;
-  NoisyAdvanceLaunch<T> w{
-      {B,     N,     TT,   t,    table, plant,     z0,       U,
-       Z,     u_min, u_max, disturbance, mask,     Xlog,     Ulog,
-       Jcl,   state_log,   live_log,    mu,        delta,    state,
-       iter,  active, fresh, n_live},
-      {w_std, v_std, seed, rollout_offset, step_offset + t,
-       v_std != nullptr ? x_true : nullptr, v_std != nullptr ? Ylog : nullptr},
-      {table, nullptr, 1, 0},
-      ref != nullptr};
-  if (ref != nullptr && !ref_args(table, ref, ref_len, ref_t0, &w.r))
+  if (noise.step < 0 || noise.step > INT_MAX - a.T_) return PDDP_E_BADARG;
+  noise.step += a.t;
+  if (noise.v_std == nullptr) noise.x_true = noise.Ylog = nullptr;
+  NoisyAdvanceLaunch<T> w{a, noise, {a.table, nullptr, 1, 0}, ref != nullptr};
+  if (ref != nullptr && !ref_args(a.table, ref, ref_len, ref_t0, &w.r))
     return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
   PDDP_DISPATCH_MODEL(launch_noisy_advance, T, p, w, (hipStream_t)stream)
@@ -275,18 +204,13 @@ extern "C" {
 #define PDDP_MPC_NOISE_ENTRY_POINTS(SUF, T)                                    \
   int pddp_mpc_advance_noisy_##SUF(                                            \
       const pddp_problem* p, const T* table, const T* ref, int ref_len,        \
-      int ref_t0, int B, int N, int TT, int t, T* z0, T* U, T* Z,              \
-      const T* u_min, const T* u_max, const T* plant, const T* disturbance,    \
-      const T* w_std, const T* v_std, uint64_t seed, uint64_t rollout_offset,  \
-      int step_offset, T* x_true, T* Ylog, const uint8_t* mask, T* Xlog,       \
-      T* Ulog, T* Jcl, int32_t* state_log, uint8_t* live_log, double* mu,      \
-      double* delta, int32_t* state, int32_t* iter, uint8_t* active,           \
-      uint8_t* fresh, int32_t* n_live, void* stream) {                         \
+      int ref_t0, PDDP_ADVANCE_STEP_PARAMS(T), const T* w_std,                 \
+      const T* v_std, uint64_t seed, uint64_t rollout_offset,                  \
+      int step_offset, T* x_true, T* Ylog, PDDP_ADVANCE_LOG_PARAMS(T)) {       \
     return pddp::noisy_advance_impl<T>(                                        \
-        p, table, ref, ref_len, ref_t0, B, N, TT, t, z0, U, Z, u_min, u_max,   \
-        plant, disturbance, w_std, v_std, seed, rollout_offset, step_offset,   \
-        x_true, Ylog, mask, Xlog, Ulog, Jcl, state_log, live_log, mu, delta,   \
-        state, iter, active, fresh, n_live, stream);                           \
+        p, {PDDP_MPC_ADVANCE_ARGS},                                            \
+        {w_std, v_std, seed, rollout_offset, step_offset, x_true, Ylog}, ref,  \
+        ref_len, ref_t0, stream);                                              \
   }                                                                            \
   int pddp_mpc_observe_##SUF(int B, int n, const T* x, const T* v_std,         \
                              uint64_t seed, uint64_t rollout_offset, int step, \
@@ -298,5 +222,9 @@ extern "C" {
 PDDP_MPC_NOISE_ENTRY_POINTS(f32, float)
 PDDP_MPC_NOISE_ENTRY_POINTS(f64, double)
 #undef PDDP_MPC_NOISE_ENTRY_POINTS
+#undef PDDP_MPC_ADVANCE_ARGS
+#undef PDDP_TRACK_ADVANCE_ARGS
+#undef PDDP_ADVANCE_LOG_PARAMS
+#undef PDDP_ADVANCE_STEP_PARAMS
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // ref_args.hpp - where the kernels with a goal PER TIME STEP take their goals
-// from: what tracking.hip and closed_loop_track.hip share.  The layout of `ref`
-// is include/pddp_hip.h's (PDDP_REF_*); DESIGN.md 3.4e.
+// from: what tracking.hip, closed_loop.hip, mpc_advance.hip and
+// mpc_advance_noise.hip share.  The layout of `ref` is include/pddp_hip.h's
+// (PDDP_REF_*); DESIGN.md 3.4e.
 #pragma once
 
 #include "pddp_common.hpp"
@@ -15,6 +16,14 @@ struct RefArgs {
   const T* ref;    // [B][ref_len][PDDP_REF_ROW]
   int ref_len, ref_t0;
 };
+
+// A statement, not a function (problem_kernels.hip's note: the same statements
+// inlined from a function reach the optimiser in another order - here too, the
+// kernels then differ in their mul / add / fma mix): K words of `src` copied to
+// `dst`, for the goals at PDDP_REF_X_GOAL (na words) and PDDP_REF_U_GOAL (m
+// words) of a reference row.
+#define PDDP_COPY(K, dst, src) \
+  _Pragma("unroll") for (int i = 0; i < (K); ++i)(dst)[i] = (src)[i];
 
 template <typename T>
 PDDP_DEV const T* ref_row(const RefArgs<T>& g, int b, int i) {

@@ -1,6 +1,8 @@
-// tracking.hip - reference tracking: the derivative records, the line search
-// and the MPC hand-over with a goal PER TIME STEP (the pddp_*_track_* entry
-// points, ILQRSolver.set_reference).
+// tracking.hip - reference tracking: the derivative records and the line
+// search with a goal PER TIME STEP (pddp_derivs_track_*,
+// pddp_line_search_track_*, ILQRSolver.set_reference).  The MPC hand-over and
+// the closed-loop rollouts along a reference stand with their operations:
+// mpc_advance.hip, closed_loop.hip.
 //
 //   `ref` [B][ref_len][PDDP_REF_ROW]: x_goal (augmented coordinates) and u_goal
 //   of trajectory b at every step of its reference (include/pddp_hip.h).
@@ -15,12 +17,11 @@
 // accept; only the integer `ref_t0` moves from one MPC control step to the
 // next.
 //
-// A translation unit of its own (csrc/Makefile: FLAGS_tracking).  Its three
-// loops are the included texts of problem_kernels.hip and mpc_advance.hip -
-// derivs_body.inc, line_search_body.inc, mpc_advance_body.inc - with the goals
-// of `P` taken from a reference row at the texts' hook points, where those
-// kernels read one problem; the row writer is model_params.hpp's
-// (DESIGN.md 3.4f).
+// A translation unit of its own (csrc/Makefile: FLAGS_tracking).  Its two
+// loops are the included texts of problem_kernels.hip - derivs_body.inc,
+// line_search_body.inc - with the goals of `P` taken from a reference row
+// (PDDP_COPY, ref_args.hpp) at the texts' hook points, where those kernels read
+// one problem; the row writer is model_params.hpp's.
 #include <type_traits>
 #include "models.hpp"
 #include "problem_args.hpp"
@@ -29,15 +30,7 @@
 
 namespace pddp {
 
-// A statement, not a function (problem_kernels.hip's note: the same statements
-// inlined from a function reach the optimiser in another order - here too, the
-// kernels then differ in their mul / add / fma mix): K words of `src` copied to
-// `dst`, for the goals at PDDP_REF_X_GOAL (na words) and PDDP_REF_U_GOAL (m
-// words) of a reference row.
-#define PDDP_COPY(K, dst, src) \
-  _Pragma("unroll") for (int i = 0; i < (K); ++i)(dst)[i] = (src)[i];
-
-// For the three kernels below: `P` is the shared problem with the model
+// For the two kernels below: `P` is the shared problem with the model
 // parameters of row b of the table, where one is given, written over it (the
 // goals come step by step), and the texts' PDDP_GOALS(point) is the kernel's
 // PDDP_GOALS_<point>.
@@ -98,67 +91,8 @@ __global__ __launch_bounds__(kWave) void track_line_search_kernel(
 #undef PDDP_GOALS_TAKE_FIRST
 }
 
-// --------------------------------------------------------------------------
-// the hand-over between two control steps of an MPC trial (mpc_advance_kernel,
-// one lane per trajectory, mpc_advance_body.inc): the stage cost logged at
-// control step t is taken under reference row ref_t0, the terminal cost at
-// t == T - 1 under row ref_t0 + 1 (both clamped).  The plant row supplies the
-// parameters only.  Dynamics, shift, rollout and re-arm read no goal.
-// --------------------------------------------------------------------------
-
-template <typename T>
-struct TrackAdvanceArgs {
-  int B, N, T_, t;   // control step t of T_
-  const T* plant;    // [B][PDDP_BATCH_ROW] or NULL: the plant's parameters
-  T* z0;             // [B][n]       in: x_t, out: x_{t+1}
-  T* U;              // [B][N][m]    shifted in place (unclamped)
-  T* Z;              // [B][N+1][n]  out: the rollout of the shifted nominal
-  const T* u_min;
-  const T* u_max;
-  const T* disturbance;  // [B][T_][n] or NULL
-  const uint8_t* mask;   // [B] or NULL
-  T* Xlog;               // [B][T_+1][n]
-  T* Ulog;               // [B][T_][m]
-  T* Jcl;                // [B]
-  int32_t* state_log;    // [B][T_]
-  uint8_t* live_log;     // [B][T_]
-  double* mu;
-  double* delta;
-  int32_t* state;
-  int32_t* iter;
-  uint8_t* active;
-  uint8_t* fresh;
-  int32_t* n_live;  // [PDDP_LIVE_SHARDS] or NULL
-};
-
-template <typename T, int MODEL>
-__global__ __launch_bounds__(kWave) void track_mpc_advance_kernel(
-    ProblemT<T> shared, TrackAdvanceArgs<T> a, RefArgs<T> goals) {
-#define PDDP_PLANT_OF_B                                                        \
-  ProblemT<T> Pl = P;                                                          \
-  if (a.plant != nullptr)                                                      \
-    write_params<T, MODEL>(Pl, a.plant + (size_t)b * PDDP_BATCH_ROW);          \
-  const T* row = ref_row(goals, b, 0);                                         \
-  PDDP_COPY(D::na, Pl.goal, row + PDDP_REF_X_GOAL)                             \
-  PDDP_COPY(m, Pl.ugoal, row + PDDP_REF_U_GOAL)
-#define PDDP_TERMINAL_GOALS                                                    \
-  const T* row1 = ref_row(goals, b, 1);                                        \
-  PDDP_COPY(D::na, Pl.goal, row1 + PDDP_REF_X_GOAL)
-// (no noise: z0 is the plant's state and the controller's)
-#define PDDP_PLANT_STATE
-#define PDDP_PLANT_STEPPED
-#define PDDP_NOMINAL_START
-#include "mpc_advance_body.inc"
-#undef PDDP_NOMINAL_START
-#undef PDDP_PLANT_STEPPED
-#undef PDDP_PLANT_STATE
-#undef PDDP_TERMINAL_GOALS
-#undef PDDP_PLANT_OF_B
-}
-
 #undef PDDP_GOALS
 #undef PDDP_PROBLEM_OF_B
-#undef PDDP_COPY
 
 // --------------------------------------------------------------------------
 // launchers and entry points
@@ -182,16 +116,6 @@ static int launch_track_line_search(const pddp_problem& p,
   const ProblemT<T> P = convert_problem<T>(p);
   PDDP_LAUNCH((track_line_search_kernel<T, MODEL>), search_lanes(w.a),
               dim3(kWave), 0, st, P, w.a, w.x);
-  return launch_status();
-}
-template <typename T, int MODEL>
-static int launch_track_advance(const pddp_problem& p,
-                                With<TrackAdvanceArgs<T>, RefArgs<T>> w,
-                                hipStream_t st) {
-  const ProblemT<T> P = convert_problem<T>(p);
-  const dim3 blocks((w.a.B + kWave - 1) / kWave);
-  PDDP_LAUNCH((track_mpc_advance_kernel<T, MODEL>), blocks, dim3(kWave), 0, st,
-              P, w.a, w.x);
   return launch_status();
 }
 
@@ -228,31 +152,6 @@ static int track_line_search_impl(const pddp_problem* p, const T* table,
   PDDP_DISPATCH_MODEL(launch_track_line_search, T, p, w, (hipStream_t)stream)
 }
 
-template <typename T>
-static int track_advance_impl(const pddp_problem* p, const T* table,
-                              const T* ref, int ref_len, int ref_t0, int B,
-                              int N, int TT, int t, T* z0, T* U, T* Z,
-                              const T* u_min, const T* u_max, const T* plant,
-                              const T* disturbance, const uint8_t* mask,
-                              T* Xlog, T* Ulog, T* Jcl, int32_t* state_log,
-                              uint8_t* live_log, double* mu, double* delta,
-                              int32_t* state, int32_t* iter, uint8_t* active,
-                              uint8_t* fresh, int32_t* n_live, void* stream) {
-  With<TrackAdvanceArgs<T>, RefArgs<T>> w{
-      {B,     N,      TT,        t,        plant, z0,    U,
-       Z,     u_min,  u_max,     disturbance,     mask,  Xlog,
-       Ulog,  Jcl,    state_log, live_log, mu,    delta, state,
-       iter,  active, fresh,     n_live},
-      {}};
-  if (B <= 0 || N <= 0 || TT <= 0 || t < 0 || t >= TT || !z0 || !U || !Z ||
-      !Xlog || !Ulog || !Jcl || !state_log || !live_log || !mu || !delta ||
-      !state || !iter || !active || !fresh ||
-      !ref_args(table, ref, ref_len, ref_t0, &w.x))
-    return PDDP_E_BADARG;
-  if (int rc = check_problem(p)) return rc;
-  PDDP_DISPATCH_MODEL(launch_track_advance, T, p, w, (hipStream_t)stream)
-}
-
 }  // namespace pddp
 
 extern "C" {
@@ -275,19 +174,6 @@ extern "C" {
     return pddp::track_line_search_impl<T>(                                    \
         p, table, ref, ref_len, ref_t0, B, N, A, Z, U, gains, alphas, u_min,   \
         u_max, active, bwd_status, Zc, Uc, Jc, stream);                        \
-  }                                                                            \
-  int pddp_mpc_advance_track_##SUF(                                            \
-      const pddp_problem* p, const T* table, const T* ref, int ref_len,        \
-      int ref_t0, int B, int N, int TT, int t, T* z0, T* U, T* Z,              \
-      const T* u_min, const T* u_max, const T* plant, const T* disturbance,    \
-      const uint8_t* mask, T* Xlog, T* Ulog, T* Jcl, int32_t* state_log,       \
-      uint8_t* live_log, double* mu, double* delta, int32_t* state,            \
-      int32_t* iter, uint8_t* active, uint8_t* fresh, int32_t* n_live,         \
-      void* stream) {                                                          \
-    return pddp::track_advance_impl<T>(                                        \
-        p, table, ref, ref_len, ref_t0, B, N, TT, t, z0, U, Z, u_min, u_max,   \
-        plant, disturbance, mask, Xlog, Ulog, Jcl, state_log, live_log, mu,    \
-        delta, state, iter, active, fresh, n_live, stream);                    \
   }
 
 PDDP_TRACK_ENTRY_POINTS(f32, float)

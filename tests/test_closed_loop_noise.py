@@ -1,6 +1,6 @@
 """Closed-loop evaluation under process and measurement noise drawn on the
 device (pddp_closed_loop_noisy_*, pddp_closed_loop_draws_*,
-csrc/closed_loop_noise.hip, ILQRSolver.closed_loop(process_std=, obs_std=),
+csrc/closed_loop.hip, ILQRSolver.closed_loop(process_std=, obs_std=),
 ILQRSolver.closed_loop_draws).
 
 The draws are defined in include/pddp_hip.h; `model_draws` below restates them

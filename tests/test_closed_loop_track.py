@@ -1,5 +1,5 @@
 """Closed-loop evaluation ALONG A REFERENCE (pddp_closed_loop_track_*,
-csrc/closed_loop_track.hip, ILQRSolver.closed_loop(track=True)): the rollouts
+csrc/closed_loop.hip, ILQRSolver.closed_loop(track=True)): the rollouts
 of pddp_closed_loop_* / pddp_closed_loop_noisy_* with the stage cost of step t
 taken under reference row min(ref_t0 + t, ref_len - 1) of the trajectory and
 the terminal cost under row min(ref_t0 + N, ref_len - 1).

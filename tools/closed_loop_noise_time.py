@@ -1,6 +1,6 @@
 """What noise drawn inside the closed-loop rollouts costs
 (ILQRSolver.closed_loop(process_std=, obs_std=), pddp_closed_loop_noisy_f32 of
-csrc/closed_loop_noise.hip) next to the noise-free launch and next to merely
+csrc/closed_loop.hip) next to the noise-free launch and next to merely
 filling the tensor the alternative design - a disturbance argument - would have
 read: cartpole f32, 4096 trajectories, horizon 100, bounded, the gains of one
 sweep at reg = 1, every plant row the shared problem, starts Z[b][0] +

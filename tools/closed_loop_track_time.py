@@ -1,6 +1,6 @@
 """What costing the closed-loop rollouts along a reference costs
 (ILQRSolver.closed_loop(track=True), pddp_closed_loop_track_f32 of
-csrc/closed_loop_track.hip) next to the launches with one goal per rollout:
+csrc/closed_loop.hip) next to the launches with one goal per rollout:
 cartpole f32, 4096 trajectories, horizon 100, bounded, the gains of one sweep
 at reg = 1, every plant row the shared problem, starts Z[b][0] +
 U(-0.05, 0.05), S = 16 and 64, costs only and with the trajectories kept.

@@ -1,7 +1,8 @@
 """What a goal per time step costs (ILQRSolver.set_reference, the track_*
-kernels of csrc/tracking.hip): cartpole f32, 4096 trajectories, horizon 100,
-bounded, the fit's ten step sizes.  Every row of the table is the shared
-problem and every row of the reference its goals, so both legs of a pair do
+kernels of csrc/tracking.hip and csrc/mpc_advance.hip): cartpole f32, 4096
+trajectories, horizon 100, bounded, the fit's ten step sizes.  Every row of
+the table is the shared problem and every row of the reference its goals, so
+both legs of a pair do
 the same work on the same buffers.  One process, the legs of a pair
 alternating launch by launch, events attached to the dispatch itself
 (pddp_attach_events):
