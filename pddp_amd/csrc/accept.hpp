@@ -49,6 +49,24 @@ struct AcceptIn {
   double mu, delta;
   T J_opt;
 };
+
+// The state a trajectory carries from one round to the next, as the global
+// arrays of AcceptArgs hold it (same types: the schedule's arithmetic is in
+// double).  The one-launch round with several rounds per launch
+// (round_n4_body.hpp) keeps one per trajectory in LDS: the rounds after the
+// launch's first read it there instead of asking L2 for what their own
+// workgroup wrote a barrier ago - a load that, queued behind the last
+// round's stores, waits for every one of them.  The global arrays are written
+// as before.
+struct RoundState {
+  double mu, delta;
+  float J_opt;
+  int32_t iter;
+  uint8_t active, fresh;
+  uint8_t pad_[6];
+};
+static_assert(sizeof(RoundState) == 32, "");
+
 template <typename T>
 PDDP_DEV AcceptIn<T> accept_load(const AcceptArgs<T>& a, int b) {
   AcceptIn<T> in;
@@ -57,6 +75,17 @@ PDDP_DEV AcceptIn<T> accept_load(const AcceptArgs<T>& a, int b) {
   in.delta = a.delta[b];
   in.J_opt = a.J_opt[b];
   in.iter = a.iter[b];
+  return in;
+}
+// (the same from the round's record; the sweep's status is the caller's)
+template <typename T>
+PDDP_DEV AcceptIn<T> accept_load(const RoundState& rs) {
+  AcceptIn<T> in;
+  in.bstat = 0;
+  in.mu = rs.mu;
+  in.delta = rs.delta;
+  in.J_opt = (T)rs.J_opt;
+  in.iter = rs.iter;
   return in;
 }
 
@@ -79,9 +108,11 @@ PDDP_DEV int argmin_first(const T* J, int A, T& Jm_out) {
 // One attempted trajectory: decides, writes mu / delta / state / J_opt / iter
 // and the masks of the next round.  Returns the accepted candidate, -1 when
 // the nominal stays; `fresh_out` = the nominal changed and the fit goes on.
-template <typename T>
+// REC: `rs` is the trajectory's record in LDS, written as well.
+template <typename T, bool REC = false>
 PDDP_DEV int accept_decide(const AcceptArgs<T>& a, int b, const AcceptIn<T>& in,
-                           int amin, T J_new, bool& fresh_out) {
+                           int amin, T J_new, bool& fresh_out,
+                           [[maybe_unused]] RoundState* rs = nullptr) {
   int amin_out = -1;
   double mu = in.mu, delta = in.delta;
   int st;
@@ -99,6 +130,7 @@ PDDP_DEV int accept_decide(const AcceptArgs<T>& a, int b, const AcceptIn<T>& in,
       const T rel = abs_(J_opt - J_new) / J_opt;
       st = (rel < (T)a.tol) ? PDDP_STATE_CONVERGED : PDDP_STATE_ACCEPTED;
       a.J_opt[b] = J_new;
+      if constexpr (REC) rs->J_opt = (float)J_new;
     } else {
       increase = true;
       st = PDDP_STATE_REJECTED;
@@ -119,12 +151,19 @@ PDDP_DEV int accept_decide(const AcceptArgs<T>& a, int b, const AcceptIn<T>& in,
   } else if (st == PDDP_STATE_ACCEPTED) {
     if (in.iter < a.n_iterations) {
       a.iter[b] = in.iter + 1;
+      if constexpr (REC) rs->iter = in.iter + 1;
       act = 1;
       fr = 1;
     }
   }
   a.active[b] = act;
   a.fresh[b] = fr;
+  if constexpr (REC) {
+    rs->mu = mu;
+    rs->delta = delta;
+    rs->active = act;
+    rs->fresh = fr;
+  }
   // sharded counter: 4096 adds on ONE word serialise at ~12 ns each (= 50 us)
   if (act && a.n_live != nullptr)
     atomicAdd(a.n_live + (b & (kLiveShards - 1)), 1);

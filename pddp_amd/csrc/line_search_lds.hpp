@@ -153,20 +153,25 @@ struct PreStaged {
   // launch: the next round's first records are made from them)
   T* carry_rows = nullptr;
 };
+// REC (PRE, several rounds per launch): `rs_wg` is the workgroup's records in
+// LDS (accept.hpp RoundState, [WPB * 4]) - the mask and the state machine's
+// inputs are read there, and its outputs go there as well as to global memory.
 template <typename T, int MODEL, bool FUSED, int WPB, int H, unsigned QM,
-          bool DENSE, bool PRE = false>
+          bool DENSE, bool PRE = false, bool REC = false>
 PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
                                    const LineSearchArgs<T> a,
                                    const AcceptArgs<T> c, T* rec, T* Lout,
                                    unsigned char* smem_raw,
                                    const PreStaged<T> pre,
-                                   const unsigned tid = threadIdx.x) {
+                                   const unsigned tid = threadIdx.x,
+                                   RoundState* rs_wg = nullptr) {
   using D = ModelDims<MODEL>;
   constexpr int n = D::n, m = D::m;
   constexpr int GS = m + m * n;
   static_assert(H == 1 || (H == 2 && FUSED), "");
   static_assert(!DENSE || (FUSED && H == 1), "");
   static_assert(!PRE || (FUSED && H == 2 && !DENSE), "");
+  static_assert(!REC || PRE, "");
   // rows of the staged gains / actions: [k, K] of a step next to one another
   // and the actions in a table of their own - or, PRE (round_n4.hip), one row
   // [k, K, u] per step (riccati_n4_elem.hpp lays it out: 8-byte reads)
@@ -221,8 +226,20 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
   const int b = b0 + grp;
   const bool exists = b < a.B;
   const int bc = exists ? b : a.B - 1;
-  const bool attempted =
-      exists && (a.active == nullptr || a.active[bc] != 0);
+  // (the record's address from a lane id the compiler cannot match with the
+  // sweep phase's: shared with it, the address stays in a register through
+  // the sweep's block of steps, the kernel's widest point)
+  [[maybe_unused]] RoundState* rs = nullptr;
+  if constexpr (REC) {
+    unsigned t_rs = tid;
+    asm("" : "+v"(t_rs));
+    rs = rs_wg + ((t_rs >> 6) % WPB) * 4 + ((t_rs & (kWave - 1)) >> 4);
+  }
+  bool attempted;
+  if constexpr (REC)
+    attempted = exists && rs->active != 0;
+  else
+    attempted = exists && (a.active == nullptr || a.active[bc] != 0);
   const bool run =
       attempted && ai < a.A &&
       (PRE ? pre.status == 0
@@ -250,7 +267,10 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
   AcceptIn<T> acc_in = {};
   if constexpr (FUSED) {
     if (attempted && ai == 0) {
-      acc_in = accept_load(c, b);
+      if constexpr (REC)
+        acc_in = accept_load<T>(*rs);
+      else
+        acc_in = accept_load(c, b);
       if constexpr (PRE) {
         acc_in.bstat = pre.status;
         acc_in.J_opt = pre.J_opt;
@@ -258,11 +278,15 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
     }
   }
   T Jmine = T(0);
+  // (PRE || ... below: round_n4.hip serves no horizon that does not fit the
+  // tail's short form, n4_nominal_plan - the long form is not compiled into
+  // its kernels)
   // (candidates dropped: see LineSearchArgs::drop_candidates)
   // (where the tail's short form applies: it reads the winner's compact rows)
   // (n <= 4: a second inlined copy of the larger models' step spills)
   const bool nocand = FUSED && n <= 4 && Lout == nullptr && rec != nullptr &&
-                      a.drop_candidates != 0 && N + 1 <= 16 * H * kTailRows;
+                      a.drop_candidates != 0 &&
+                      (PRE || N + 1 <= 16 * H * kTailRows);
   // One rollout of this lane's candidate (ilqr.py:677-723 + :764-791): states
   // to Zci (stride zstep per step), actions to Uci (stride ustep), the cost
   // returned.  A stride of zero makes the target a one-row scratch - the
@@ -271,7 +295,8 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
   // (the candidates' actions are only stored where something reads them: the
   // tail's short form re-evaluates the winner's)
   const bool store_uc = !(FUSED && n <= 6 && Lout == nullptr &&
-                          rec != nullptr && N + 1 <= 16 * H * kTailRows);
+                          rec != nullptr &&
+                          (PRE || N + 1 <= 16 * H * kTailRows));
   // (`cost`: std::true_type where the caller uses the returned cost)
   auto rollout = [&](T alpha, T* Zci, size_t zstep, T* Uci, size_t ustep,
                      auto cost) {
@@ -419,7 +444,8 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
     // nobody had written into the nominal - cartpole f32 horizons beyond
     // ~101, found by test_one_launch_round_equals_two_launches[16-127])
     const bool compact0 = FUSED && Lout == nullptr && rec != nullptr &&
-                          ai == 0 && n <= 6 && N + 1 <= 16 * H * kTailRows;
+                          ai == 0 && n <= 6 &&
+                          (PRE || N + 1 <= 16 * H * kTailRows);
     T* Zci = compact0 ? rec + (size_t)b * (N + 1) * n
                       : a.Zc + ((size_t)b * (N + 1) * a.A + ai) * n;
     T* Uci = a.Uc + ((size_t)b * N * a.A + ai) * m;
@@ -454,7 +480,7 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
     int amin_out = -1, fresh_i = 0;
     if (attempted && ai == 0 && hid == 0) {
       bool fr;
-      amin_out = accept_decide(c, b, acc_in, amin, J_new, fr);
+      amin_out = accept_decide<T, REC>(c, b, acc_in, amin, J_new, fr, rs);
       fresh_i = fr ? 1 : 0;
     }
     amin_out = __shfl(amin_out, lane & 48);
@@ -466,6 +492,17 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
     // are not contracted alike - and its cost, Jc, from the first time)
     if constexpr (n <= 4) {
       if (nocand && hid == 0 && __any(amin_out > 0)) {
+        if constexpr (PRE) {
+          // (the step size read, and waited for, on every path of this block:
+          // hoisted above the test and used below it only, a load is one the
+          // compiler waits for at the next write of its register)
+          T alpha_r = a.alphas[ai];
+          asm volatile("" : "+v"(alpha_r));
+          if (amin_out > 0 && ai == amin_out)
+            rollout(alpha_r, rec + (size_t)b * (N + 1) * n, (size_t)n,
+                    a.Uc + ((size_t)b * N * a.A + ai) * m, 0,
+                    std::false_type{});
+        } else
         if (amin_out > 0 && ai == amin_out)
           rollout(a.alphas[ai], rec + (size_t)b * (N + 1) * n, (size_t)n,
                   a.Uc + ((size_t)b * N * a.A + ai) * m, 0, std::false_type{});
@@ -510,7 +547,7 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
       const int t_first = ai + 16 * hid;  // rows t_first, t_first + 16 H, ...
       constexpr int KR = kTailRows;  // rows per lane the short form below
                                      // covers (`nocand` above knows it)
-      if (n <= 6 && Lout == nullptr && N + 1 <= 16 * H * KR) {
+      if (n <= 6 && Lout == nullptr && (PRE || N + 1 <= 16 * H * KR)) {
         // No records to write (the next sweep evaluates them): the tail is
         // the winner's rows - all of this lane's requested at once, one
         // memory latency instead of one per row - and the gains, which are
@@ -541,11 +578,10 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
         }
         const T* Gl = Gs;  // (the staged gains)
         if constexpr (PRE) {
-          // (rows of GST words in LDS, of GS in gains_acc)
-          for (int t = ai + 16 * hid; t < N; t += 16 * H) {
-#pragma unroll
-            for (int j = 0; j < GS; ++j) Ga[t * GS + j] = Gl[t * GST + j];
-          }
+          // (the round kernel copies them LAST, below: on gfx950 a wavefront's
+          // loads and stores return through one in-order counter - issued
+          // here, their ~20 stores per lane stood between the rows requested
+          // above and the first control law)
         } else {
           // eight words per lane requested from LDS before the first is
           // stored (a plain loop waits out an LDS latency per word: 16 trips
@@ -562,6 +598,9 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
           for (; o < N * GS; o += 16 * H) Ga[o] = Gl[o];
         }
         PDDP_TLS_AT(10);
+        // (REC: the step sizes are in LDS, round_n4_body.hpp - a global load
+        // here, its address the decision's, would be queued behind every
+        // store of the tail that precedes its use)
         const T alpha_w = a.alphas[amin_out];
 #pragma unroll
         for (int k = 0; k < KR; ++k) {
@@ -589,6 +628,18 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
           for (int j = 0; j < m; ++j) us[j] = Us[tu * UST + j];
           control_law<T, n, m>(zz[k], zr, gr, us, alpha_w, umin, umax, uu[k]);
         }
+        if constexpr (PRE) {
+          // Every row requested above has arrived HERE, the ones past the
+          // horizon that nothing below uses too.  A load the compiler cannot
+          // see waited for on every path is one it waits for later, at the
+          // next write of its register - in the next round's prologue, behind
+          // every store issued below.
+#pragma unroll
+          for (int k = 0; k < KR; ++k) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) asm volatile("" : "+v"(zz[k][j]));
+          }
+        }
 #pragma unroll
         for (int k = 0; k < KR; ++k) {
           const int t = t_first + 16 * H * k;
@@ -610,6 +661,14 @@ PDDP_DEV void line_search_lds_body(const ProblemT<T> P,
                 for (int j = 0; j < m; ++j) cr[n + j] = uu[k][j];
               }
             }
+          }
+        }
+        if constexpr (PRE) {
+          // self._K <- K, from the staged rows (GST words in LDS, GS in
+          // gains_acc).  Nothing of the round waits for these stores.
+          for (int t = ai + 16 * hid; t < N; t += 16 * H) {
+#pragma unroll
+            for (int j = 0; j < GS; ++j) Ga[t * GS + j] = Gl[t * GST + j];
           }
         }
       } else {

@@ -43,6 +43,7 @@
 
 #include <type_traits>
 #include "models.hpp"
+#include "accept.hpp"           // RoundState
 #include "riccati_n4_quad.hpp"  // boxqp1_wave, rank_one_coeffs
 
 namespace pddp {
@@ -619,14 +620,21 @@ constexpr int kCarryF = kTrajW * kCarryRows * kCarryW;  // 340 floats
 constexpr int kGainL = kGain + 1;
 constexpr int round_gains_floats(int N) { return (kTrajW * N * kGainL + 3) & ~3; }
 
-template <typename T, unsigned QM, bool OVL, bool ROUND, int BR = kBrEigBox>
+template <typename T, unsigned QM, bool OVL, bool ROUND, int BR = kBrEigBox,
+          bool REC = false>
 PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
                               const ProblemT<T>& prob, unsigned char* smem_raw,
                               RoundOut& ro,
                               const unsigned tid = threadIdx.x,
-                              const int carry = -1) {
+                              const int carry = -1,
+                              RoundState* rs_wg = nullptr) {
   // carry (ROUND): -1 none; 1 this is the launch's first round - the rows
   // above are filled from global memory; 0 a later round - they are read
+  // REC (ROUND, several rounds per launch): `rs_wg` is the workgroup's
+  // [kWaves * kTrajW] records in LDS (accept.hpp RoundState), filled by the
+  // caller - active, mu, fresh and the nominal's cost are read there, not in
+  // global memory, and what finish_costs writes goes there too
+  static_assert(ROUND || !REC, "");
   static_assert(OVL || !ROUND, "");
   // (float64: the inline form only - two image buffers of doubles for four
   // pairs are 220 KB - with the closed-form BoxQP of riccati_n4.hpp and IEEE
@@ -666,7 +674,13 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
   // (both wavefronts of a pair decide alike: they own the same trajectories;
   // s_barrier does not wait for wavefronts that have ended)
   if (b0 >= a.B) return false;
-  const bool counted = exists && (a.active == nullptr || a.active[bc] != 0);
+  [[maybe_unused]] RoundState* const rs =
+      REC ? rs_wg + pair * kTrajW + row : nullptr;
+  bool counted;
+  if constexpr (REC)
+    counted = exists && rs->active != 0;
+  else
+    counted = exists && (a.active == nullptr || a.active[bc] != 0);
   if (!__any(counted)) return false;
   PDDP_EM_MARK(0);
   PDDP_TL(0);
@@ -699,6 +713,11 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
     const V4 v = *reinterpret_cast<const V4*>(Zg + 4 * tau);
     zq[0] = v[0]; zq[1] = v[1]; zq[2] = v[2]; zq[3] = v[3];
     uq = Ug[tau];
+    if constexpr (REC) {  // (block 0: waited for on this path, as in terminal)
+      if (jb == 0)
+        asm volatile("" : "+v"(zq[0]), "+v"(zq[1]), "+v"(zq[2]), "+v"(zq[3]),
+                          "+v"(uq));
+    }
     if constexpr (ROUND) {
       if (jb == 0 && carry == 1 && N - tau <= kBlk) {
         T* cr = carry_w + (N - tau) * kCarryW;
@@ -718,6 +737,11 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
     } else {
       const V4 zNv = *reinterpret_cast<const V4*>(Zg + 4 * N);
       zN[0] = zNv[0]; zN[1] = zNv[1]; zN[2] = zNv[2]; zN[3] = zNv[3];
+      // (REC: the load is waited for on THIS path.  Where the two paths meet
+      // the compiler waits for whatever either may have in flight, and in
+      // the rounds that took the other one that is the last round's stores)
+      if constexpr (REC)
+        asm volatile("" : "+v"(zN[0]), "+v"(zN[1]), "+v"(zN[2]), "+v"(zN[3]));
       if (ROUND && carry == 1 && l == 0) {
         carry_w[0] = zN[0]; carry_w[1] = zN[1]; carry_w[2] = zN[2];
         carry_w[3] = zN[3];
@@ -778,18 +802,30 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
   // J_opt = sum of the stage costs and the terminal one (ilqr.py:289), for
   // the trajectories whose nominal changed
   auto finish_costs = [&]() {
-    const bool sums = counted && (gen.fresh == nullptr || gen.fresh[bc] != 0);
+    bool sums;
+    if constexpr (REC)
+      sums = counted && rs->fresh != 0;
+    else
+      sums = counted && (gen.fresh == nullptr || gen.fresh[bc] != 0);
     // (OVL: the terminal cost is the sweep wavefront's; inline: our own)
     const T Jrow = group_sum(Jacc) + (OVL ? term_w[row * kTermRow + 20] : l_term);
     if constexpr (ROUND) {
       // the cost the accept test compares with (ilqr.py:166): the new sum, or
       // what the nominal already had
-      const T Jold = gen.J_opt[bc];
+      T Jold;
+      if constexpr (REC)
+        Jold = rs->J_opt;
+      else
+        Jold = gen.J_opt[bc];
       if (l == 0) term_w[row * kTermRow + 21] = sums ? Jrow : Jold;
     }
     if (sums && l == 0) {
       gen.J_opt[bc] = Jrow;
       if (gen.fresh != nullptr) gen.fresh[bc] = 0;
+      if constexpr (REC) {
+        rs->J_opt = Jrow;
+        rs->fresh = 0;
+      }
     }
   };
   // the gains of a block's first `cnt` steps (t_top, t_top - 1, ...) from the
@@ -872,7 +908,11 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
   }
 
   // =================================================================== sweep
-  const T reg = (T)a.reg[bc];
+  T reg;
+  if constexpr (REC)
+    reg = (T)rs->mu;
+  else
+    reg = (T)a.reg[bc];
   // LDS offsets of this lane (floats, inside a step's image)
   const int oA = rbase + 4 * i, oB = rbase + 4 * j, oL = rbase + 32 + l;
   const int oTi = rbase + 16 + 2 * i, oTj = rbase + 24 + 2 * j;
