@@ -28,9 +28,13 @@ A property of the inputs, asserted here: the float64 `eigh` of the cast matrix
 has min |lam| >= 1e-3 max |lam| (graded, denorm: every lam > 0), so that the
 discontinuous clamp `e < 0 -> 1e-12` never sits on a rounding error.
 """
+import functools
 import itertools
 
 import numpy as np
+
+import oracle as orc
+from golden_util import np_dtype
 
 FAMILIES = ("spd", "indef", "repeat", "cI", "negI", "diag", "block", "perm",
             "graded", "denorm")
@@ -432,6 +436,22 @@ def probe_batch(m, dtype, V_zz_reg, bounded):
     else:
         labels, A, reg = cases(FAMILIES, m, dtype, per_family=10)
     return labels, A, reg, probe_records(A, dtype)
+
+
+BRANCHES = [("eig", False, False), ("chol", True, False),
+            ("eig_box", False, True), ("chol_box", True, True)]
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_side(m, dtype, V_zz_reg, bounded):
+    """The oracle of `dtype` on a probe batch - computed once, shared by the
+    CPU and the GPU tests, not to be written to."""
+    batch = probe_batch(m, np_dtype(dtype), V_zz_reg, bounded)
+    k, K, st = oracle_probe(orc.load(np_dtype(dtype)), batch[3], batch[2],
+                            V_zz_reg, bounded)
+    ref = bounded_reference(batch[1], batch[2], batch[3], V_zz_reg) \
+        if bounded else None
+    return batch, k, K, st, ref
 
 
 # --------------------------------------------------------------------------

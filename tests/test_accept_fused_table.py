@@ -25,10 +25,9 @@ import torch
 
 import accept_model as am
 import oracle as orc
+from accept_rows import bits, ITER_ROWS, MAX_REG, N_IT, REG_ROWS, SENT, TOL
 from golden_util import np_dtype, rel_err
-from test_accept_table import (ITER_ROWS, MAX_REG, N_IT, REG_ROWS, SENT, TDT,
-                               TOL, bits)
-from test_gpu_parity import TOL as PARITY_TOL, _setup
+from solver_util import make_solver, TDT, TOL as PARITY_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -76,7 +75,7 @@ def _solver(problem, dtype, B, N, A, branch, bounded, huge=None, steps=None):
     `steps`: another list altogether."""
     huge = (not bounded) if huge is None else huge
     from pddp_amd.controllers.solver import ILQRSolver
-    s0, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N, seed=4)
+    s0, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N, seed=4)
     td = TDT[dtype]
     s = ILQRSolver(s0.problem, B, N, td, "cuda",
                    s0.u_min if bounded else None,

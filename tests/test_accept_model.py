@@ -178,7 +178,7 @@ def test_model_edges(dtype):
 
 
 def test_decision_table_covers_every_exit():
-    import test_accept_table as tab
+    import accept_rows as tab
     """The table itself: every state, both masks, a winner at every kind of
     position - by the model, before any kernel is asked."""
     for dtype in ("f32", "f64"):

@@ -56,9 +56,12 @@ import torch
 
 import oracle as orc
 import action_families as af
+from action_families import BRANCHES, oracle_side
 from golden_util import np_dtype, rel_err
-from test_action_algebra_oracle import BRANCHES, oracle_side
-from test_gpu_parity import F32_RATIO, TDT, _check_gains, _f32_ok
+from solver_util import TDT
+# (conftest.py dumps sys.modules["test_gpu_parity"].STATS: the fp32
+# bookkeeping stays in that module - the one import from a test module)
+from test_gpu_parity import _check_gains, _f32_ok, F32_RATIO
 
 pytestmark = pytest.mark.gpu
 

@@ -27,33 +27,17 @@ K at most 1.45, k at most 8.5 but for one float64 `graded` case at 1.3e3, and
 the BoxQP ends beside the minimiser on 1 of 214 cases (float64, m = 3) and 2 of
 3365 (float32, m = 3)."""
 import collections
-import functools
 
 import numpy as np
 import pytest
 
-import oracle as orc
 import action_families as af
+from action_families import BRANCHES, oracle_side
 from golden_util import np_dtype
 
 R_BAR = {"f64": 4 * 5.9, "f32": 4 * 3.0}
 K_BAR_EPS = {"f64": 4 * 17.0, "f32": 4 * 2.5e3}
 LEFT_OUT = 0.04
-
-BRANCHES = [("eig", False, False), ("chol", True, False),
-            ("eig_box", False, True), ("chol_box", True, True)]
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_side(m, dtype, V_zz_reg, bounded):
-    """The oracle of `dtype` on a probe batch - computed once, shared with
-    the GPU tests, not to be written to."""
-    batch = af.probe_batch(m, np_dtype(dtype), V_zz_reg, bounded)
-    k, K, st = af.oracle_probe(orc.load(np_dtype(dtype)), batch[3], batch[2],
-                               V_zz_reg, bounded)
-    ref = af.bounded_reference(batch[1], batch[2], batch[3], V_zz_reg) \
-        if bounded else None
-    return batch, k, K, st, ref
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])

@@ -9,7 +9,6 @@ constant of a pddp_problem) move records and costs by parts in ten, orders of
 magnitude above the bars - those of tests/test_gpu_parity.py: a kernel that
 ignores the table, or reads a neighbour's row, fails the comparisons."""
 import ctypes
-import os
 import re
 import types
 
@@ -18,76 +17,23 @@ import pytest
 import torch
 
 import oracle as orc
-from golden_util import DT, FWD_NAMES, np_dtype, rel_err
-from test_gpu_parity import PROBLEMS, TDT, _run_traced, _setup
+from abi_util import assert_entry_points, HDR
+from golden_util import FWD_NAMES, np_dtype, rel_err
+from solver_util import (make_solver, named_views, perturbed, PROBLEMS,
+                         record_tol, run_traced, set_table, TDT)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PARAM_COUNT = {"cartpole": 6, "pendulum": 5, "double_cartpole": 8,
-               "rendezvous": 3}  # dt included (include/pddp_problem.h)
 NEW_SYMBOLS = ["pddp_%s_batch_%s" % (k, t)
                for k in ("nominal_rollout", "derivs", "line_search")
                for t in ("f32", "f64")]
-REC_NAMES = ("F_z", "F_u", "L_z", "L_u", "L_zz", "L_uz", "L_uu")
-
-
-def _tol(dtype):
-    # test_derivative_records_vs_oracle's / test_line_search_vs_oracle's bars
-    return 1e-10 if dtype == "f64" else 2e-4
-
-
-def _perturbed(problem, B, seed):
-    """(params [B][P], x_goal [B][na], u_goal [B][m]) as float64 arrays of
-    float32 values, and the oracle's problem of every trajectory."""
-    rng = np.random.RandomState(seed)
-    base = orc.make_problem(problem, DT[problem])
-    P, na, m = PARAM_COUNT[problem], base.aug_size, base.action_size
-    par = np.tile(np.array(base.params[:P]), (B, 1))
-    par[:, 0] *= rng.uniform(0.9, 1.1, B)
-    par[:, 1:] *= rng.uniform(0.8, 1.2, (B, P - 1))
-    xg = np.tile(np.array(base.x_goal[:na]), (B, 1)) + \
-        rng.uniform(-0.5, 0.5, (B, na))
-    ug = np.tile(np.array(base.u_goal[:m]), (B, 1)) + \
-        rng.uniform(-0.2, 0.2, (B, m))
-    par, xg, ug = (a.astype(np.float32).astype(np.float64)
-                   for a in (par, xg, ug))
-    ops = []
-    for b in range(B):
-        op = orc.make_problem(problem, DT[problem])
-        for i in range(P):
-            op.params[i] = par[b, i]
-        for i in range(na):
-            op.x_goal[i] = xg[b, i]
-        for i in range(m):
-            op.u_goal[i] = ug[b, i]
-        ops.append(op)
-    return par, xg, ug, ops
-
-
-def _set_table(s, par, xg, ug):
-    s.set_batch_problem(params=torch.from_numpy(par),
-                        x_goal=torch.from_numpy(xg),
-                        u_goal=torch.from_numpy(ug))
-
-
-def _views(s):
-    v = dict(zip(REC_NAMES, s.record_views()))
-    v["Z"], v["L"] = s.Z, s.L
-    return v
 
 
 def test_batch_entry_points_are_declared_exported_and_bound():
     """CPU: the six entry points in the header, the built library and
     _native._SIGS; the row layout of the header == _native's constants."""
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name), name
-        assert name in _native.exported_symbols(), name
-        assert name[:-4] in _native._SIGS, name
-    defs = dict(re.findall(r"#define\s+(PDDP_BATCH_\w+)\s+(\d+)", hdr))
+    assert_entry_points(NEW_SYMBOLS)
+    defs = dict(re.findall(r"#define\s+(PDDP_BATCH_\w+)\s+(\d+)", HDR))
     assert {k: int(v) for k, v in defs.items()} == {
         "PDDP_BATCH_ROW": _native.BATCH_ROW,
         "PDDP_BATCH_PARAMS": _native.BATCH_PARAMS,
@@ -103,16 +49,16 @@ def test_batch_entry_points_are_declared_exported_and_bound():
 @pytest.mark.parametrize("problem", PROBLEMS)
 def test_batch_records_vs_oracle(problem, dtype):
     B, N = 6, 70  # > 64: a second, ragged chunk of the record staging
-    s, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
-    par, xg, ug, ops = _perturbed(problem, B, seed=21)
-    _set_table(s, par, xg, ug)
+    s, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
+    par, xg, ug, ops = perturbed(problem, B, seed=21)
+    set_table(s, par, xg, ug)
     assert tuple(s.batch_table.shape) == (B, 20)
     assert s.batch_table.dtype == TDT[dtype] and s.batch_table.is_cuda
     s.nominal_rollout()
     s.derivs(set_state=False)
-    views = _views(s)
+    views = named_views(s)
     o = orc.load(np_dtype(dtype))
-    tol = _tol(dtype)
+    tol = record_tol(dtype)
     for b in range(B):
         ref = o.forward(ops[b], z0[b], U[b], u_min, u_max)
         for nm in FWD_NAMES:
@@ -132,18 +78,18 @@ def test_batch_line_search_vs_oracle(problem, dtype):
     from pddp_amd.controllers.solver import (ILQRSolver, fit_alphas,
                                              mpc_alphas)
     B, N = 5, 12
-    s0, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
-    par, xg, ug, ops = _perturbed(problem, B, seed=22)
+    s0, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
+    par, xg, ug, ops = perturbed(problem, B, seed=22)
     td = TDT[dtype]
     o = orc.load(np_dtype(dtype))
-    tol = _tol(dtype)
+    tol = record_tol(dtype)
     for alphas in (fit_alphas(td, "cuda"), mpc_alphas(td, "cuda"),
                    torch.linspace(1.0, 0.01, 17).to(td)):
         s = ILQRSolver(s0.problem, B, N, td, "cuda", torch.from_numpy(u_min),
                        torch.from_numpy(u_max), alphas=alphas)
         s.z0.copy_(s0.z0)
         s.U.copy_(s0.U)
-        _set_table(s, par, xg, ug)
+        set_table(s, par, xg, ug)
         s.nominal_rollout()
         s.derivs(set_state=False)
         regv = torch.full((B,), 1.0, dtype=torch.float64, device="cuda")
@@ -176,13 +122,13 @@ def test_replicated_table_equals_uniform_problem(problem, dtype):
     gains (to rounding, not bit for bit: the same closed forms inlined into
     two kernels are contracted into FMAs differently, csrc/Makefile)."""
     B, N = 5, 12
-    s, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
-    tol = _tol(dtype)
+    s, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
+    tol = record_tol(dtype)
 
     def run():
         s.nominal_rollout()
         s.derivs(set_state=False)
-        out = {k: v.clone() for k, v in _views(s).items()}
+        out = {k: v.clone() for k, v in named_views(s).items()}
         out["J_opt"] = s.J_opt.clone()
         return out
 
@@ -218,9 +164,9 @@ def test_replicated_table_equals_uniform_problem(problem, dtype):
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_batch_kernels_honour_their_masks(dtype):
     B, N = 5, 12
-    s, _, z0, U, u_min, u_max = _setup("cartpole", dtype, B, N)
-    par, xg, ug, _ = _perturbed("cartpole", B, seed=23)
-    _set_table(s, par, xg, ug)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", dtype, B, N)
+    par, xg, ug, _ = perturbed("cartpole", B, seed=23)
+    set_table(s, par, xg, ug)
     s.nominal_rollout()
     s.derivs(set_state=False)
     regv = torch.full((B,), 1.0, dtype=torch.float64, device="cuda")
@@ -264,11 +210,11 @@ def test_batch_fit_traces_vs_oracle(problem):
     costs, final nominal and accepted gains (test_fit_traces_vs_oracle's
     shape and bars)."""
     B, N, n_it = 6, 30, 12
-    s, _, z0, U, u_min, u_max = _setup(problem, "f64", B, N, seed=3)
-    par, xg, ug, ops = _perturbed(problem, B, seed=24)
-    _set_table(s, par, xg, ug)
+    s, _, z0, U, u_min, u_max = make_solver(problem, "f64", B, N, seed=3)
+    par, xg, ug, ops = perturbed(problem, B, seed=24)
+    set_table(s, par, xg, ug)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
-    traces = _run_traced(s, n_it)
+    traces = run_traced(s, n_it)
     assert s._one_launch is False and s._nominal_sweep is False
     o = orc.load(np.float64)
     alphas = s.alphas.cpu().numpy()
@@ -298,12 +244,12 @@ def test_batch_plan_and_lifecycle():
     from pddp_amd import _native
     from pddp_amd.controllers.solver import ILQRSolver
     B, N = 20, 10
-    s, _, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N)
     z0t, Ut = torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda()
     fresh_plan = s._plan(0)
     assert fresh_plan == "one_launch"
-    par, xg, ug, _ = _perturbed("cartpole", B, seed=25)
-    _set_table(s, par, xg, ug)
+    par, xg, ug, _ = perturbed("cartpole", B, seed=25)
+    set_table(s, par, xg, ug)
     assert s._plan(0) == "records+separate"
     assert s._derivs_due is True and s._graph is None
     s.set_nominal(z0t, Ut)

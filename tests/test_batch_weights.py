@@ -13,7 +13,6 @@ ten, orders of magnitude above the bars - those of
 tests/test_batch_problem.py: a kernel that ignores the weights, reads a
 neighbour's row or replaces an off-diagonal entry fails the comparisons."""
 import ctypes
-import os
 import re
 import types
 
@@ -22,12 +21,12 @@ import pytest
 import torch
 
 import oracle as orc
+from abi_util import assert_entry_points, HDR
 from golden_util import DT, FWD_NAMES, np_dtype, rel_err
-from test_batch_problem import _perturbed, _set_table, _tol, _views
-from test_gpu_parity import PROBLEMS, TDT, _run_traced, _setup
+from solver_util import (make_solver, named_views, perturbed, PROBLEMS,
+                         record_tol, run_traced, set_table, TDT)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["pddp_%s_weighted_%s" % (k, t)
                for k in ("derivs", "line_search") for t in ("f32", "f64")]
 
@@ -86,14 +85,8 @@ def test_weighted_entry_points_are_declared_exported_and_bound():
     exported_symbols() and _native._SIGS; the row layout of the header ==
     _native's constants; the ABI version stays 1."""
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name), name
-        assert name in _native.exported_symbols(), name
-        assert name[:-4] in _native._SIGS, name
-    defs = dict(re.findall(r"#define\s+(PDDP_WEIGHT_\w+)\s+(\d+)", hdr))
+    assert_entry_points(NEW_SYMBOLS)
+    defs = dict(re.findall(r"#define\s+(PDDP_WEIGHT_\w+)\s+(\d+)", HDR))
     assert {k: int(v) for k, v in defs.items()} == {
         "PDDP_WEIGHT_ROW": _native.WEIGHT_ROW,
         "PDDP_WEIGHT_Q": _native.WEIGHT_Q,
@@ -111,14 +104,14 @@ def test_weighted_records_vs_oracle(problem, dtype):
     """Weights alone (table == NULL), then weights AND a perturbed table: both
     writers over the shared problem."""
     B, N = 6, 70  # > 64: a second, ragged chunk of the record staging
-    s, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
+    s, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
     o = orc.load(np_dtype(dtype))
-    tol = _tol(dtype)
+    tol = record_tol(dtype)
     for with_table in (False, True):
         ops = None
         if with_table:
-            par, xg, ug, ops = _perturbed(problem, B, seed=31)
-            _set_table(s, par, xg, ug)
+            par, xg, ug, ops = perturbed(problem, B, seed=31)
+            set_table(s, par, xg, ug)
         q, qt, r, ops = _weights(problem, B, seed=32, ops=ops)
         _set_weights(s, q, qt, r)
         assert (s.batch_table is not None) == with_table
@@ -128,7 +121,7 @@ def test_weighted_records_vs_oracle(problem, dtype):
         s.nominal_rollout()
         s._rec.fill_(float("nan"))
         s.derivs(set_state=False)
-        views = _views(s)
+        views = named_views(s)
         for b in range(B):
             ref = o.forward(ops[b], z0[b], U[b], u_min, u_max)
             for nm in FWD_NAMES:
@@ -148,10 +141,10 @@ def test_weighted_line_search_vs_oracle(problem, dtype):
     from pddp_amd.controllers.solver import (ILQRSolver, fit_alphas,
                                              mpc_alphas)
     B, N = 5, 12
-    s0, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
+    s0, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
     td = TDT[dtype]
     o = orc.load(np_dtype(dtype))
-    tol = _tol(dtype)
+    tol = record_tol(dtype)
     for alphas, with_table in (
             (fit_alphas(td, "cuda"), False), (mpc_alphas(td, "cuda"), False),
             (torch.linspace(1.0, 0.01, 17).to(td), False),
@@ -162,8 +155,8 @@ def test_weighted_line_search_vs_oracle(problem, dtype):
         s.U.copy_(s0.U)
         ops = None
         if with_table:
-            par, xg, ug, ops = _perturbed(problem, B, seed=33)
-            _set_table(s, par, xg, ug)
+            par, xg, ug, ops = perturbed(problem, B, seed=33)
+            set_table(s, par, xg, ug)
         q, qt, r, ops = _weights(problem, B, seed=34, ops=ops)
         _set_weights(s, q, qt, r)
         s.nominal_rollout()
@@ -197,12 +190,12 @@ def test_replicated_weights_equal_uniform_problem(problem, dtype):
     kernels against the uniform entry points' on the same inputs and gains (to
     rounding, not bit for bit: these are other kernels, csrc/Makefile)."""
     B, N = 5, 12
-    s, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
-    tol = _tol(dtype)
+    s, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
+    tol = record_tol(dtype)
 
     def run():
         s.derivs(set_state=False)
-        out = {k: v.clone() for k, v in _views(s).items()}
+        out = {k: v.clone() for k, v in named_views(s).items()}
         out["J_opt"] = s.J_opt.clone()
         return out
 
@@ -234,7 +227,7 @@ def test_replicated_weights_equal_uniform_problem(problem, dtype):
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_weighted_kernels_honour_their_masks(dtype):
     B, N = 5, 12
-    s, _, z0, U, u_min, u_max = _setup("cartpole", dtype, B, N)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", dtype, B, N)
     q, qt, r, _ = _weights("cartpole", B, seed=35)
     _set_weights(s, q, qt, r)
     s.nominal_rollout()
@@ -277,11 +270,11 @@ def test_weighted_fit_traces_vs_oracle(problem):
     costs, final nominal and accepted gains (test_batch_fit_traces_vs_oracle's
     shape and bars)."""
     B, N, n_it = 6, 30, 12
-    s, _, z0, U, u_min, u_max = _setup(problem, "f64", B, N, seed=3)
+    s, _, z0, U, u_min, u_max = make_solver(problem, "f64", B, N, seed=3)
     q, qt, r, ops = _weights(problem, B, seed=36)
     _set_weights(s, q, qt, r)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
-    traces = _run_traced(s, n_it)
+    traces = run_traced(s, n_it)
     assert s._one_launch is False and s._nominal_sweep is False
     o = orc.load(np.float64)
     alphas = s.alphas.cpu().numpy()
@@ -311,7 +304,7 @@ def test_weights_plan_and_lifecycle():
     from pddp_amd import _native
     from pddp_amd.controllers.solver import ILQRSolver
     B, N = 20, 10
-    s, _, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N)
     z0t, Ut = torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda()
     fresh_plan = s._plan(0)
     assert fresh_plan == "one_launch"
@@ -416,7 +409,7 @@ def test_weights_are_checked_on_the_host():
     device holds the tensors; nothing is launched.)"""
     from pddp_amd import _native
     B, N = 4, 5
-    s = _setup("cartpole", "f32", B, N)[0]
+    s = make_solver("cartpole", "f32", B, N)[0]
     q, qt, r, _ = _weights("cartpole", B, seed=38)
     low = q.copy()
     low[:, 0] = 0.1
@@ -449,7 +442,7 @@ def test_closed_loop_costs_are_the_shared_problems():
     shared Q, Q_term, R: bit-equal to an un-weighted solver's that was given
     the same nominal and accepted gains by copy."""
     B, N, S = 6, 30, 3
-    s, _, z0, U, u_min, u_max = _setup("cartpole", "f64", B, N, seed=3)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f64", B, N, seed=3)
     q, qt, r, _ = _weights("cartpole", B, seed=39)
     _set_weights(s, q, qt, r)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
@@ -458,7 +451,7 @@ def test_closed_loop_costs_are_the_shared_problems():
     z0s = torch.from_numpy(
         z0[:, None, :] + 1e-2 * rng.randn(B, S, z0.shape[1])).cuda()
     got = s.closed_loop(samples=S, z0=z0s)
-    s2 = _setup("cartpole", "f64", B, N, seed=3)[0]
+    s2 = make_solver("cartpole", "f64", B, N, seed=3)[0]
     for nm in ("Z", "U", "gains_acc"):
         getattr(s2, nm).copy_(getattr(s, nm))
     want = s2.closed_loop(samples=S, z0=z0s)
@@ -475,8 +468,8 @@ def test_mpc_trial_with_weights_is_the_composed_trial():
     step rounds(2, n_iterations=1), then pddp_mpc_advance_f64."""
     from pddp_amd import _native
     B, N, T, R = 5, 20, 3, 2
-    s, _, z0, U, u_min, u_max = _setup("cartpole", "f64", B, N)
-    s2 = _setup("cartpole", "f64", B, N)[0]
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f64", B, N)
+    s2 = make_solver("cartpole", "f64", B, N)[0]
     q, qt, r, _ = _weights("cartpole", B, seed=41)
     _set_weights(s, q, qt, r)
     _set_weights(s2, q, qt, r)
@@ -506,7 +499,7 @@ def test_mpc_trial_with_weights_is_the_composed_trial():
     for nm in ("z0", "Z", "U", "mu", "delta", "state"):
         assert torch.equal(getattr(s, nm), getattr(s2, nm)), nm
     # the rounds inside the trial did optimise under the weights
-    s3 = _setup("cartpole", "f64", B, N)[0]
+    s3 = make_solver("cartpole", "f64", B, N)[0]
     plain = s3.mpc_closed_loop(T, R)
     assert not torch.equal(plain.U, got.U)
 
@@ -521,7 +514,7 @@ def test_captured_round_with_weights_and_the_controller_methods():
     q, qt, r, _ = _weights("cartpole", B, seed=42)
     out = []
     for graph in (False, True):
-        s = _setup("cartpole", "f64", B, N)[0]
+        s = make_solver("cartpole", "f64", B, N)[0]
         _set_weights(s, q, qt, r)
         s.set_nominal(s.z0, s.U)
         if graph:
@@ -535,7 +528,7 @@ def test_captured_round_with_weights_and_the_controller_methods():
         out.append(s)
     for nm in ("Z", "U", "J_opt", "state", "mu", "delta"):
         assert torch.equal(getattr(out[0], nm), getattr(out[1], nm)), nm
-    plain = _setup("cartpole", "f64", B, N)[0]
+    plain = make_solver("cartpole", "f64", B, N)[0]
     plain.set_nominal(plain.z0, plain.U)
     plain.round()
     assert not torch.equal(plain.J_opt, out[1].J_opt)

@@ -8,8 +8,9 @@ real size against the reference's own float64 outputs."""
 import numpy as np
 import pytest
 import torch
+from golden_util import rel_err
+from solver_util import bnn_problem, bnn_real_size_run, BOUND, MEAN0
 
-from test_gpu_parity import BOUND, MEAN0, _bnn_real_size_run
 
 pytestmark = pytest.mark.gpu
 
@@ -258,7 +259,7 @@ def test_bnn_f64_hip_kernels_vs_reference_real_size():
     for everything (measured on the MI355X: rollouts, costs and the line search
     1e-17 .. 8e-16, the Jacobians - through the differential of a Cholesky
     factor - 3e-15 .. 9e-15)."""
-    rows = _bnn_real_size_run(torch.float64)
+    rows = bnn_real_size_run(torch.float64)
     assert rows[-1]["path"] == {"dynamics": "hip", "cost": "hip"}
     seen = set()
     for r in rows[:-1]:
@@ -329,8 +330,7 @@ def test_full_size_bnn_round_f64(problem, B, N):
     - nominal rollout 1e-12, derivative records 1e-8, candidate costs under the
     HIP gains 1e-10, and the same best step size."""
     import copy
-    from test_gpu_parity import _bnn_problem, rel_err
-    model, cost, z0, U, solver = _bnn_problem(problem, B, N)
+    model, cost, z0, U, solver = bnn_problem(problem, B, N)
     dup = [(0, B - 1), (17, B // 2)]
     for a, b in dup:
         z0[b], U[b] = z0[a], U[a]

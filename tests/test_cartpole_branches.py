@@ -4,7 +4,7 @@ next to the bounded eig-clamp one (csrc/cartpole_branches.hip, DESIGN.md
 3.1i): eig-clamp without action bounds (ilqr.py:631-643), V_zz-regularised
 without (ilqr.py:587-599) and with them (ilqr.py:600-617).
 
-On the random nominal of `_setup` the unbounded eig-clamp sweep fails for
+On the random nominal of `make_solver` the unbounded eig-clamp sweep fails for
 every trajectory at reg 0, 1e-6 and 1 and goes through at reg = 100; the
 V_zz-regularised forms fail at 0 and 1e-6 and go through at 1 and 100 (the
 CPU oracle, fp32 and fp64 alike).  So every sweep test runs mu = 100 (gains
@@ -16,8 +16,10 @@ import torch
 
 import oracle as orc
 from golden_util import np_dtype, rel_err
-from test_gpu_parity import (STATS, _check_gains, _nominal_kernel,
-                             _run_traced, _setup)
+from solver_util import make_solver, nominal_kernel, run_traced
+# (conftest.py dumps sys.modules["test_gpu_parity"].STATS: the fp32
+# bookkeeping stays in that module - the one import from a test module)
+from test_gpu_parity import _check_gains, STATS
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +33,7 @@ MU_OK, MU_FAIL = 100.0, 1e-6
 
 
 def _solver(dtype, B, N, seed, branch, bounded):
-    s, op, z0, U, u_min, u_max = _setup("cartpole", dtype, B, N, seed=seed)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", dtype, B, N, seed=seed)
     if not bounded:
         s.u_min = s.u_max = None
     s.branch = branch
@@ -146,7 +148,7 @@ def test_f32_sweep_from_nominal_vs_records_and_oracle(B, N, kernel, combo):
     branches: against pddp_derivs_f32 + the sweep on records (status equal,
     gains to 2e-4 of the largest, L 1e-6, J_opt 1e-5) and against the oracle
     through `_check_gains`; status flips against the fp32 oracle capped."""
-    with _nominal_kernel(kernel):
+    with nominal_kernel(kernel):
         _sweep_case("f32", B, N, combo[1], combo[2])
 
 
@@ -157,7 +159,7 @@ def test_sweep_from_nominal_reports_a_nan_nominal(kernel, combo):
     the other rows of the same wavefront are not disturbed."""
     _, branch, bounded = combo
     B, N = 24, 40
-    with _nominal_kernel(kernel):
+    with nominal_kernel(kernel):
         s, op, z0, U, u_min, u_max = _solver("f32", B, N, 3, branch, bounded)
         U = U.copy()
         U[2, 17] = np.nan
@@ -310,7 +312,7 @@ def test_unbounded_fit_through_the_one_launch_round_vs_oracle():
     s, op, z0, U, u_min, u_max = _solver("f32", B, N, 7, 0, False)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     s._nominal_sweep = None if s._nominal_sweep_pays() else False
-    traces = _run_traced(s, n_it)
+    traces = run_traced(s, n_it)
     assert s._one_launch is True
     assert s._nominal_sweep is True and s._fused is True
     o32, o64 = orc.load(np.float32), orc.load(np.float64)

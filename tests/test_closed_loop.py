@@ -8,9 +8,6 @@ Z'[0] under one problem, so rollout (b, s) is control_law on the plant row's
 problem with Z' = Z[b] but Z'[0] = z0s[b][s], k'[0] = K[b][0] (z0s[b][s] -
 Z[b][0]), k'[t > 0] = 0 and the one step size 1: its first action is then
 U[b][0] + K[b][0] (x_0 - Z[b][0]) and every later one the feedback law."""
-import ctypes
-import os
-import re
 import types
 
 import numpy as np
@@ -18,76 +15,14 @@ import pytest
 import torch
 
 import oracle as orc
+from abi_util import assert_entry_points, caller, cartpole_pointers
 from golden_util import np_dtype, rel_err
-from test_batch_problem import _perturbed, _set_table, _tol
-from test_gpu_parity import PROBLEMS, _setup
+from solver_util import (closed_loop_call, make_solver, perturbed,
+                         perturbed_starts, plant_rows, policy_solver, PROBLEMS,
+                         record_tol, SENTINEL, set_table)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["pddp_closed_loop_f32", "pddp_closed_loop_f64"]
-SENTINEL = -7.25
-
-
-def _plant_rows(problem, B, S, seed, dtype):
-    """[B][S][20] plant rows (numpy, the run's dtype) from `_perturbed`, and
-    the oracle's problem of every (b, s)."""
-    from pddp_amd import _native as N_
-    par, xg, ug, ops = _perturbed(problem, B * S, seed)
-    rows = np.zeros((B * S, N_.BATCH_ROW))
-    rows[:, N_.BATCH_PARAMS:N_.BATCH_PARAMS + par.shape[1]] = par
-    rows[:, N_.BATCH_X_GOAL:N_.BATCH_X_GOAL + xg.shape[1]] = xg
-    rows[:, N_.BATCH_U_GOAL:N_.BATCH_U_GOAL + ug.shape[1]] = ug
-    rows = rows.reshape(B, S, N_.BATCH_ROW).astype(np_dtype(dtype))
-    return rows, [ops[b * S:(b + 1) * S] for b in range(B)]
-
-
-def _policy(problem, dtype, B, N, seed=0):
-    """A solver holding a nominal and the gains of one sweep at reg = 1 (as
-    test_batch_line_search_vs_oracle makes them), bounded."""
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N, seed)
-    s.nominal_rollout()
-    s.derivs(set_state=False)
-    s.backward(reg=torch.full((B,), 1.0, dtype=torch.float64, device="cuda"))
-    assert int(s.bwd_status.abs().sum()) == 0
-    return s, op, u_min, u_max
-
-
-def _starts(s, S, seed):
-    """z0s = Z[b][0] + U(-0.05, 0.05), [B][S][n] in the run's dtype."""
-    rng = np.random.RandomState(seed)
-    Z0 = s.Z[:, 0].cpu().numpy()
-    d = rng.uniform(-0.05, 0.05, (s.B, S, s.n))
-    return (Z0[:, None, :] + d).astype(Z0.dtype)
-
-
-def _call(s, S, z0s=None, plant=None, gains="sweep", bounded=True,
-          active=None, keep=True, stats=True, fill=None):
-    """pddp_closed_loop_* itself on the solver's nominal; outputs pre-filled
-    with `fill`.  z0s / plant: numpy or None."""
-    from pddp_amd import _native
-    B, N, n, m = s.B, s.N, s.n, s.m
-    opts = dict(dtype=s.dtype, device="cuda")
-
-    def buf(*shape):
-        return torch.empty(*shape, **opts) if fill is None else \
-            torch.full(shape, fill, **opts)
-
-    dev = lambda a: None if a is None else torch.from_numpy(
-        np.ascontiguousarray(a)).to(**opts)
-    z0s_t, plant_t = dev(z0s), dev(plant)
-    g = s.gains if isinstance(gains, str) else gains
-    out = types.SimpleNamespace(
-        X=buf(B, N + 1, S, n) if keep else None,
-        U=buf(B, N, S, m) if keep else None, J=buf(B, S),
-        stats=buf(B, 4) if stats else None)
-    p = _native.ptr
-    _native.call("pddp_closed_loop", s.dtype, ctypes.addressof(s.problem), B,
-                 N, S, p(s.Z), p(s.U), p(g), p(z0s_t), p(plant_t),
-                 p(s.u_min if bounded else None),
-                 p(s.u_max if bounded else None), p(active), p(out.X),
-                 p(out.U), p(out.J), p(out.stats), s._s())
-    torch.cuda.synchronize()
-    return out
 
 
 def _oracle_rollouts(s, dtype, ops, z0s, u_min, u_max):
@@ -116,12 +51,12 @@ def _oracle_rollouts(s, dtype, ops, z0s, u_min, u_max):
 
 
 def _check_vs_oracle(problem, dtype, B, N, S, seed):
-    s, _, u_min, u_max = _policy(problem, dtype, B, N)
-    rows, ops = _plant_rows(problem, B, S, seed, dtype)
-    z0s = _starts(s, S, seed + 100)
-    out = _call(s, S, z0s=z0s, plant=rows)
+    s, _, u_min, u_max = policy_solver(problem, dtype, B, N)
+    rows, ops = plant_rows(problem, B, S, seed, dtype)
+    z0s = perturbed_starts(s, S, seed + 100)
+    out = closed_loop_call(s, S, z0s=z0s, plant=rows)
     X, U, J = _oracle_rollouts(s, dtype, ops, z0s, u_min, u_max)
-    tol = _tol(dtype)
+    tol = record_tol(dtype)
     for b in range(B):
         e = (rel_err(out.X[b].cpu().numpy(), X[b]),
              rel_err(out.U[b].cpu().numpy(), U[b]),
@@ -134,13 +69,7 @@ def _check_vs_oracle(problem, dtype, B, N, S, seed):
 def test_closed_loop_entry_points_are_declared_exported_and_bound():
     """CPU: both symbols in the header, the built library and _native._SIGS."""
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name), name
-        assert name in _native.exported_symbols(), name
-        assert name[:-4] in _native._SIGS, name
+    assert_entry_points(SYMBOLS)
     assert len(_native._SIGS["pddp_closed_loop"]) == 17
     assert _native.lib().pddp_hip_abi_version() == 1
 
@@ -150,27 +79,13 @@ def test_closed_loop_refuses_before_any_launch():
     call): PDDP_E_BADARG for a null Jc, S = 0 and one of Xc / Uc alone;
     PDDP_E_UNSUPPORTED for a DEFAULT-encoding problem, both dtypes.  The
     non-null pointers are host words nobody reads."""
-    import pddp_amd
     from pddp_amd import _native
-    from pddp_amd.examples import cartpole
-    enc = pddp_amd.StateEncoding
-    model, cost = cartpole.CartpoleDynamicsModel(0.1), cartpole.CartpoleCost()
-    prob = model.native_problem(enc.IGNORE_UNCERTAINTY, cost)
-    prob_d = model.native_problem(enc.DEFAULT, cost)
-    pp, ppd = ctypes.addressof(prob), ctypes.addressof(prob_d)
-    word = (ctypes.c_double * 2)()
-    q = ctypes.addressof(word)
+    pp, ppd, q = cartpole_pointers()
     lib = _native.lib()
     for t in ("f32", "f64"):
-        fn = getattr(lib, "pddp_closed_loop_" + t)
         #         B  N  S  Z  U  K  z0s   plant umin  umax  act   Xc Uc Jc st
         good = [2, 3, 1, q, q, q, None, None, None, None, None, q, q, q, q]
-
-        def call(problem, **change):
-            a = list(good)
-            for k, v in change.items():
-                a[int(k[1:])] = v
-            return fn(problem, *a, None)
+        call = caller(getattr(lib, "pddp_closed_loop_" + t), good)
 
         assert call(pp, _13=None) == -1, t             # Jc
         assert call(pp, _2=0) == -1, t                 # S
@@ -217,13 +132,13 @@ def test_closed_loop_is_position_independent():
     """The same controller in every b, the same (z0, plant row) in every s:
     all 210 columns and all statistics rows are the same bits."""
     B, N, S = 3, 12, 70
-    s, _, _, _ = _policy("cartpole", "f32", B, N)
+    s, _, _, _ = policy_solver("cartpole", "f32", B, N)
     for t in (s.Z, s.U, s.gains):
         t.copy_(t[0:1].expand_as(t).clone())
-    rows, _ = _plant_rows("cartpole", 1, 1, 33, "f32")
+    rows, _ = plant_rows("cartpole", 1, 1, 33, "f32")
     rows = np.tile(rows, (B, S, 1))
-    z0s = np.tile(_starts(s, 1, 133)[0:1], (B, S, 1))
-    out = _call(s, S, z0s=z0s, plant=rows)
+    z0s = np.tile(perturbed_starts(s, 1, 133)[0:1], (B, S, 1))
+    out = closed_loop_call(s, S, z0s=z0s, plant=rows)
     X = out.X.permute(1, 0, 2, 3).reshape(N + 1, B * S, -1)
     U = out.U.permute(1, 0, 2, 3).reshape(N, B * S, -1)
     assert torch.isfinite(out.J).all()
@@ -240,11 +155,11 @@ def test_closed_loop_reproduces_the_nominal(problem, dtype):
     """z0s = plant = NULL with feedback on: every rollout is the nominal and
     costs J_opt (S = 1 and S = 5)."""
     B, N = 3, 12
-    s, _, _, _ = _policy(problem, dtype, B, N)
-    tol = _tol(dtype)
+    s, _, _, _ = policy_solver(problem, dtype, B, N)
+    tol = record_tol(dtype)
     Z, J = s.Z.cpu().numpy(), s.J_opt.cpu().numpy()
     for S in (1, 5):
-        out = _call(s, S)
+        out = closed_loop_call(s, S)
         for i in range(S):
             e = (rel_err(out.X[:, :, i].cpu().numpy(), Z),
                  rel_err(out.J[:, i].cpu().numpy(), J))
@@ -259,40 +174,41 @@ def test_closed_loop_open_loop_equals_the_batch_rollout(problem, dtype):
     """gains = NULL, S = 1, plant rows given: the rollout of
     pddp_nominal_rollout_batch_* with those rows."""
     B, N = 5, 12
-    s, _, _, _ = _policy(problem, dtype, B, N)
-    par, xg, ug, _ = _perturbed(problem, B, seed=34)
-    _set_table(s, par, xg, ug)
+    s, _, _, _ = policy_solver(problem, dtype, B, N)
+    par, xg, ug, _ = perturbed(problem, B, seed=34)
+    set_table(s, par, xg, ug)
     s.nominal_rollout()
     rows = s.batch_table.cpu().numpy().reshape(B, 1, -1)
-    out = _call(s, 1, plant=rows, gains=None)
+    out = closed_loop_call(s, 1, plant=rows, gains=None)
     e = rel_err(out.X[:, :, 0].cpu().numpy(), s.Z.cpu().numpy())
     print(problem, dtype, e)
-    assert e < _tol(dtype), e
+    assert e < record_tol(dtype), e
 
 
 @gpu
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_closed_loop_nullables_and_masks(dtype):
     B, N, S = 3, 12, 5
-    s, _, _, _ = _policy("cartpole", dtype, B, N)
-    rows, _ = _plant_rows("cartpole", B, S, 35, dtype)
-    z0s = _starts(s, S, 135)
-    tol = _tol(dtype)
-    kept = _call(s, S, z0s=z0s, plant=rows)
+    s, _, _, _ = policy_solver("cartpole", dtype, B, N)
+    rows, _ = plant_rows("cartpole", B, S, 35, dtype)
+    z0s = perturbed_starts(s, S, 135)
+    tol = record_tol(dtype)
+    kept = closed_loop_call(s, S, z0s=z0s, plant=rows)
     # costs only
-    lean = _call(s, S, z0s=z0s, plant=rows, keep=False)
+    lean = closed_loop_call(s, S, z0s=z0s, plant=rows, keep=False)
     for nm in ("J", "stats"):
         a, b = getattr(lean, nm), getattr(kept, nm)
         print(dtype, nm, "costs-only == kept, bit for bit:",
               torch.equal(a, b))
         assert rel_err(a.cpu().numpy(), b.cpu().numpy()) < tol, nm
     # without statistics
-    bare = _call(s, S, z0s=z0s, plant=rows, stats=False)
+    bare = closed_loop_call(s, S, z0s=z0s, plant=rows, stats=False)
     assert torch.equal(bare.J, kept.J) and torch.equal(bare.X, kept.X)
     # active mask: the skipped keep the sentinel, the others their bits
     active = torch.tensor([1, 0, 1], dtype=torch.uint8, device="cuda")
     off = np.array([False, True, False])
-    got = _call(s, S, z0s=z0s, plant=rows, active=active, fill=SENTINEL)
+    got = closed_loop_call(s, S, z0s=z0s, plant=rows, active=active,
+                           fill=SENTINEL)
     for nm in ("X", "U", "J", "stats"):
         a, b = getattr(got, nm), getattr(kept, nm)
         assert bool((a[off] == SENTINEL).all()), nm
@@ -300,7 +216,7 @@ def test_closed_loop_nullables_and_masks(dtype):
     # one plant that diverges (a huge dt), unbounded
     wild = rows.copy()
     wild[1, 2, 0] = 1e30
-    out = _call(s, S, z0s=z0s, plant=wild, bounded=False)
+    out = closed_loop_call(s, S, z0s=z0s, plant=wild, bounded=False)
     J, st = out.J.cpu().numpy(), out.stats.cpu().numpy()
     assert not np.isfinite(J[1, 2])
     fin = np.isfinite(J)
@@ -310,7 +226,8 @@ def test_closed_loop_nullables_and_masks(dtype):
     assert (st[[0, 2], 3] == S).all()
     # no finite cost at all: mean = min = max = +inf, count 0
     wild[1, :, 0] = 1e30
-    st = _call(s, S, z0s=z0s, plant=wild, bounded=False).stats.cpu().numpy()
+    st = closed_loop_call(s, S, z0s=z0s, plant=wild,
+                          bounded=False).stats.cpu().numpy()
     assert np.array_equal(st[1], [np.inf, np.inf, np.inf, 0.0]), st[1]
     assert (st[[0, 2], 3] == S).all()
 
@@ -338,9 +255,9 @@ def test_closed_loop_through_the_public_interface():
     accepted policy once on its own row - the nominal and its cost - and
     leaves the solver as it was."""
     B, N, n_it = 6, 30, 12
-    s, _, z0, U, u_min, u_max = _setup("cartpole", "f64", B, N, seed=3)
-    par, xg, ug, _ = _perturbed("cartpole", B, seed=24)
-    _set_table(s, par, xg, ug)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f64", B, N, seed=3)
+    par, xg, ug, _ = perturbed("cartpole", B, seed=24)
+    set_table(s, par, xg, ug)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     s.fit(n_it)
     names = ("state", "mu", "delta", "Z", "U", "batch_table", "gains_acc",
@@ -356,7 +273,7 @@ def test_closed_loop_through_the_public_interface():
     assert np.allclose(J, Jopt, rtol=1e-7, atol=0)
     e = rel_err(r.X[:, :, 0].cpu().numpy(), s.Z.cpu().numpy())
     print("X", e)
-    assert e < _tol("f64"), e
+    assert e < record_tol("f64"), e
     assert torch.equal(r.stats[:, 0], r.J[:, 0])
     assert s.closed_loop().X is None
     for k in names:
@@ -366,9 +283,9 @@ def test_closed_loop_through_the_public_interface():
     # itself on hand-built rows.  params [B][S][P] over the table, x_goal
     # [B][na] the same for every s, u_goal left to the table.
     S = 4
-    z0s = _starts(s, S, 36)
-    par2, xg2, _, _ = _perturbed("cartpole", B * S, seed=37)
-    _, xg3, _, _ = _perturbed("cartpole", B, seed=38)
+    z0s = perturbed_starts(s, S, 36)
+    par2, xg2, _, _ = perturbed("cartpole", B * S, seed=37)
+    _, xg3, _, _ = perturbed("cartpole", B, seed=38)
     rows = s.batch_table.cpu().numpy()[:, None, :].repeat(S, 1)
     rows[:, :, 0:par2.shape[1]] = par2.reshape(B, S, -1)
     rows[:, :, 8:8 + xg3.shape[1]] = xg3[:, None, :]
@@ -379,14 +296,14 @@ def test_closed_loop_through_the_public_interface():
               params=torch.from_numpy(par2.reshape(B, S, -1)),
               x_goal=torch.from_numpy(xg3), keep=True)
     for accepted, g in ((True, s.gains_acc), (False, s.gains)):
-        want = _call(s, S, z0s=z0s, plant=rows, gains=g)
+        want = closed_loop_call(s, S, z0s=z0s, plant=rows, gains=g)
         r4 = s.closed_loop(accepted=accepted, **kw)
         for nm in ("X", "U", "J", "stats"):
             assert torch.equal(getattr(r4, nm), getattr(want, nm)), \
                 (accepted, nm)
     acc, last = s.closed_loop(**kw), s.closed_loop(accepted=False, **kw)
     assert not torch.equal(acc.J, last.J)  # (the two gain sets do differ)
-    open_loop = _call(s, S, z0s=z0s, plant=rows, gains=None)
+    open_loop = closed_loop_call(s, S, z0s=z0s, plant=rows, gains=None)
     assert torch.equal(s.closed_loop(feedback=False, **kw).J, open_loop.J)
     assert torch.equal(acc.X[:, 0], kw["z0"])
     assert bool((acc.stats[:, 3] == S).all())

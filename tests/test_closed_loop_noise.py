@@ -3,130 +3,33 @@ device (pddp_closed_loop_noisy_*, pddp_closed_loop_draws_*,
 csrc/closed_loop.hip, ILQRSolver.closed_loop(process_std=, obs_std=),
 ILQRSolver.closed_loop_draws).
 
-The draws are defined in include/pddp_hip.h; `model_draws` below restates them
-in numpy (Philox4x32-10 on a counter, Box-Muller on its words, everything past
-the exact uniforms in float64).  The rollouts are checked against the CPU
+The draws are defined in include/pddp_hip.h; `solver_util.model_draws` restates
+them in numpy (Philox4x32-10 on a counter, Box-Muller on its words, everything
+past the exact uniforms in float64).  The rollouts are checked against the CPU
 oracle stepped rollout by rollout under the noisy law with the MODEL's normals,
 so a device draw that differs from the model shows in two places."""
 import ctypes
-import os
-import re
-import types
 
 import numpy as np
 import pytest
 import torch
 
 import oracle as orc
+from abi_util import assert_entry_points, caller, cartpole_pointers
 from golden_util import np_dtype, rel_err
-from test_batch_problem import _tol
-from test_closed_loop import _plant_rows, _policy, _starts
-from test_closed_loop import _call as _plain_call
-from test_gpu_parity import PROBLEMS
+from solver_util import (check_stats, closed_loop_call, draws_call,
+                         model_draws, noisy_call, perturbed_starts,
+                         philox4x32_10, plant_rows, policy_solver, PROBLEMS,
+                         record_tol)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["pddp_closed_loop_noisy_f32", "pddp_closed_loop_noisy_f64",
            "pddp_closed_loop_draws_f32", "pddp_closed_loop_draws_f64"]
 STD = 0.02
 VARIANTS = {"process": (STD, None), "obs": (None, STD), "both": (STD, STD)}
 
-# ---- the numpy model of the draws ------------------------------------------
-_U = np.uint64
-_M0, _M1, _W0, _W1 = _U(0xD2511F53), _U(0xCD9E8D57), _U(0x9E3779B9), \
-    _U(0xBB67AE85)
-_LO, _32 = _U(0xffffffff), _U(32)
 
-
-def philox4x32_10(counter, key):
-    """counter: four uint64 arrays of 32-bit words, key: two words."""
-    c0, c1, c2, c3 = (np.asarray(c, _U) for c in counter)
-    k0, k1 = _U(key[0]), _U(key[1])
-    for _ in range(10):
-        p0, p1 = _M0 * c0, _M1 * c2  # (32 x 32 bits: fits 64)
-        c0, c1, c2, c3 = (p1 >> _32) ^ c1 ^ k0, p1 & _LO, \
-            (p0 >> _32) ^ c3 ^ k1, p0 & _LO
-        k0, k1 = (k0 + _W0) & _LO, (k1 + _W1) & _LO
-    return c0, c1, c2, c3
-
-
-def _box_muller(u1, u2):
-    r = np.sqrt(-2.0 * np.log(u1))
-    return r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)
-
-
-def model_draws(B, N, S, n, which, seed, offset, dtype):
-    """[B][N][S][n] float64: the unit normals of stream `which`."""
-    per = 4 if dtype == "f32" else 2
-    nb = -(-n // per)
-    shape = (B, N, S, nb)
-    r = (np.arange(B * S, dtype=_U) + _U(offset)).reshape(B, 1, S, 1)
-    t = np.arange(N, dtype=_U).reshape(1, N, 1, 1)
-    k = np.arange(nb, dtype=_U).reshape(1, 1, 1, nb)
-    counter = [np.broadcast_to(a, shape) for a in (
-        r & _LO, r >> _32, t, (_U(which) << _U(16)) | k)]
-    x = philox4x32_10(counter, (seed & 0xffffffff, seed >> 32))
-    if dtype == "f32":
-        u = [((w >> _U(9)).astype(np.float64) + 0.5) * 2.0 ** -23 for w in x]
-        z = _box_muller(u[0], u[1]) + _box_muller(u[2], u[3])
-    else:
-        u = [(((hi << _U(20)) | (lo >> _U(12))).astype(np.float64) + 0.5) *
-             2.0 ** -52 for hi, lo in ((x[0], x[1]), (x[2], x[3]))]
-        z = _box_muller(u[0], u[1])
-    return np.stack(z, -1).reshape(B, N, S, nb * per)[..., :n]
-
-
-# ---- the entry points themselves -------------------------------------------
-def _dev(a, s):
-    return None if a is None else torch.from_numpy(
-        np.ascontiguousarray(a)).to(dtype=s.dtype, device="cuda")
-
-
-def _std_vec(s, std):
-    return None if std is None else torch.full(
-        (s.n,), std, dtype=s.dtype, device="cuda")
-
-
-def _noisy_call(s, S, z0s=None, plant=None, w_std=None, v_std=None, seed=0,
-                offset=0, keep=True, stats=True, b0=0, gains="sweep"):
-    """pddp_closed_loop_noisy_* on trajectories b0.. of the solver's nominal
-    (z0s / plant: numpy, all B trajectories' or None; w_std / v_std: a float
-    for every component, a tensor or None)."""
-    from pddp_amd import _native
-    B, N, n, m = s.B - b0, s.N, s.n, s.m
-    opts = dict(dtype=s.dtype, device="cuda")
-    z0s_t = _dev(None if z0s is None else z0s[b0:], s)
-    plant_t = _dev(None if plant is None else plant[b0:], s)
-    w_t = w_std if torch.is_tensor(w_std) else _std_vec(s, w_std)
-    v_t = v_std if torch.is_tensor(v_std) else _std_vec(s, v_std)
-    g = s.gains if isinstance(gains, str) else gains
-    out = types.SimpleNamespace(
-        X=torch.empty(B, N + 1, S, n, **opts) if keep else None,
-        U=torch.empty(B, N, S, m, **opts) if keep else None,
-        J=torch.empty(B, S, **opts),
-        stats=torch.empty(B, 4, **opts) if stats else None)
-    p = _native.ptr
-    _native.call("pddp_closed_loop_noisy", s.dtype,
-                 ctypes.addressof(s.problem), B, N, S,
-                 p(s.Z[b0:].contiguous()), p(s.U[b0:].contiguous()),
-                 p(None if g is None else g[b0:].contiguous()), p(z0s_t),
-                 p(plant_t), p(s.u_min), p(s.u_max), p(w_t), p(v_t), seed,
-                 offset, None, p(out.X), p(out.U), p(out.J), p(out.stats),
-                 s._s())
-    torch.cuda.synchronize()
-    return out
-
-
-def _draws_call(B, N, S, n, which, seed, offset, dtype):
-    from pddp_amd import _native
-    td = torch.float32 if dtype == "f32" else torch.float64
-    W = torch.full((B, N, S, n), float("nan"), dtype=td, device="cuda")
-    _native.call("pddp_closed_loop_draws", td, B, N, S, n, which, seed,
-                 offset, _native.ptr(W), _native.stream_handle())
-    torch.cuda.synchronize()
-    return W
-
-
+# ---- what the rollouts should give ------------------------------------------
 def _oracle_noisy_rollouts(s, dtype, ops, z0s, u_min, u_max, w_std, v_std,
                            seed, offset=0):
     """(X [B][N+1][S][n], U [B][N][S][m], J [B][S]): the oracle's dynamics and
@@ -162,33 +65,13 @@ def _oracle_noisy_rollouts(s, dtype, ops, z0s, u_min, u_max, w_std, v_std,
     return X, Uo, J
 
 
-def _check_stats(out, dtype, S):
-    """As test_closed_loop_wider_than_a_wavefront: min, max and count exact,
-    the mean within S eps of numpy's on the returned costs."""
-    J, st = out.J.cpu().numpy(), out.stats.cpu().numpy()
-    assert np.isfinite(J).all() and (J > 0).all()
-    eps = 2.0 ** -23 if dtype == "f32" else 2.0 ** -52
-    for b in range(J.shape[0]):
-        assert st[b, 1] == J[b].min() and st[b, 2] == J[b].max(), b
-        assert st[b, 3] == S, b
-        mean = J[b].astype(np.float64).mean()
-        e = abs(float(st[b, 0]) - mean) / mean
-        assert e <= S * eps, (b, e, S * eps)
-
-
 # ---- CPU -------------------------------------------------------------------
 def test_noisy_entry_points_are_declared_exported_and_bound():
     """CPU: the four symbols in the header, the built library,
     exported_symbols() and _native._SIGS; the ABI version and
     pddp_closed_loop's 17 arguments as they were."""
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name), name
-        assert name in _native.exported_symbols(), name
-        assert name[:-4] in _native._SIGS, name
+    assert_entry_points(SYMBOLS)
     assert len(_native._SIGS["pddp_closed_loop"]) == 17
     assert len(_native._SIGS["pddp_closed_loop_noisy"]) == 21
     assert len(_native._SIGS["pddp_closed_loop_draws"]) == 9
@@ -207,31 +90,17 @@ def test_noisy_entry_points_refuse_before_any_launch():
     for a null W, a non-positive size, which outside {0, 1} and
     n > PDDP_MAX_STATE (8).  The non-null pointers are host words nobody
     reads."""
-    import pddp_amd
     from pddp_amd import _native
-    from pddp_amd.examples import cartpole
-    enc = pddp_amd.StateEncoding
-    model, cost = cartpole.CartpoleDynamicsModel(0.1), cartpole.CartpoleCost()
-    prob = model.native_problem(enc.IGNORE_UNCERTAINTY, cost)
-    prob_d = model.native_problem(enc.DEFAULT, cost)
-    pp, ppd = ctypes.addressof(prob), ctypes.addressof(prob_d)
-    word = (ctypes.c_double * 2)()
-    q = ctypes.addressof(word)
+    pp, ppd, q = cartpole_pointers()
     lib = _native.lib()
     for t in ("f32", "f64"):
-        fn = getattr(lib, "pddp_closed_loop_noisy_" + t)
         #       0  1  2  3  4  5  6     7     8     9     10 11 12 13
         #       B  N  S  Z  U  K  z0s   plant umin  umax  w  v  seed off
         good = [2, 3, 1, q, q, q, None, None, None, None, q, q, 7, 0,
                 #  14   15 16 17 18
                 #  act  Xc Uc Jc st
                 None, q, q, q, q]
-
-        def call(problem, **change):
-            a = list(good)
-            for k, v in change.items():
-                a[int(k[1:])] = v
-            return fn(problem, *a, None)
+        call = caller(getattr(lib, "pddp_closed_loop_noisy_" + t), good)
 
         assert call(pp, _17=None) == -1, t             # Jc
         assert call(pp, _0=0) == -1, t                 # B
@@ -249,15 +118,9 @@ def test_noisy_entry_points_refuse_before_any_launch():
         assert call(ppd, _11=None) == _native.E_UNSUPPORTED, t
         assert call(ppd, _15=None, _16=None) == _native.E_UNSUPPORTED, t
 
-        dr = getattr(lib, "pddp_closed_loop_draws_" + t)
         #        B  N  S  n  which seed off W
         dgood = [2, 3, 4, 4, 0, 7, 0, q]
-
-        def draws(**change):
-            a = list(dgood)
-            for k, v in change.items():
-                a[int(k[1:])] = v
-            return dr(*a, None)
+        draws = caller(getattr(lib, "pddp_closed_loop_draws_" + t), dgood)
 
         assert draws(_7=None) == -1, t                 # W
         for i in range(4):                             # B, N, S, n
@@ -279,7 +142,7 @@ def test_numpy_model_known_answers():
             (0xa4093822, 0x299f31d0),
             (0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1))]
     for counter, key, want in kat:
-        got = philox4x32_10([np.array([c], _U) for c in counter], key)
+        got = philox4x32_10([np.array([c], np.uint64) for c in counter], key)
         assert tuple(int(g[0]) for g in got) == want, (counter, got)
     a32 = model_draws(1, 1, 1, 4, 0, 2026, 0, "f32").ravel()
     a64 = model_draws(1, 1, 1, 2, 0, 2026, 0, "f64").ravel()
@@ -317,8 +180,8 @@ def test_draws_match_the_model(shape, dtype):
     worst = 0.0
     for which in (0, 1):
         for offset in (0, 5, 2 ** 32 - 3):
-            W = _draws_call(B, N, S, n, which, 2026, offset,
-                            dtype).cpu().numpy().astype(np.float64)
+            W = draws_call(B, N, S, n, which, 2026, offset,
+                           dtype).cpu().numpy().astype(np.float64)
             want = model_draws(B, N, S, n, which, 2026, offset, dtype)
             dev = (np.abs(W - want) / np.maximum(1.0, np.abs(want))).max()
             worst = max(worst, dev / eps)
@@ -328,13 +191,13 @@ def test_draws_match_the_model(shape, dtype):
 
 
 def _check_noisy_vs_oracle(problem, dtype, B, N, S, seed):
-    s, _, u_min, u_max = _policy(problem, dtype, B, N)
-    rows, ops = _plant_rows(problem, B, S, seed, dtype)
-    z0s = _starts(s, S, seed + 100)
-    tol = _tol(dtype)
+    s, _, u_min, u_max = policy_solver(problem, dtype, B, N)
+    rows, ops = plant_rows(problem, B, S, seed, dtype)
+    z0s = perturbed_starts(s, S, seed + 100)
+    tol = record_tol(dtype)
     for name, (w_std, v_std) in VARIANTS.items():
-        out = _noisy_call(s, S, z0s=z0s, plant=rows, w_std=w_std, v_std=v_std,
-                          seed=11)
+        out = noisy_call(s, S, z0s=z0s, plant=rows, w_std=w_std, v_std=v_std,
+                         seed=11)
         X, U, J = _oracle_noisy_rollouts(s, dtype, ops, z0s, u_min, u_max,
                                          w_std, v_std, seed=11)
         for b in range(B):
@@ -343,11 +206,11 @@ def _check_noisy_vs_oracle(problem, dtype, B, N, S, seed):
                  rel_err(out.J[b].cpu().numpy(), J[b]))
             print(problem, dtype, S, name, b, e)
             assert max(e) < tol, (name, b, e)
-        _check_stats(out, dtype, S)
+        check_stats(out, dtype, S)
         # (the bar tells the noise from none: 0.02 per step on states of
         # order 1 to 10 is far above it, as the plain launch's states show)
         if name == "both":
-            plain = _plain_call(s, S, z0s=z0s, plant=rows)
+            plain = closed_loop_call(s, S, z0s=z0s, plant=rows)
             d = rel_err(plain.X.cpu().numpy(), X)
             print(problem, dtype, S, "plain rollout off by", d)
             assert d > 5 * tol, d
@@ -374,25 +237,25 @@ def test_noisy_rollouts_wider_than_a_wavefront(dtype):
 @pytest.mark.parametrize("S", [5, 70])
 def test_noise_is_reproducible_and_offsets_shift_it(S, dtype):
     B, N = 3, 12
-    s, _, _, _ = _policy("cartpole", dtype, B, N)
-    rows, _ = _plant_rows("cartpole", B, S, 35, dtype)
-    z0s = _starts(s, S, 135)
+    s, _, _, _ = policy_solver("cartpole", dtype, B, N)
+    rows, _ = plant_rows("cartpole", B, S, 35, dtype)
+    z0s = perturbed_starts(s, S, 135)
     kw = dict(z0s=z0s, plant=rows, w_std=STD, v_std=STD)
-    a = _noisy_call(s, S, seed=7, **kw)
-    b = _noisy_call(s, S, seed=7, **kw)
+    a = noisy_call(s, S, seed=7, **kw)
+    b = noisy_call(s, S, seed=7, **kw)
     for nm in ("J", "X", "U", "stats"):
         assert torch.equal(getattr(a, nm), getattr(b, nm)), nm
-    lean = _noisy_call(s, S, seed=7, keep=False, **kw)
+    lean = noisy_call(s, S, seed=7, keep=False, **kw)
     assert torch.equal(lean.J, a.J) and torch.equal(lean.stats, a.stats)
-    other = _noisy_call(s, S, seed=8, **kw)
+    other = noisy_call(s, S, seed=8, **kw)
     assert not torch.equal(other.J, a.J)
     assert not bool((other.J == a.J).any())
     # trajectories 1 .. B-1 alone, placed where they were in the batch
-    tail = _noisy_call(s, S, seed=7, offset=S, b0=1, **kw)
+    tail = noisy_call(s, S, seed=7, offset=S, b0=1, **kw)
     for nm in ("J", "X", "U", "stats"):
         assert torch.equal(getattr(tail, nm), getattr(a, nm)[1:]), nm
     # (and without the offset they see trajectory 0's noise instead)
-    moved = _noisy_call(s, S, seed=7, offset=0, b0=1, **kw)
+    moved = noisy_call(s, S, seed=7, offset=0, b0=1, **kw)
     assert not torch.equal(moved.J, a.J[1:])
 
 
@@ -400,13 +263,13 @@ def test_noise_is_reproducible_and_offsets_shift_it(S, dtype):
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_zero_noise_is_the_plain_rollout(dtype):
     B, N, S = 3, 12, 5
-    s, _, _, _ = _policy("cartpole", dtype, B, N)
-    rows, _ = _plant_rows("cartpole", B, S, 36, dtype)
-    z0s = _starts(s, S, 136)
-    plain = _plain_call(s, S, z0s=z0s, plant=rows)
-    zero = _noisy_call(s, S, z0s=z0s, plant=rows, w_std=0.0, v_std=0.0,
-                       seed=3)
-    tol = _tol(dtype)
+    s, _, _, _ = policy_solver("cartpole", dtype, B, N)
+    rows, _ = plant_rows("cartpole", B, S, 36, dtype)
+    z0s = perturbed_starts(s, S, 136)
+    plain = closed_loop_call(s, S, z0s=z0s, plant=rows)
+    zero = noisy_call(s, S, z0s=z0s, plant=rows, w_std=0.0, v_std=0.0,
+                      seed=3)
+    tol = record_tol(dtype)
     for nm in ("X", "U", "J", "stats"):
         a, b = getattr(zero, nm), getattr(plain, nm)
         print(dtype, nm, "zero noise == plain, bit for bit:",
@@ -422,11 +285,11 @@ def test_solver_closed_loop_keywords():
     accepted nothing are zero.)"""
     from pddp_amd import _native
     B, N, S = 3, 12, 5
-    s, _, _, _ = _policy("cartpole", "f64", B, N)
+    s, _, _, _ = policy_solver("cartpole", "f64", B, N)
     same = lambda a, b: all(
         torch.equal(getattr(a, nm), getattr(b, nm)) for nm in ("J", "stats"))
     r = s.closed_loop(samples=S, process_std=STD, seed=7, accepted=False)
-    want = _noisy_call(s, S, w_std=STD, seed=7, keep=False)
+    want = noisy_call(s, S, w_std=STD, seed=7, keep=False)
     assert r.X is None and same(r, want)
     # a scalar and an [n] vector agree; obs_std, sample_offset and keep go
     # through
@@ -436,23 +299,23 @@ def test_solver_closed_loop_keywords():
     levels = torch.tensor([0.01, 0.02, 0.03, 0.04], dtype=torch.float64)
     r = s.closed_loop(samples=S, process_std=levels, obs_std=0.5 * levels,
                       seed=9, sample_offset=40, accepted=False, keep=True)
-    want = _noisy_call(s, S, w_std=levels.cuda(), v_std=(0.5 * levels).cuda(),
-                       seed=9, offset=40)
+    want = noisy_call(s, S, w_std=levels.cuda(), v_std=(0.5 * levels).cuda(),
+                      seed=9, offset=40)
     assert same(r, want) and torch.equal(r.X, want.X) and \
         torch.equal(r.U, want.U)
     r = s.closed_loop(samples=S, obs_std=STD, seed=7, accepted=False)
-    assert same(r, _noisy_call(s, S, v_std=STD, seed=7, keep=False))
+    assert same(r, noisy_call(s, S, v_std=STD, seed=7, keep=False))
     with pytest.raises(_native.NativeError):
         s.closed_loop(samples=S, process_std=torch.ones(3), accepted=False)
     # without the keywords: the plain entry point, as before
     r = s.closed_loop(samples=S, accepted=False, keep=True)
-    want = _plain_call(s, S)
+    want = closed_loop_call(s, S)
     assert same(r, want) and torch.equal(r.X, want.X)
     # the draws
     for which, w in (("process", 0), ("obs", 1)):
         W = s.closed_loop_draws(S, which=which, seed=7, sample_offset=3)
         assert tuple(W.shape) == (B, N, S, s.n)
-        assert torch.equal(W, _draws_call(B, N, S, s.n, w, 7, 3, "f64"))
+        assert torch.equal(W, draws_call(B, N, S, s.n, w, 7, 3, "f64"))
     with pytest.raises(_native.NativeError):
         s.closed_loop_draws(S, which="both")
     # under a reference closed_loop refuses, with or without noise

@@ -13,8 +13,6 @@ and row, so a kernel that costs under the plant row's goals, under a
 neighbour's row or without the clamp is orders of magnitude above the bars -
 the project's own, the line search's: 1e-10 in f64, 2e-4 in f32."""
 import ctypes
-import os
-import re
 import types
 
 import numpy as np
@@ -22,20 +20,16 @@ import pytest
 import torch
 
 import oracle as orc
+from abi_util import assert_entry_points, caller, cartpole_pointers
 from golden_util import DT, np_dtype, rel_err
-from test_batch_problem import _tol
-from test_closed_loop import _call as _plain_call
-from test_closed_loop import _plant_rows, _policy, _starts
-from test_closed_loop_noise import _check_stats, _dev, _noisy_call, \
-    _std_vec, model_draws
-from test_gpu_parity import PROBLEMS
-from test_reference_tracking import _fresh_ops, _loop_solver, _ref_tensor, \
-    _reference, _row, _same_bits, _set_ref, _under
+from solver_util import (check_stats, closed_loop_call, fresh_ops, loop_solver,
+                         model_draws, noisy_call, perturbed, perturbed_starts,
+                         plant_rows, policy_solver, PROBLEMS, record_tol,
+                         ref_row, ref_tensor, reference_rows, same_bits,
+                         SENTINEL, set_ref, std_vec, to_device, under_row)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["pddp_closed_loop_track_f32", "pddp_closed_loop_track_f64"]
-SENTINEL = -7.25
 STD = 0.02
 NOISE = {"none": (None, None), "process": (STD, None), "obs": (None, STD),
          "both": (STD, STD)}
@@ -51,13 +45,7 @@ def test_tracked_entry_points_are_declared_exported_and_bound():
     and _native._SIGS, with the two uint64 words where the header has them;
     the siblings' argument counts and the ABI version as they were."""
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name), name
-        assert name in _native.exported_symbols(), name
-        assert name[:-4] in _native._SIGS, name
+    assert_entry_points(SYMBOLS)
     sig = _native._SIGS["pddp_closed_loop_track"]
     # the noisy sibling's arguments + (ref, ref_len, ref_t0) after the problem
     assert len(sig) == len(_native._SIGS["pddp_closed_loop_noisy"]) + 3 == 24
@@ -80,31 +68,17 @@ def test_tracked_entry_points_refuse_before_any_launch():
     before the problem's, so a DEFAULT-encoding problem with no noise answers
     PDDP_E_UNSUPPORTED, where pddp_closed_loop_noisy_* answers PDDP_E_BADARG
     for the same call.  That such a launch RUNS is the GPU tests' to show."""
-    import pddp_amd
     from pddp_amd import _native
-    from pddp_amd.examples import cartpole
-    enc = pddp_amd.StateEncoding
-    model, cost = cartpole.CartpoleDynamicsModel(0.1), cartpole.CartpoleCost()
-    prob = model.native_problem(enc.IGNORE_UNCERTAINTY, cost)
-    prob_d = model.native_problem(enc.DEFAULT, cost)
-    pp, ppd = ctypes.addressof(prob), ctypes.addressof(prob_d)
-    word = (ctypes.c_double * 2)()
-    q = ctypes.addressof(word)
+    pp, ppd, q = cartpole_pointers()
     lib = _native.lib()
     for t in ("f32", "f64"):
-        fn = getattr(lib, "pddp_closed_loop_track_" + t)
         #       0    1    2   3  4  5  6  7  8  9     10    11    12
         #       ref  len  t0  B  N  S  Z  U  K  z0s   plant umin  umax
         good = [q, 5, 0, 2, 3, 1, q, q, q, None, None, None, None,
                 # 13 14 15   16   17    18 19 20 21
                 # w  v  seed off  act   Xc Uc Jc st
                 q, q, 7, 0, None, q, q, q, q]
-
-        def call(problem, **change):
-            a = list(good)
-            for k, v in change.items():
-                a[int(k[1:])] = v
-            return fn(problem, *a, None)
+        call = caller(getattr(lib, "pddp_closed_loop_track_" + t), good)
 
         assert call(pp, _0=None) == -1, t              # ref
         assert call(pp, _1=0) == -1, t                 # ref_len
@@ -150,9 +124,9 @@ def _track_call(s, S, ref, t0, z0s=None, plant=None, w_std=None, v_std=None,
         return torch.empty(*shape, **opts) if fill is None else \
             torch.full(shape, fill, **opts)
 
-    z0s_t = _dev(None if z0s is None else z0s[b0:], s)
-    plant_t = _dev(None if plant is None else plant[b0:], s)
-    w_t, v_t = _std_vec(s, w_std), _std_vec(s, v_std)
+    z0s_t = to_device(None if z0s is None else z0s[b0:], s.dtype)
+    plant_t = to_device(None if plant is None else plant[b0:], s.dtype)
+    w_t, v_t = std_vec(s, w_std), std_vec(s, v_std)
     g = s.gains if isinstance(gains, str) else gains
     out = types.SimpleNamespace(
         X=buf(B, N + 1, S, n) if keep else None,
@@ -174,9 +148,9 @@ def _track_call(s, S, ref, t0, z0s=None, plant=None, w_std=None, v_std=None,
 
 def _untracked_call(s, S, z0s, plant, w_std, v_std, seed, offset=0):
     if w_std is None and v_std is None:
-        return _plain_call(s, S, z0s=z0s, plant=plant)
-    return _noisy_call(s, S, z0s=z0s, plant=plant, w_std=w_std, v_std=v_std,
-                       seed=seed, offset=offset)
+        return closed_loop_call(s, S, z0s=z0s, plant=plant)
+    return noisy_call(s, S, z0s=z0s, plant=plant, w_std=w_std, v_std=v_std,
+                      seed=seed, offset=offset)
 
 
 def _oracle_tracked(s, dtype, ops, z0s, u_min, u_max, xr, ur, t0, w_std,
@@ -208,13 +182,13 @@ def _oracle_tracked(s, dtype, ops, z0s, u_min, u_max, xr, ur, t0, w_std,
                 u = np.clip(U[b, t] + K[b, t] @ (y - Z[b, t]), u_min, u_max)
                 u = u.astype(d)
                 X[b, t, i], Uo[b, t, i] = x, u
-                J[b, i] += o.cost(_under(p, xr[b], ur[b], _row(L, t0, t)),
+                J[b, i] += o.cost(under_row(p, xr[b], ur[b], ref_row(L, t0, t)),
                                   x, u)[0]
                 x = o.dynamics(p, x, u, jac=False)[0]
                 if Wn is not None:
                     x = x + Wn[b, t, i]
             X[b, N, i] = x
-            J[b, i] += o.cost(_under(p, xr[b], ur[b], _row(L, t0, N)), x,
+            J[b, i] += o.cost(under_row(p, xr[b], ur[b], ref_row(L, t0, N)), x,
                               None, terminal=True)[0]
     return X, Uo, J
 
@@ -232,16 +206,16 @@ def _assert_close(out, want, tol, what):
     return worst
 
 
-def _inputs(problem, dtype, B, N, S, L, seed):
+def _track_inputs(problem, dtype, B, N, S, L, seed):
     """A policy, perturbed plants (the goal fields of plant (0, 0) far off:
     they are not read) with the oracle's problem of each, perturbed starts and
     a reference of L rows."""
     from pddp_amd import _native as N_
-    s, _, u_min, u_max = _policy(problem, dtype, B, N)
-    rows, ops = _plant_rows(problem, B, S, seed, dtype)
+    s, _, u_min, u_max = policy_solver(problem, dtype, B, N)
+    rows, ops = plant_rows(problem, B, S, seed, dtype)
     rows[0, 0, N_.BATCH_X_GOAL:N_.BATCH_U_GOAL + N_.MAX_ACTION] = 1e3
-    z0s = _starts(s, S, seed + 100)
-    xr, ur = _reference(problem, B, L, seed + 200)
+    z0s = perturbed_starts(s, S, seed + 100)
+    xr, ur = reference_rows(problem, B, L, seed + 200)
     return s, u_min, u_max, rows, ops, z0s, xr, ur
 
 
@@ -259,17 +233,17 @@ def test_tracked_rollouts_vs_oracle(problem, dtype):
     launch on the same inputs is more than 100 bars away in J: the bar tells
     tracking from none."""
     B, N, S, L, t0 = 3, 12, 5, 20, 2
-    s, u_min, u_max, rows, ops, z0s, xr, ur = _inputs(problem, dtype, B, N,
-                                                      S, L, seed=51)
-    ref = _ref_tensor(xr, ur, dtype)
-    tol = _tol(dtype)
+    s, u_min, u_max, rows, ops, z0s, xr, ur = _track_inputs(
+        problem, dtype, B, N, S, L, seed=51)
+    ref = ref_tensor(xr, ur, dtype)
+    tol = record_tol(dtype)
     for name, (w_std, v_std) in NOISE.items():
         out = _track_call(s, S, ref, t0, z0s=z0s, plant=rows, w_std=w_std,
                           v_std=v_std, seed=11)
         want = _oracle_tracked(s, dtype, ops, z0s, u_min, u_max, xr, ur, t0,
                                w_std, v_std, seed=11)
         _assert_close(out, want, tol, (problem, dtype, name))
-        _check_stats(out, dtype, S)
+        check_stats(out, dtype, S)
         plain = _untracked_call(s, S, z0s, rows, w_std, v_std, seed=11)
         far = min(rel_err(plain.J[b].cpu().numpy(), want[2][b])
                   for b in range(B))
@@ -291,14 +265,14 @@ def test_tracked_rollouts_hold_the_last_row(problem, dtype, case):
     L, t0 = {"short": (4, 1), "clamped_on_entry": (4, 50),
              "exact_end": (15, 2)}[case]
     assert case != "exact_end" or t0 + N == L - 1
-    s, u_min, u_max, rows, ops, z0s, xr, ur = _inputs(problem, dtype, B, N,
-                                                      S, L, seed=52)
-    out = _track_call(s, S, _ref_tensor(xr, ur, dtype), t0, z0s=z0s,
+    s, u_min, u_max, rows, ops, z0s, xr, ur = _track_inputs(
+        problem, dtype, B, N, S, L, seed=52)
+    out = _track_call(s, S, ref_tensor(xr, ur, dtype), t0, z0s=z0s,
                       plant=rows, w_std=STD, v_std=STD, seed=12)
     want = _oracle_tracked(s, dtype, ops, z0s, u_min, u_max, xr, ur, t0, STD,
                            STD, seed=12)
-    _assert_close(out, want, _tol(dtype), (problem, dtype, case))
-    _check_stats(out, dtype, S)
+    _assert_close(out, want, record_tol(dtype), (problem, dtype, case))
+    check_stats(out, dtype, S)
 
 
 @gpu
@@ -310,14 +284,14 @@ def test_tracked_rollouts_wider_than_a_wavefront(dtype):
     wavefronts through LDS.  The goals travel in registers at every S: there
     is no second path to cover."""
     B, N, S, L, t0 = 3, 12, 70, 20, 2
-    s, u_min, u_max, rows, ops, z0s, xr, ur = _inputs("cartpole", dtype, B,
-                                                      N, S, L, seed=53)
-    out = _track_call(s, S, _ref_tensor(xr, ur, dtype), t0, z0s=z0s,
+    s, u_min, u_max, rows, ops, z0s, xr, ur = _track_inputs(
+        "cartpole", dtype, B, N, S, L, seed=53)
+    out = _track_call(s, S, ref_tensor(xr, ur, dtype), t0, z0s=z0s,
                       plant=rows, w_std=STD, v_std=STD, seed=13)
     want = _oracle_tracked(s, dtype, ops, z0s, u_min, u_max, xr, ur, t0, STD,
                            STD, seed=13)
-    _assert_close(out, want, _tol(dtype), ("cartpole", dtype, S))
-    _check_stats(out, dtype, S)
+    _assert_close(out, want, record_tol(dtype), ("cartpole", dtype, S))
+    check_stats(out, dtype, S)
 
 
 @gpu
@@ -331,14 +305,14 @@ def test_constant_reference_equals_the_untracked_launches(problem, dtype):
     DESIGN 3.4e differ in the last bit for the cartpole in f64)."""
     from pddp_amd import _native as N_
     B, N, S, L = 3, 12, 5, 7
-    s, _, _, _ = _policy(problem, dtype, B, N)
-    z0s = _starts(s, S, 154)
+    s, _, _, _ = policy_solver(problem, dtype, B, N)
+    z0s = perturbed_starts(s, S, 154)
     shared = s._shared_row().cpu().numpy().astype(np.float64)
     na, m = s.problem.aug_size, s.m
     xr = np.tile(shared[N_.BATCH_X_GOAL:N_.BATCH_X_GOAL + na], (B, L, 1))
     ur = np.tile(shared[N_.BATCH_U_GOAL:N_.BATCH_U_GOAL + m], (B, L, 1))
-    ref = _ref_tensor(xr, ur, dtype)
-    tol = _tol(dtype)
+    ref = ref_tensor(xr, ur, dtype)
+    tol = record_tol(dtype)
     for name, (w_std, v_std) in (("none", NOISE["none"]),
                                  ("both", NOISE["both"])):
         got = _track_call(s, S, ref, 3, z0s=z0s, w_std=w_std, v_std=v_std,
@@ -360,12 +334,12 @@ def test_states_and_actions_do_not_depend_on_the_reference(problem, dtype):
     kernel on inputs that differ only in values the dynamics never read.  X
     and U are the same bits, J differs."""
     B, N, S, L = 3, 12, 5, 20
-    s, _, _, rows, _, z0s, xr, ur = _inputs(problem, dtype, B, N, S, L,
-                                            seed=55)
-    xr2, ur2 = _reference(problem, B, L, seed=999)
+    s, _, _, rows, _, z0s, xr, ur = _track_inputs(
+        problem, dtype, B, N, S, L, seed=55)
+    xr2, ur2 = reference_rows(problem, B, L, seed=999)
     kw = dict(z0s=z0s, plant=rows, w_std=STD, v_std=STD, seed=15)
-    a = _track_call(s, S, _ref_tensor(xr, ur, dtype), 2, **kw)
-    b = _track_call(s, S, _ref_tensor(xr2, ur2, dtype), 2, **kw)
+    a = _track_call(s, S, ref_tensor(xr, ur, dtype), 2, **kw)
+    b = _track_call(s, S, ref_tensor(xr2, ur2, dtype), 2, **kw)
     assert torch.equal(a.X, b.X) and torch.equal(a.U, b.U)
     assert not bool((a.J == b.J).any())
 
@@ -380,9 +354,9 @@ def test_tracked_launch_repeats_offsets_and_masks(S, dtype):
     mask: the skipped trajectory's outputs stay as the caller filled them,
     the others keep their bits."""
     B, N, L, t0 = 3, 12, 9, 2
-    s, _, _, rows, _, z0s, xr, ur = _inputs("cartpole", dtype, B, N, S, L,
-                                            seed=56)
-    ref = _ref_tensor(xr, ur, dtype)
+    s, _, _, rows, _, z0s, xr, ur = _track_inputs(
+        "cartpole", dtype, B, N, S, L, seed=56)
+    ref = ref_tensor(xr, ur, dtype)
     kw = dict(z0s=z0s, plant=rows, w_std=STD, v_std=STD, seed=7, offset=40)
     a = _track_call(s, S, ref, t0, **kw)
     b = _track_call(s, S, ref, t0, **kw)
@@ -413,13 +387,12 @@ def test_solver_and_controller_follow_the_reference():
     import pddp_amd
     from pddp_amd import _native
     from pddp_amd.examples import cartpole
-    from test_batch_problem import _perturbed
     B, N, S, L = 3, 12, 5, 20
-    s, _, u_min, u_max = _policy("cartpole", "f64", B, N)
+    s, _, u_min, u_max = policy_solver("cartpole", "f64", B, N)
     with pytest.raises(_native.NativeError, match="reference"):
         s.closed_loop(samples=S, track=True)   # no reference is set
-    xr, ur = _reference("cartpole", B, L, seed=57)
-    _set_ref(s, xr, ur, 2)
+    xr, ur = reference_rows("cartpole", B, L, seed=57)
+    set_ref(s, xr, ur, 2)
     with pytest.raises(_native.NativeError, match="reference"):
         s.closed_loop(samples=S)               # as before
     with pytest.raises(_native.NativeError, match="reference"):
@@ -429,8 +402,8 @@ def test_solver_and_controller_follow_the_reference():
         with pytest.raises(_native.NativeError, match="goal"):
             s.closed_loop(samples=S, track=True, **kw)
     # against the entry point: plant rows = the shared row + params
-    z0s = _starts(s, S, 157)
-    par, _, _, _ = _perturbed("cartpole", B * S, seed=58)
+    z0s = perturbed_starts(s, S, 157)
+    par, _, _, _ = perturbed("cartpole", B * S, seed=58)
     par = par.reshape(B, S, -1)
     rows = np.tile(s._shared_row().cpu().numpy(), (B, S, 1))
     rows[:, :, :par.shape[2]] = par
@@ -453,26 +426,26 @@ def test_solver_and_controller_follow_the_reference():
             assert torch.equal(getattr(r, nm), getattr(want, nm)), (noise, nm)
     assert s.closed_loop(samples=S, track=True, accepted=False).X is None
     for k in names:
-        assert _same_bits(getattr(s, k), before[k]), k
+        assert same_bits(getattr(s, k), before[k]), k
     assert s.ref_start == 2 and s._graph is graph and s._plan(0) == plan
 
     # after two MPC control steps the window stands two rows further on
-    m_ = _loop_solver("cartpole", "f64", B, N)
-    _set_ref(m_, xr, ur, 1)
+    m_ = loop_solver("cartpole", "f64", B, N)
+    set_ref(m_, xr, ur, 1)
     m_.mpc_closed_loop(2, 2)
     assert m_.ref_start == 3
-    z0m = _starts(m_, S, 158)
+    z0m = perturbed_starts(m_, S, 158)
     r = m_.closed_loop(z0=torch.from_numpy(z0m), track=True, keep=True,
                        accepted=False)
     torch.cuda.synchronize()
-    ops = [[op] * S for op in _fresh_ops("cartpole", B)]
+    ops = [[op] * S for op in fresh_ops("cartpole", B)]
     um, uM = m_.u_min.cpu().numpy(), m_.u_max.cpu().numpy()
     want = _oracle_tracked(m_, "f64", ops, z0m, um, uM, xr, ur, 1 + 2, None,
                            None, seed=0)
-    _assert_close(r, want, _tol("f64"), ("after mpc_closed_loop",))
+    _assert_close(r, want, record_tol("f64"), ("after mpc_closed_loop",))
     stale = _oracle_tracked(m_, "f64", ops, z0m, um, uM, xr, ur, 1, None,
                             None, seed=0)
-    assert rel_err(r.J.cpu().numpy(), stale[2]) > 100 * _tol("f64")
+    assert rel_err(r.J.cpu().numpy(), stale[2]) > 100 * record_tol("f64")
     assert m_.ref_start == 3
 
     # the controller forwards the keyword and returns the trial tuple
@@ -486,7 +459,7 @@ def test_solver_and_controller_follow_the_reference():
     ctrl.fit(U0, encoding=enc, n_iterations=4, z0=z0, quiet=True)
     with pytest.raises(_native.NativeError, match="reference"):
         ctrl.closed_loop(samples=S, track=True)
-    xc, uc = _reference("cartpole", B, Nc + 1, seed=59)
+    xc, uc = reference_rows("cartpole", B, Nc + 1, seed=59)
     ctrl.set_reference(torch.from_numpy(xc), torch.from_numpy(uc))
     (X, Ua, dX), J = ctrl.closed_loop(track=True, samples=S, obs_std=STD,
                                       seed=5)

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pddp_amd  # noqa: E402
 from pddp_amd import GaussianVariable, StateEncoding  # noqa: E402
 from pddp_amd.models.gp import gp_dynamics_model_factory  # noqa: E402
+from gp_util import max_rel, system_model, system_rows, SYSTEMS  # noqa: E402
 
 
 def _toy(seed=0, M=14, angular=(2,)):
@@ -188,34 +189,6 @@ def test_gp_controller_on_gpu_matches_cpu_model():
 
 
 # ---- the HIP kernel of the moment-matched step (csrc/gp_step.hip) -------------
-_SYSTEMS = {"pendulum": (2, 1, [0]), "cartpole": (4, 1, [2]),
-            "double_cartpole": (6, 1, [1, 2])}
-
-
-def _system_model(system, M, dtype, seed=0):
-    D, m, ang = _SYSTEMS[system]
-    g = torch.Generator().manual_seed(seed)
-    X = torch.randn(M, D, generator=g, dtype=torch.float64)
-    U = torch.randn(M, m, generator=g, dtype=torch.float64)
-    dX = 0.3 * torch.sin(X @ torch.randn(D, D, generator=g,
-                                          dtype=torch.float64)) + 0.2 * U
-    model = gp_dynamics_model_factory(D, m, ang)().double()
-    model.fit(X, U, dX)
-    return model.to(dtype).cuda(), (X, U, dX)
-
-
-def _system_rows(system, R, encoding, dtype, seed=1, spread=0.2):
-    from pddp_amd.utils.encoding import encode
-    D, m, _ = _SYSTEMS[system]
-    g = torch.Generator().manual_seed(seed)
-    mean = 0.5 * torch.randn(R, D, generator=g, dtype=torch.float64)
-    A = spread * torch.randn(R, D, D, generator=g, dtype=torch.float64)
-    C = A @ A.transpose(-1, -2) + 1e-3 * torch.eye(D, dtype=torch.float64)
-    z = encode(mean, C=C, encoding=encoding)
-    u = torch.randn(R, m, generator=g, dtype=torch.float64)
-    return z.to(dtype).cuda(), u.to(dtype).cuda()
-
-
 def _torch_step(model, z, u, encoding, jacobian):
     """The torch module with the kernel switched off; Jacobians by autograd,
     one replica of the row per output (controllers/plugin.py _dyn_derivs)."""
@@ -237,12 +210,8 @@ def _torch_step(model, z, u, encoding, jacobian):
         model.use_native = True
 
 
-def _rel(a, b):
-    return float((a - b).abs().max() / (b.abs().max() + 1e-300))
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("system", sorted(_SYSTEMS))
+@pytest.mark.parametrize("system", sorted(SYSTEMS))
 @pytest.mark.parametrize("encoding", [1, 2, 3, 4])
 @pytest.mark.parametrize("dtype,tol_step,tol_jac", [
     (torch.float64, 1e-11, 1e-10), (torch.float32, 2e-5, 5e-4)])
@@ -253,8 +222,8 @@ def test_gp_step_kernel_vs_torch_module(system, encoding, dtype, tol_step,
     through it: three systems, four encodings, both dtypes; 66 training points
     (more than one tile of 64 lanes)."""
     enc = StateEncoding(encoding)
-    model, _ = _system_model(system, 66, dtype)
-    z, u = _system_rows(system, 19, enc, dtype)
+    model, _ = system_model(system, 66, dtype)
+    z, u = system_rows(system, 19, enc, dtype)
     assert model.native_ok(z, enc, jacobian=True)
     ref, Fz_r, Fu_r = _torch_step(model, z, u, enc, True)
     out, Fz, Fu = model.native_step(z, u, enc, jacobian=True)
@@ -271,11 +240,11 @@ def test_gp_step_kernel_vs_torch_module(system, encoding, dtype, tol_step,
                                      (plain, ref, r64, tol_step),
                                      (Fz, Fz_r, Fz64, tol_jac),
                                      (Fu, Fu_r, Fu64, tol_jac)):
-            assert _rel(got.double(), exact) < max(
-                tol, 4.0 * _rel(tor.double(), exact))
+            assert max_rel(got.double(), exact) < max(
+                tol, 4.0 * max_rel(tor.double(), exact))
     else:
-        assert _rel(out, ref) < tol_step and _rel(plain, ref) < tol_step
-        assert _rel(Fz, Fz_r) < tol_jac and _rel(Fu, Fu_r) < tol_jac
+        assert max_rel(out, ref) < tol_step and max_rel(plain, ref) < tol_step
+        assert max_rel(Fz, Fz_r) < tol_jac and max_rel(Fu, Fu_r) < tol_jac
     # and `forward` itself goes through the kernel when nobody can ask for
     # gradients
     with torch.no_grad():
@@ -288,13 +257,13 @@ def test_gp_step_kernel_vs_numpy_port():
     """The kernel against the independent numpy restatement
     (oracle/gp_port.py `step`), fp64, cartpole-shaped."""
     from pddp_amd.utils.encoding import decode_covar, decode_mean
-    model, (X, U, dX) = _system_model("cartpole", 33, torch.float64, seed=4)
+    model, (X, U, dX) = system_model("cartpole", 33, torch.float64, seed=4)
     gp, ell, sf2, sn2 = _oracle_state(model.cpu())
     Xt = model.Xt.cpu().numpy()
     Kinv, beta = gp.condition(Xt, dX.numpy(), ell, sf2, sn2)
     model = model.cuda()
     enc = StateEncoding.DEFAULT
-    z, u = _system_rows("cartpole", 5, enc, torch.float64, seed=6)
+    z, u = system_rows("cartpole", 5, enc, torch.float64, seed=6)
     zn = model.native_step(z, u, enc).cpu()
     for r in range(5):
         mean = decode_mean(z[r].cpu(), enc, state_size=4).numpy()
@@ -312,9 +281,9 @@ def test_gp_step_kernel_refuses_what_it_does_not_cover():
     """Full-covariance encoding and unbuilt shapes stay on the torch path
     (native_ok False); the C entry point itself returns PDDP_E_UNSUPPORTED."""
     from pddp_amd import _native
-    model, _ = _system_model("cartpole", 20, torch.float64)
+    model, _ = system_model("cartpole", 20, torch.float64)
     enc = StateEncoding.FULL_COVARIANCE_MATRIX
-    z, u = _system_rows("cartpole", 3, enc, torch.float64)
+    z, u = system_rows("cartpole", 3, enc, torch.float64)
     assert not model.native_ok(z, enc)
     with pytest.raises(_native.NativeError):
         model.native_step(z, u, enc)
@@ -597,7 +566,7 @@ def test_gp_full_size_rounds_of_configs3():
     m64 = copy.deepcopy(model).double()
     _, Fz64, Fu64 = _torch_step(m64, z.double(), u.double(),
                                 StateEncoding.DEFAULT, True)
-    assert _rel(Fz.double(), Fz64) < 2e-3 and _rel(Fu.double(), Fu64) < 2e-3
+    assert max_rel(Fz.double(), Fz64) < 2e-3 and max_rel(Fu.double(), Fu64) < 2e-3
 
 
 @pytest.mark.gpu
@@ -651,14 +620,14 @@ def test_gp_step_kernel_training_set_sizes(M):
     counts (the zero-weight phantom partners), exactly one lane tile, one more,
     two tiles less one - step and Jacobian against the torch module, fp64."""
     enc = StateEncoding.DEFAULT
-    model, _ = _system_model("cartpole", M, torch.float64, seed=M)
-    z, u = _system_rows("cartpole", 7, enc, torch.float64, seed=M + 1)
+    model, _ = system_model("cartpole", M, torch.float64, seed=M)
+    z, u = system_rows("cartpole", 7, enc, torch.float64, seed=M + 1)
     assert model.native_ok(z, enc, jacobian=True)
     ref, Fz_r, Fu_r = _torch_step(model, z, u, enc, True)
     out, Fz, Fu = model.native_step(z, u, enc, jacobian=True)
     plain = model.native_step(z, u, enc)
-    assert _rel(out, ref) < 1e-10 and _rel(plain, ref) < 1e-10
-    assert _rel(Fz, Fz_r) < 1e-9 and _rel(Fu, Fu_r) < 1e-9
+    assert max_rel(out, ref) < 1e-10 and max_rel(plain, ref) < 1e-10
+    assert max_rel(Fz, Fz_r) < 1e-9 and max_rel(Fu, Fu_r) < 1e-9
 
 
 @pytest.mark.gpu
@@ -674,8 +643,8 @@ def test_gp_step_kernel_at_the_outer_loops_dataset_size():
     to 1e-10."""
     import copy
     enc = StateEncoding.DEFAULT
-    model, _ = _system_model("double_cartpole", 300, torch.float32, seed=3)
-    z, u = _system_rows("double_cartpole", 5, enc, torch.float32, seed=4)
+    model, _ = system_model("double_cartpole", 300, torch.float32, seed=3)
+    z, u = system_rows("double_cartpole", 5, enc, torch.float32, seed=4)
     assert model.native_ok(z, enc, jacobian=True)
     ref, Fz_r, Fu_r = _torch_step(model, z, u, enc, True)
     out, Fz, Fu = model.native_step(z, u, enc, jacobian=True)
@@ -684,11 +653,11 @@ def test_gp_step_kernel_at_the_outer_loops_dataset_size():
     r64, Fz64, Fu64 = _torch_step(m64, z.double(), u.double(), enc, True)
     for got, tor, exact, tol in ((out, ref, r64, 2e-5), (Fz, Fz_r, Fz64, 5e-4),
                                  (Fu, Fu_r, Fu64, 5e-4)):
-        assert _rel(got.double(), exact) < max(
-            tol, 4.0 * _rel(tor.double(), exact))
+        assert max_rel(got.double(), exact) < max(
+            tol, 4.0 * max_rel(tor.double(), exact))
     assert not m64.native_ok(z.double(), enc, jacobian=True)
     assert m64.native_ok(z.double(), enc)
-    assert _rel(m64.native_step(z.double(), u.double(), enc), r64) < 1e-10
+    assert max_rel(m64.native_step(z.double(), u.double(), enc), r64) < 1e-10
 
 
 @pytest.mark.gpu
@@ -706,14 +675,14 @@ def test_gp_jacobian_beyond_the_g_table(M, dtype):
     yardstick), the first size past the table and the last that fits."""
     import copy
     enc = StateEncoding.DEFAULT
-    model, _ = _system_model("double_cartpole", M, dtype, seed=M)
-    z, u = _system_rows("double_cartpole", 2, enc, dtype, seed=M + 1)
+    model, _ = system_model("double_cartpole", M, dtype, seed=M)
+    z, u = system_rows("double_cartpole", 2, enc, dtype, seed=M + 1)
     assert model.native_ok(z, enc, jacobian=True)
     out, Fz, Fu = model.native_step(z, u, enc, jacobian=True)
     if dtype == torch.float64:
         ref, Fz_r, Fu_r = _torch_step(model, z, u, enc, True)
-        assert _rel(out, ref) < 1e-10
-        assert _rel(Fz, Fz_r) < 1e-9 and _rel(Fu, Fu_r) < 1e-9
+        assert max_rel(out, ref) < 1e-10
+        assert max_rel(Fz, Fz_r) < 1e-9 and max_rel(Fu, Fu_r) < 1e-9
         return
     ref, Fz_r, Fu_r = _torch_step(model, z, u, enc, True)
     m64 = copy.deepcopy(model).double()
@@ -721,8 +690,8 @@ def test_gp_jacobian_beyond_the_g_table(M, dtype):
     r64, Fz64, Fu64 = _torch_step(m64, z.double(), u.double(), enc, True)
     for got, tor, exact, tol in ((out, ref, r64, 2e-5), (Fz, Fz_r, Fz64, 5e-4),
                                  (Fu, Fu_r, Fu64, 5e-4)):
-        assert _rel(got.double(), exact) < max(
-            tol, 4.0 * _rel(tor.double(), exact))
+        assert max_rel(got.double(), exact) < max(
+            tol, 4.0 * max_rel(tor.double(), exact))
 
 
 @pytest.mark.gpu
@@ -731,9 +700,9 @@ def test_gp_kernel_view_follows_a_loaded_state():
     made from: after `load_state_dict` (or a parameter changed in place) the
     kernel answers with the new model, not the cached one."""
     enc = StateEncoding.DEFAULT
-    a, _ = _system_model("cartpole", 20, torch.float64, seed=1)
-    b, _ = _system_model("cartpole", 20, torch.float64, seed=2)
-    z, u = _system_rows("cartpole", 5, enc, torch.float64)
+    a, _ = system_model("cartpole", 20, torch.float64, seed=1)
+    b, _ = system_model("cartpole", 20, torch.float64, seed=2)
+    z, u = system_rows("cartpole", 5, enc, torch.float64)
     out_a, out_b = a.native_step(z, u, enc), b.native_step(z, u, enc)
     assert not torch.allclose(out_a, out_b)
     a.load_state_dict(b.state_dict())
@@ -741,7 +710,7 @@ def test_gp_kernel_view_follows_a_loaded_state():
     with torch.no_grad():
         a.log_ell.add_(0.1)
     ref = _torch_step(a, z, u, enc, False)
-    assert _rel(a.native_step(z, u, enc), ref) < 1e-11
+    assert max_rel(a.native_step(z, u, enc), ref) < 1e-11
 
 
 @pytest.mark.gpu
@@ -854,7 +823,7 @@ def test_gp_step_with_a_row_mask(dtype):
     """pddp_gp_step_masked_*: groups of rows with a zero mask entry are skipped
     - their outputs (step and Jacobians) are left as they were - and the other
     rows are the unmasked launch's, bit for bit."""
-    model, _ = _system_model("cartpole", 30, dtype)
+    model, _ = system_model("cartpole", 30, dtype)
     enc = StateEncoding.DEFAULT
     g = torch.Generator().manual_seed(5)
     groups, per = 5, 3

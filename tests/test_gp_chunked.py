@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pddp_amd  # noqa: E402,F401
 from pddp_amd import GaussianVariable, StateEncoding  # noqa: E402
 from pddp_amd.models.gp import gp_dynamics_model_factory  # noqa: E402
-from test_gp import _rel, _system_model, _system_rows  # noqa: E402
+from gp_util import max_rel, system_model, system_rows  # noqa: E402
 
 LDS = 160 * 1024
 
@@ -95,10 +95,10 @@ def _check(got, exact, torch_same_dtype, tols, label, noise=None):
     for k, (g, e, tol) in enumerate(zip(got, exact, tols)):
         bar = tol
         if torch_same_dtype is not None:
-            bar = max(bar, 4.0 * _rel(torch_same_dtype[k].double(), e))
+            bar = max(bar, 4.0 * max_rel(torch_same_dtype[k].double(), e))
         if noise is not None:
             bar = max(bar, 4.0 * noise[k])
-        d = _rel(g.double(), e)
+        d = max_rel(g.double(), e)
         print("%s [%d]: kernel vs fp64 module %.3e, bar %.3e%s" % (
             label, k, d, bar,
             "" if noise is None else ", module vs permuted module %.3e"
@@ -175,10 +175,10 @@ def test_gp_chunked_equals_resident_where_both_exist(system, M, dtype):
     encoding."""
     f64 = dtype == torch.float64
     tols = (1e-10, 1e-9, 1e-9) if f64 else (2e-5, 5e-4, 5e-4)
-    model, _ = _system_model(system, M, dtype, seed=M)
+    model, _ = system_model(system, M, dtype, seed=M)
     m64 = model if f64 else _double(model)
     for enc in (StateEncoding.DEFAULT, StateEncoding.VARIANCE_ONLY):
-        z, u = _system_rows(system, 3, enc, dtype, seed=M + 1)
+        z, u = system_rows(system, 3, enc, dtype, seed=M + 1)
         assert model.native_ok(z, enc, jacobian=True)
         assert model.native_form(z, enc, jacobian=True) == "resident"
         exact = _lean_step(m64, z.double(), u.double(), enc, True)
@@ -238,8 +238,8 @@ def test_gp_step_at_sizes_beyond_the_resident_form(M, dtype, jacobian):
     The fixed bars decide everywhere."""
     enc = StateEncoding.DEFAULT
     f64 = dtype == torch.float64
-    model, _ = _system_model("double_cartpole", M, dtype, seed=M)
-    z, u = _system_rows("double_cartpole", 2, enc, dtype, seed=M + 1)
+    model, _ = system_model("double_cartpole", M, dtype, seed=M)
+    z, u = system_rows("double_cartpole", 2, enc, dtype, seed=M + 1)
     assert model.native_form(z, enc, jacobian=jacobian) == "chunked"
     assert not model.native_ok(z, enc, jacobian=jacobian)
     m64 = model if f64 else _double(model)
@@ -247,7 +247,7 @@ def test_gp_step_at_sizes_beyond_the_resident_form(M, dtype, jacobian):
     exact = wrap(_lean_step(m64, z.double(), u.double(), enc, jacobian))
     perm = wrap(_lean_step(_permuted(m64), z.double(), u.double(), enc,
                            jacobian))
-    noise = [_rel(p, e) for p, e in zip(perm, exact)]
+    noise = [max_rel(p, e) for p, e in zip(perm, exact)]
     del perm
     same = None if f64 else wrap(_lean_step(model, z, u, enc, jacobian))
     got = wrap(model.native_step(z, u, enc, jacobian=jacobian))
@@ -266,7 +266,7 @@ def _rollout_pair(system, dtype, Md, B=5, N=4):
     """pddp_gp_rollout_* and the per-step line search (`_line_search_gp_torch`:
     the step kernel per time step, the costs in torch) on one problem, as
     tests/test_gp.py test_gp_rollout_kernel_vs_per_step_line_search - with
-    smooth targets (those of test_gp.py `_system_model`) in place of that
+    smooth targets (those of gp_util.py `system_model`) in place of that
     test's pure-noise ones.  Reason, measured on the MI355X against the fp64
     per-step form on the same gains: noise targets at 66 points of the
     pendulum give weights of |beta| = 824, |Kinv| = 6.5e3, and EVERY float form
@@ -462,8 +462,8 @@ def test_gp_chunked_launch_split_is_bit_equal_to_one_launch(dtype):
     launch gives - step, Jacobian and the masked entry - and two calls on the
     same inputs are bit-equal."""
     enc = StateEncoding.DEFAULT
-    model, _ = _system_model("double_cartpole", 150, dtype, seed=5)
-    z, u = _system_rows("double_cartpole", 11, enc, dtype, seed=6)
+    model, _ = system_model("double_cartpole", 150, dtype, seed=5)
+    z, u = system_rows("double_cartpole", 11, enc, dtype, seed=6)
     mask = torch.tensor([1, 0, 1, 1, 0, 1], dtype=torch.uint8, device=z.device)
 
     def run():

@@ -8,18 +8,14 @@ import pytest
 import torch
 
 import oracle as orc
-from golden_util import (DT, FWD_NAMES, TAGS_DC150, elementwise_err, load,
-                         load_dc150, np_dtype, rel_err, tags)
+from golden_util import (DT, elementwise_err, FWD_NAMES, load, load_dc150,
+                         np_dtype, rel_err, tags, TAGS_DC150)
+from solver_util import (bnn_mpc_controller, bnn_problem, bnn_real_size_run,
+                         BOUND, make_solver, MEAN0, nominal_kernel, PROBLEMS,
+                         run_traced, TDT, TOL)
 
 pytestmark = pytest.mark.gpu
 
-PROBLEMS = ["cartpole", "pendulum", "double_cartpole", "rendezvous"]
-BOUND = {"cartpole": 10.0, "pendulum": 2.5, "double_cartpole": 20.0,
-         "rendezvous": 5.0}
-MEAN0 = {"cartpole": [0, 0, 0, 0], "pendulum": [0, 0],
-         "double_cartpole": [0, 0, np.pi, 0, np.pi, 0],
-         "rendezvous": [-10, -10, 10, 10, 0, -5, 5, 0]}
-TDT = {"f64": torch.float64, "f32": torch.float32}
 # fp64 is held to 1e-9 everywhere.  fp32 bounds are DATA-DRIVEN: the sweep is a
 # recursion through a discontinuous BoxQP whose conditioning (not the kernel)
 # sets the fp32 error - the oracle's own IEEE fp32 run, in the reference's
@@ -28,7 +24,7 @@ TDT = {"f64": torch.float64, "f32": torch.float32}
 # branch (profiles/r02_sweep_error_stats.json).  So an fp32 kernel is judged
 # by (a) its error against the fp64 oracle relative to the fp32 oracle's error
 # against the same fp64 oracle, and (b) counted status / clamp-pattern flips.
-TOL = {"f64": 1e-9}
+# (TOL = {"f64": 1e-9} is solver_util's.)
 # single-trajectory comparisons (small samples: the ratio of two draws from a
 # heavy-tailed error distribution is noisy): error vs the fp64 oracle at most
 # F32_RATIO x the fp32 oracle's own on the same trajectory, or below the floor
@@ -39,6 +35,12 @@ TOL = {"f64": 1e-9}
 # error outside the ratio is 5.5e-4 (eig-clamp) / 2.2e-5 (Cholesky).  The
 # sharp statement is test_sweep_variants_vs_oracle_many_trajectories.
 import os  # noqa: E402
+# What follows down to _check_gains is the one set of helpers that stays in a
+# test module: tests/conftest.py dumps sys.modules["test_gpu_parity"].STATS
+# under PDDP_DUMP_STATS, so the rows must be appended to THIS module's list.
+# test_action_algebra.py, test_cartpole_branches.py and
+# tools/sweep_error_stats.py import these names from here; everything else
+# shared is in solver_util.py.
 F32_RATIO = 8.0  # (tools/sweep_error_stats.py surveys other ratios itself)
 F32_FLOOR = {0: 1e-3, 1: 3e-5}  # by gain branch (0 eig-clamp, 1 Cholesky)
 STATS = []  # rows recorded by the fp32 comparisons (dumped by conftest)
@@ -86,34 +88,6 @@ def _check_gains(dtype, kb, Kb, kr, Kr, args, kw, soft=None, **ctx):
     return True
 
 
-def _setup(problem, dtype, B, N, seed=0):
-    import pddp_amd
-    from pddp_amd.controllers.solver import ILQRSolver
-    from pddp_amd.utils.encoding import StateEncoding
-    mod = getattr(pddp_amd.examples, problem)
-    model_cls = [getattr(mod, n) for n in dir(mod)
-                 if n.endswith("DynamicsModel") and n != "DynamicsModel"][0]
-    cost_cls = [getattr(mod, n) for n in dir(mod)
-                if n.endswith("Cost") and n != "AugmentedQRCost"][0]
-    model, cost = model_cls(DT[problem]), cost_cls()
-    prob = model.native_problem(StateEncoding.IGNORE_UNCERTAINTY, cost)
-    rng = np.random.RandomState(seed)
-    n, m = prob.encoded_size, prob.action_size
-    z0 = np.asarray(MEAN0[problem], np.float64) + 1e-2 * rng.randn(B, n)
-    U = 0.1 * rng.randn(B, N, m)
-    bound = BOUND[problem]
-    td = TDT[dtype]
-    u_min = torch.full((m,), -bound, dtype=td)
-    u_max = torch.full((m,), bound, dtype=td)
-    s = ILQRSolver(prob, B, N, td, "cuda", u_min, u_max)
-    z0 = z0.astype(np_dtype(dtype))
-    U = U.astype(np_dtype(dtype))
-    s.z0.copy_(torch.from_numpy(z0))
-    s.U.copy_(torch.from_numpy(U))
-    op = orc.make_problem(problem, DT[problem])
-    return s, op, z0, U, u_min.numpy(), u_max.numpy()
-
-
 def test_native_library_loaded():
     """The product path is the HIP library, and it is the in-tree build."""
     from pddp_amd import _native
@@ -127,7 +101,7 @@ def test_constants_agree_with_oracle():
     """Host-side problem constants (pddp_amd.examples) == the oracle's own
     (which are pinned to the reference's by test_oracle_golden)."""
     for problem in PROBLEMS:
-        s, op, *_ = _setup(problem, "f64", 1, 2)
+        s, op, *_ = make_solver(problem, "f64", 1, 2)
         p = s.problem
         for f in ("model", "encoding", "state_size", "action_size",
                   "encoded_size", "aug_size"):
@@ -140,7 +114,7 @@ def test_constants_agree_with_oracle():
 @pytest.mark.parametrize("problem", PROBLEMS)
 def test_derivative_records_vs_oracle(problem, dtype):
     B, N = 6, 70  # > 64: exercises the second chunk of the record staging
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
+    s, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
     s.nominal_rollout()
     s.derivs(set_state=False)
     views = dict(zip(("F_z", "F_u", "L_z", "L_u", "L_zz", "L_uz", "L_uu"),
@@ -179,7 +153,7 @@ def test_backward_vs_oracle(problem, dtype, variant):
     if variant in (7, 17) and dtype != "f32":
         pytest.skip("variants 7 / 17 = f32 kernels with approximate division")
     B, N = 5, 40
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
+    s, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
     s.nominal_rollout()
     s.derivs(set_state=False)
     o = orc.load(np_dtype(dtype))
@@ -293,7 +267,7 @@ def test_backward_vs_reference_golden(problem, dtype):
 @pytest.mark.parametrize("problem", PROBLEMS)
 def test_line_search_vs_oracle(problem, dtype):
     B, N = 4, 12
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
+    s, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
     s.nominal_rollout()
     s.derivs(set_state=False)
     regv = torch.full((B,), 1.0, dtype=torch.float64, device="cuda")
@@ -317,25 +291,6 @@ def test_line_search_vs_oracle(problem, dtype):
         assert rel_err(Jc[b], J) < tol
 
 
-def _run_traced(s, n_iterations, tol=5e-6, max_reg=1e10, max_rounds=400):
-    traces = [[] for _ in range(s.B)]
-
-    def on_round(r, s):
-        act = s.active.cpu().numpy()
-        st = s.state.cpu().numpy()
-        J = s.J_opt.cpu().numpy()
-        mu = s.mu.cpu().numpy()
-        de = s.delta.cpu().numpy()
-        for b in range(s.B):
-            if on_round.attempted[b]:
-                traces[b].append((st[b], J[b], mu[b], de[b]))
-        on_round.attempted = act.copy()
-
-    on_round.attempted = np.ones(s.B, np.uint8)
-    s.fit(n_iterations, tol, max_reg, on_round, max_rounds=max_rounds)
-    return traces
-
-
 @pytest.mark.parametrize("bounded", [True, False])
 @pytest.mark.parametrize("problem", ["cartpole", "pendulum",
                                      "double_cartpole"])
@@ -344,11 +299,11 @@ def test_fit_traces_vs_oracle(problem, bounded):
     mu / delta and costs as the oracle's restatement of iLQRController.fit
     (which test_oracle_golden pins to the reference's own traces)."""
     B, N, n_it = 6, 30, 12
-    s, op, z0, U, u_min, u_max = _setup(problem, "f64", B, N, seed=3)
+    s, op, z0, U, u_min, u_max = make_solver(problem, "f64", B, N, seed=3)
     if not bounded:
         s.u_min = s.u_max = None
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
-    traces = _run_traced(s, n_it)
+    traces = run_traced(s, n_it)
     o = orc.load(np.float64)
     alphas = s.alphas.cpu().numpy()
     kw = dict(u_min=u_min, u_max=u_max) if bounded else {}
@@ -406,7 +361,7 @@ def test_full_size_batch_invariance(dtype):
     bit-identical); (2) a sample of trajectories matches the oracle; (3) costs
     never increase over accepted rounds."""
     B, N = 4096, 100
-    s, op, z0, U, u_min, u_max = _setup("cartpole", dtype, B, N, seed=11)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", dtype, B, N, seed=11)
     dup = [(0, 4095), (17, 2048), (1000, 1001)]
     for a, b in dup:
         z0[b], U[b] = z0[a], U[a]
@@ -1197,7 +1152,7 @@ def test_backward_ragged_shapes(B, N, dtype, problem):
     all branches, against the oracle."""
     # (other problems in fp32: the matrix-core kernel, one wavefront per
     # trajectory in four-wave workgroups, a four-slot record ring)
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N, seed=B * 31 + N)
+    s, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N, seed=B * 31 + N)
     s.nominal_rollout()
     s.derivs(set_state=False)
     o = orc.load(np_dtype(dtype))
@@ -1506,7 +1461,7 @@ def test_graph_replay_equals_eager_rounds():
     B, N = 64, 30
     res = []
     for graph, rps in ((False, 1), (True, 1), (True, 4)):
-        s, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=5)
+        s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=5)
         s.reset_controller_state()
         s.nominal_rollout()
         rounds = s.fit(n_iterations=20, graph=graph, rounds_per_sync=rps)
@@ -1548,7 +1503,7 @@ def test_fused_round_equals_separate_kernels(problem, dtype):
     contracted into FMAs differently; bit for bit only with -ffp-contract=off,
     csrc/Makefile)."""
     B, N = 37, 33
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N, seed=3)
+    s, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N, seed=3)
     s._nominal_sweep = False  # (the launch that WRITES records is the subject)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     names = ("Z", "U", "rec", "L", "J_opt", "mu", "delta", "state", "iter",
@@ -1670,23 +1625,6 @@ def test_best_rollout_exchange_on_the_device(dtype):
         ex.post(J, Z, U, offset=1 << 53)
 
 
-class _nominal_kernel(object):
-    """pddp_sweep_nominal_kernel(which) for the duration of a `with` block:
-    3 / 4 the record generator of riccati_n4_elem.hpp inline / on wavefronts
-    of its own, 0 auto (by batch)."""
-
-    def __init__(self, which):
-        self.which = which
-
-    def __enter__(self):
-        from pddp_amd import _native
-        self.prev = _native.lib().pddp_sweep_nominal_kernel(self.which)
-
-    def __exit__(self, *exc):
-        from pddp_amd import _native
-        _native.lib().pddp_sweep_nominal_kernel(self.prev)
-
-
 @pytest.mark.parametrize("B,N", [(37, 33), (16, 100), (5, 10), (130, 47),
                                  (3, 8), (300, 201), (2, 1), (70, 16),
                                  (33, 32), (6, 17)])
@@ -1699,7 +1637,7 @@ def test_sweep_from_nominal_f64_vs_oracle_and_records(B, N):
     to 1e-9, stage costs and J_opt to 1e-12 (ilqr.py:393-486, :529-674) - and
     against pddp_derivs_f64 followed by the recorded sweep; ragged batches,
     horizons shorter than / not a multiple of a block, masked trajectories."""
-    s, op, z0, U, u_min, u_max = _setup("cartpole", "f64", B, N, seed=11)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", "f64", B, N, seed=11)
     assert s._nominal_sweep is None  # in its domain, untried
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     s.mu.fill_(1.0)
@@ -1764,7 +1702,7 @@ def test_sweep_from_nominal_equals_records_then_sweep(B, N, kernel):
     and J_opt = L.sum() - ragged batches, horizons that are not a multiple of
     the generators' blocks (four steps / sixteen steps), horizons shorter than
     a block, masked trajectories."""
-    with _nominal_kernel(kernel):
+    with nominal_kernel(kernel):
         _sweep_from_nominal_case(B, N, same_arithmetic=False)
 
 
@@ -1786,7 +1724,7 @@ def test_sweep_from_nominal_of_the_other_problems(problem, B, N, dtype, bounded,
     fresh nominals, masked trajectories left alone - both gain branches,
     bounded and not, fp64 to 1e-9 (the same record code, the same step) and
     fp32 to what two f32 sweeps of the same step agree to."""
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N, seed=4)
+    s, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N, seed=4)
     if not bounded:
         s.u_min = s.u_max = None
     s.branch = branch
@@ -1840,8 +1778,8 @@ def test_sweep_from_nominal_reports_a_nan_nominal(kernel):
     kernel) reports - PDDP_BWD_NAN, `eig` on a NaN Q_uu (ilqr.py:631) - and
     the other trajectories of the same wavefront are not disturbed."""
     B, N = 24, 40
-    with _nominal_kernel(kernel):
-        s, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=3)
+    with nominal_kernel(kernel):
+        s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=3)
         U = U.copy()
         U[2, 17] = np.nan
         U[9, 0] = np.nan
@@ -1865,7 +1803,7 @@ def test_sweep_from_nominal_reports_a_nan_nominal(kernel):
 
 
 def _sweep_from_nominal_case(B, N, same_arithmetic):
-    s, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=11)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=11)
     assert s._nominal_sweep is None  # in its domain, untried
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     s.mu.fill_(1.0)
@@ -1965,7 +1903,7 @@ def test_round_from_nominal_equals_round_with_records(kernel):
     the same decisions, nominals and regularisation, round by round.  (The
     recorded sweep is the deferred rank-one form, the sweep from the nominal
     the plain recursion: values to 2e-2 after 14 rounds.)"""
-    with _nominal_kernel(kernel):
+    with nominal_kernel(kernel):
         _rounds_side_by_side(2e-2)
 
 
@@ -1980,7 +1918,7 @@ def test_one_launch_round_equals_two_launches(B, N):
     stage costs, J_opt) bit for bit; the search's outputs to rounding (the same
     closed forms inlined into another kernel are contracted into FMAs
     differently, Makefile)."""
-    s, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=5)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=5)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     names = ("Z", "U", "L", "J_opt", "mu", "delta", "state", "iter", "active",
              "fresh", "gains", "gains_acc", "Jc", "bwd_status", "n_live")
@@ -2075,7 +2013,7 @@ def test_one_launch_round_single_trajectory_and_mpc_schedule():
     assert float((out[True][1] - out[False][1]).abs().max()) <= 1e-4 * float(
         out[False][1].abs().max().clamp_min(1.0))
     # eleven step sizes, a small batch: rounds in one launch == single rounds
-    a, op, z0n, Un, _, _ = _setup("cartpole", "f32", 3, 20, seed=2)
+    a, op, z0n, Un, _, _ = make_solver("cartpole", "f32", 3, 20, seed=2)
     from pddp_amd.controllers.solver import ILQRSolver
     prob = a.problem
     mk = lambda: ILQRSolver(prob, 3, 20, torch.float32, "cuda",
@@ -2103,8 +2041,8 @@ def test_rounds_in_one_launch_equal_single_rounds(B, N, R):
     loop, the hand-over between rounds through a workgroup-scope fence and a
     barrier instead of a launch boundary: every output identical, bit for bit,
     including trajectories that leave the fit on the way."""
-    a, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=9)
-    b, *_ = _setup("cartpole", "f32", B, N, seed=9)
+    a, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=9)
+    b, *_ = make_solver("cartpole", "f32", B, N, seed=9)
     for s in (a, b):
         s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     names = ("Z", "U", "L", "J_opt", "mu", "delta", "state", "iter", "active",
@@ -2142,8 +2080,8 @@ def test_rounds_from_nominal_cartpole_f64():
 
 def _rounds_side_by_side(vtol, problem="cartpole", dtype="f32", N=40):
     B = 64
-    a, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N, seed=5)
-    b, *_ = _setup(problem, dtype, B, N, seed=5)
+    a, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N, seed=5)
+    b, *_ = make_solver(problem, dtype, B, N, seed=5)
     assert a._nominal_sweep_possible()
     a._nominal_sweep = None
     b._nominal_sweep = False
@@ -2180,8 +2118,8 @@ def test_search_accept_without_candidates(B, N):
     and was rolled out a second time."""
     from pddp_amd import _native
     lib = _native.lib()
-    a, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=3)
-    b, *_ = _setup("cartpole", "f32", B, N, seed=3)
+    a, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=3)
+    b, *_ = make_solver("cartpole", "f32", B, N, seed=3)
     a.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     b.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     other_winners = accepted = 0
@@ -2235,8 +2173,8 @@ def test_search_accept_dense_form(B, N, cand):
     and tail arithmetic; only where the operands come from differs)."""
     from pddp_amd import _native
     lib = _native.lib()
-    a, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=3)
-    b, *_ = _setup("cartpole", "f32", B, N, seed=3)
+    a, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=3)
+    b, *_ = make_solver("cartpole", "f32", B, N, seed=3)
     a.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     b.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     accepted = 0
@@ -2322,7 +2260,7 @@ def test_benched_round_kernels_vs_oracle(rounds_before):
     of the feed-forward gains moves its fp64 cost by less than 3e-8 -
     "well-conditioned"."""
     B, N = 4096, 100
-    s, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=11)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=11)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     tol, max_reg, n_it = 5e-6, 1e10, 50
     for _ in range(rounds_before):
@@ -2446,9 +2384,9 @@ def test_fit_through_the_record_free_round_vs_oracle():
     fp64 oracle's at least as long as the fp32 oracle's do, less a margin; and
     where they agree the costs match to 1e-4."""
     B, N, n_it = 256, 100, 6
-    s, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=7)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=7)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
-    traces = _run_traced(s, n_it)
+    traces = run_traced(s, n_it)
     assert s._nominal_sweep is True and s._fused is True
     o32, o64 = orc.load(np.float32), orc.load(np.float64)
     alphas = s.alphas.cpu().numpy()
@@ -3113,7 +3051,7 @@ def test_sweep_variants_vs_oracle_many_trajectories(dtype):
     median <= 1e-5 on k, max <= 1e-5 on K.  Measured distributions:
     profiles/r02_sweep_error_stats.json."""
     B, N = 384, 100
-    s, op, z0, U, u_min, u_max = _setup("cartpole", dtype, B, N, seed=5)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", dtype, B, N, seed=5)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     s.derivs(mask=s.fresh)
     o = orc.load(np_dtype(dtype))
@@ -3156,7 +3094,7 @@ def test_sweep_variants_vs_oracle_many_trajectories(dtype):
                     s.fresh.fill_(1)
                     s.L.zero_()
                     s.J_opt.fill_(-1.0)
-                    with _nominal_kernel(int(variant[-1])):
+                    with nominal_kernel(int(variant[-1])):
                         assert s.sweep_nominal()
                     Lg = s.L.cpu().numpy()
                     Lr = np.stack([fwd[b]["L"] for b in range(B)])
@@ -3353,78 +3291,6 @@ def test_boxqp_many_dimensions_on_the_gpu():
     assert torch.equal(f4.cpu(), ft.cpu())
 
 
-def _bnn_real_size_run(dtype=torch.float32, raw=None):
-    """Runs the HIP BNN path (native nominal rollout, forward-mode Jacobians,
-    hyper-dual cost derivatives, moment-step line search around the fused
-    network kernel) on the inputs of tests/golden/bnn_cartpole_real_size.npz and
-    returns rows {what, r, hip_vs_f64, hip_vs_f32, ref32_vs_f64}."""
-    import os
-    import pddp_amd
-    from golden_util import GOLDEN_DIR
-    from pddp_amd.controllers.plugin import TorchProblem
-    from pddp_amd.controllers.solver import ILQRSolver
-    from pddp_amd.examples import cartpole
-    from pddp_amd.models.bnn import (bnn_dynamics_model_factory,
-                                     load_reference_state)
-    g = np.load(os.path.join(GOLDEN_DIR, "bnn_cartpole_real_size.npz"))
-    CM = cartpole.CartpoleDynamicsModel
-    P, H, N = int(g["P"]), int(g["H"]), int(g["N"])
-    model = bnn_dynamics_model_factory(
-        4, 1, [H, H], CM.angular_indices, CM.non_angular_indices)(
-            n_particles=P).float().eval()
-    load_reference_state(model, {k[len("state/"):]: g[k] for k in g.files
-                                 if k.startswith("state/")})
-    # (float64: the same weights and noise cast up, as the fixture's f64 run)
-    model = model.to(dtype).cuda()
-    model.eps_in = {k: v.to(dtype).cuda() for k, v in model.eps_in.items()}
-    for d in model.model.drops:
-        d.noise = d.noise.to(dtype).cuda()
-    cost = cartpole.CartpoleCost().to(dtype).cuda()
-    enc = pddp_amd.StateEncoding.DEFAULT
-    opts = {"use_predicted_std": False, "infer_noise_variables": True}
-    plugin = TorchProblem(model, cost, enc, opts, {})
-    R = g["z0"].shape[0]
-    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype).cuda()
-    s = ILQRSolver(None, R, N, dtype, "cuda", cu(g["u_min"]),
-                   cu(g["u_max"]), cu(g["alphas"]), plugin=plugin, n=14, m=1)
-    s.set_nominal(cu(g["z0"]), cu(g["U"]))  # native nominal rollout
-    s.derivs()
-    path = dict(plugin.last_derivs_path)
-    views = dict(zip(("F_z", "F_u", "L_z", "L_u", "L_zz", "L_uz", "L_uu"),
-                     s.record_views()))
-    views["Z"], views["L"] = s.Z, s.L
-    rows = []
-
-    def add(what, r, got, key):
-        a32, a64 = g["f32/%d/%s" % (r, key)], g["f64/%d/%s" % (r, key)]
-        rows.append(dict(what=what, r=r, hip_vs_f64=rel_err(got, a64),
-                         hip_vs_f32=rel_err(got, a32),
-                         ref32_vs_f64=rel_err(a32, a64)))
-    for r in range(R):
-        for nm in ("Z", "F_z", "F_u", "L", "L_z", "L_u", "L_zz", "L_uu"):
-            add(nm, r, views[nm][r].cpu().numpy(), "fwd/" + nm)
-        assert float(views["L_uz"][r].abs().max()) == 0.0 == float(
-            np.abs(g["f64/%d/fwd/L_uz" % r]).max())
-    # the line search on the reference's own gains
-    for r in range(R):
-        # (the fixture feeds the float32 run's gains and nominal to both dtypes)
-        s.gains[r, :, :1] = cu(g["f32/%d/k" % r])
-        s.gains[r, :, 1:] = cu(g["f32/%d/K" % r]).reshape(N, 14)
-        s.Z[r] = cu(g["f32/%d/fwd/Z" % r])
-    s.line_search(use_status=False)
-    Zc = s.Zc.permute(0, 1, 2, 3).cpu().numpy()  # [R][N+1][A][n]
-    Uc = s.Uc.cpu().numpy()
-    Jc = s.Jc.cpu().numpy()
-    if raw is not None:  # (tools/dbg: the arrays themselves)
-        raw.update(Zc=Zc, Uc=Uc, Jc=Jc, g=g)
-    for r in range(R):
-        add("Z_new", r, Zc[r], "ls/Z_new")
-        add("U_new", r, Uc[r], "ls/U_new")
-        add("J", r, Jc[r], "ls/J")
-    rows.append(dict(what="path", path=path))
-    return rows
-
-
 def test_bnn_bf16_split_twin_vs_reference_real_size():
     """The same check with the network kernel's layer 2 on its bf16-split twin
     (pddp_bnn_mlp_precision(3)): everything the rollouts and the line search
@@ -3438,7 +3304,7 @@ def test_bnn_bf16_split_twin_vs_reference_real_size():
     lib = _native.lib()
     prev = lib.pddp_bnn_mlp_precision(3)
     try:
-        rows = _bnn_real_size_run()
+        rows = bnn_real_size_run()
     finally:
         lib.pddp_bnn_mlp_precision(prev)
     assert rows[-1]["path"] == {"dynamics": "hip", "cost": "hip"}
@@ -3471,7 +3337,7 @@ def test_bnn_hip_kernels_vs_reference_real_size():
     (measured on the MI355X: Jacobians 1.3e-6 .. 4.9e-6 where the reference's
     own float32 run is 3e-7 .. 2.9e-6 off; everything else <= 3e-7, held to
     2e-6)."""
-    rows = _bnn_real_size_run()
+    rows = bnn_real_size_run()
     assert rows[-1]["path"] == {"dynamics": "hip", "cost": "hip"}
     seen = set()
     for r in rows[:-1]:
@@ -3481,31 +3347,6 @@ def test_bnn_hip_kernels_vs_reference_real_size():
         seen.add(r["what"])
     assert seen == {"Z", "F_z", "F_u", "L", "L_z", "L_u", "L_zz", "L_uu",
                     "Z_new", "U_new", "J"}
-
-
-def _bnn_mpc_controller(B, N, graph, P=100, H=200, seed=0,
-                        use_predicted_std=False, dtype=torch.float32):
-    import pddp_amd
-    from pddp_amd.examples import cartpole
-    from pddp_amd.models.bnn import bnn_dynamics_model_factory
-    torch.manual_seed(seed)
-    CM = cartpole.CartpoleDynamicsModel
-    model = bnn_dynamics_model_factory(
-        4, 1, [H, H], CM.angular_indices, CM.non_angular_indices)(
-            n_particles=P).cuda().to(dtype).eval()
-    with torch.no_grad():  # untrained network: keep its dynamics gentle
-        model.model.out.weight.mul_(0.05)
-        model.model.out.bias.mul_(0.05)
-    cost = cartpole.CartpoleCost().cuda().to(dtype)
-    ctrl = pddp_amd.controllers.iLQRController(
-        None, model, cost, graph=graph,
-        model_opts={"use_predicted_std": use_predicted_std,
-                    "infer_noise_variables": True})
-    g = torch.Generator().manual_seed(seed + 1)
-    ctrl._U_nominal = (0.1 * torch.randn(B, N, 1, generator=g)).cuda().to(dtype)
-    x = (torch.tensor([0.0, 0.0, 3.14159, 0.0]) +
-         1e-2 * torch.randn(B, 4, generator=g)).cuda().to(dtype)
-    return ctrl, CM(0.1).cuda().to(dtype), x
 
 
 @pytest.mark.parametrize("use_predicted_std", [False, True])
@@ -3544,7 +3385,7 @@ def _mpc_graph_replay_equals_eager(use_predicted_std, dtype, steps=5):
     u_max = torch.tensor([10.0], dtype=dtype)
     runs = {}
     for graph in (False, True):
-        ctrl, plant, x = _bnn_mpc_controller(
+        ctrl, plant, x = bnn_mpc_controller(
             B, N, graph, use_predicted_std=use_predicted_std, dtype=dtype)
         x[255], x[100] = x[0], x[7]          # duplicated restarts
         ctrl._U_nominal[255] = ctrl._U_nominal[0]
@@ -3844,7 +3685,7 @@ def test_bnn_graphs_follow_model_resample_and_refit():
     u_min, u_max = torch.tensor([-10.0]), torch.tensor([10.0])
     runs = {}
     for graph in (False, True):
-        ctrl, plant, x = _bnn_mpc_controller(B, N, graph, P=32, H=64)
+        ctrl, plant, x = bnn_mpc_controller(B, N, graph, P=32, H=64)
         model = ctrl.model
         z = torch.cat([x, tri.expand(B, -1)], -1)
         us, gens = [], []
@@ -3933,51 +3774,6 @@ def test_controller_step_equals_fit_iterations():
     assert abs(a._mu - b._mu) <= 1e-15 and abs(a._delta - b._delta) <= 1e-15
 
 
-def _bnn_problem(problem, B, N, seed=0):
-    """The BNN workloads of bench.py (configs[2] / configs[3]'s problem):
-    [200, 200] hidden, 100 particles, DEFAULT encoding, float32, bounded."""
-    import pddp_amd
-    from pddp_amd.controllers.ilqr import fit_alphas
-    from pddp_amd.controllers.plugin import TorchProblem
-    from pddp_amd.controllers.solver import ILQRSolver
-    from pddp_amd.models.bnn import bnn_dynamics_model_factory
-    torch.manual_seed(0)
-    if problem == "cartpole":
-        from pddp_amd.examples import cartpole as ex
-        CM, cost_cls = ex.CartpoleDynamicsModel, ex.CartpoleCost
-        mean0, bound = [0.0, 0.0, 3.14159, 0.0], 10.0
-    else:
-        from pddp_amd.examples import double_cartpole as ex
-        CM, cost_cls = ex.DoubleCartpoleDynamicsModel, ex.DoubleCartpoleCost
-        mean0, bound = [0.0, 0.0, 3.14159, 0.0, 3.14159, 0.0], 20.0
-    D, m = CM.state_size, 1
-    n = D + D * (D + 1) // 2
-    model = bnn_dynamics_model_factory(
-        D, m, [200, 200], CM.angular_indices, CM.non_angular_indices)(
-            n_particles=100).cuda().eval()
-    with torch.no_grad():  # untrained weights: keep the dynamics gentle
-        model.model.out.weight.mul_(0.05)
-        model.model.out.bias.mul_(0.05)
-    cost = cost_cls().cuda()
-    enc = pddp_amd.StateEncoding.DEFAULT
-    opts = {"use_predicted_std": False, "infer_noise_variables": True}
-    g = torch.Generator().manual_seed(seed)
-    mean = torch.tensor(mean0)
-    z0 = torch.stack([pddp_amd.GaussianVariable(
-        mean + 1e-2 * torch.randn(D, generator=g),
-        var=1e-2 * torch.ones(D)).encode(enc) for _ in range(B)]).cuda()
-    U = (0.1 * torch.randn(B, N, m, generator=g)).cuda()
-
-    def solver(model_, cost_, rows, dtype, native64=False):
-        plugin = TorchProblem(model_, cost_, enc, opts, {})
-        if dtype == torch.float64 and not native64:
-            plugin.use_native_cost = False  # the float64 twin is the torch checker
-        return ILQRSolver(None, rows, N, dtype, "cuda", torch.tensor([-bound]),
-                          torch.tensor([bound]), fit_alphas(dtype, "cuda"),
-                          plugin=plugin, n=n, m=m)
-    return model, cost, z0, U, solver
-
-
 def _float64_twin(model, cost):
     """The same network, masks and particle noise, computed by the torch ops
     of pddp_amd.models.bnn in float64 (that path is pinned to the reference's
@@ -4018,7 +3814,7 @@ def test_smallest_preactivation_helper():
     test_full_size_bnn_round, on a small problem: it reproduces the solver's
     own float64 rollout (so the pre-activations it inspects are the ones of
     that step), and a typical step is far from a flip."""
-    model, cost, z0, U, solver = _bnn_problem("cartpole", 4, 12)
+    model, cost, z0, U, solver = bnn_problem("cartpole", 4, 12)
     m64, c64 = _float64_twin(model, cost)
     s3 = solver(m64, c64, 4, torch.float64)
     s3.set_nominal(z0[:4].double(), U[:4].double())
@@ -4071,7 +3867,7 @@ def _full_size_bnn_round(problem, B, N, precision):
          derivative records, and the line search's costs under the HIP gains
          - then the accept decision wherever the float64 margin between the
          best two step sizes is not a rounding matter."""
-    model, cost, z0, U, solver = _bnn_problem(problem, B, N)
+    model, cost, z0, U, solver = bnn_problem(problem, B, N)
     dup = [(0, B - 1), (17, B // 2), (1000 % B, 1001 % B)]
     for a, b in dup:
         z0[b], U[b] = z0[a], U[a]

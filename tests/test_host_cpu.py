@@ -13,15 +13,13 @@ import pytest
 import torch
 
 import oracle as orc
+from abi_util import HDR, ROOT
 from golden_util import DT, load
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_abi_library_exports_every_declared_symbol():
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    declared = set(re.findall(r"\b(pddp_[a-z0-9_]+)\s*\(", hdr))
+    declared = set(re.findall(r"\b(pddp_[a-z0-9_]+)\s*\(", HDR))
     declared = {d for d in declared if not d.startswith("pddp_record_layout")
                 or d == "pddp_record_layout_of"}
     lib = ctypes.CDLL(_native.LIB_PATH)
@@ -500,3 +498,41 @@ def test_hot_kernels_keep_their_working_set_in_registers():
            "qr_cost_derivs_kernel<float", "qr_cost_derivs_kernel<double, 4, 1>")
     for h in hot:
         assert any(h in r["kernel"] for r in rows), h
+
+
+def test_no_test_module_is_imported_for_its_helpers():
+    """Shared helpers live in helper modules (solver_util, abi_util, ...): no
+    file under tests/ or tools/ imports a test module, at any indentation.
+    The exceptions are the fp32 bookkeeping names that tests/conftest.py looks
+    up in sys.modules["test_gpu_parity"], each importer listed here."""
+    allowed = {
+        ("tests/test_action_algebra.py", "test_gpu_parity"):
+            {"F32_RATIO", "_check_gains", "_f32_ok"},
+        ("tests/test_cartpole_branches.py", "test_gpu_parity"):
+            {"STATS", "_check_gains"},
+    }
+    plain = re.compile(r"^\s*import\s+(.+)$")
+    bad = []
+    for top in ("tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in sorted(files):
+                if not f.endswith(".py"):
+                    continue
+                path = os.path.join(dirpath, f)
+                rel = os.path.relpath(path, ROOT).replace(os.sep, "/")
+                with open(path) as fh:
+                    text = fh.read()
+                for m in re.finditer(
+                        r"^[ \t]*from[ \t]+(test_\w*)[ \t]+import[ \t]*"
+                        r"(\([^)]*\)|(?:[^\n\\]|\\\n)*)", text, re.M):
+                    names = set(re.findall(r"(\w+)(?:\s+as\s+\w+)?\s*(?:,|$)",
+                                           m.group(2).strip("()"), re.M))
+                    if not names or names - allowed.get((rel, m.group(1)),
+                                                        set()):
+                        bad.append((rel, m.group(0).strip()))
+                for line in text.splitlines():
+                    m = plain.match(line)
+                    if m and any(part.strip().startswith("test_")
+                                 for part in m.group(1).split(",")):
+                        bad.append((rel, line.strip()))
+    assert not bad, bad

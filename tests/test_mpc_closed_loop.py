@@ -15,29 +15,22 @@ import pytest
 import torch
 
 import oracle as orc
+from abi_util import assert_entry_points, caller, cartpole_pointers, ROOT
 from golden_util import DT, np_dtype, rel_err
-from test_batch_problem import _perturbed, _set_table, _tol
-from test_closed_loop import _plant_rows
-from test_gpu_parity import PROBLEMS, TDT, _setup
+from solver_util import (BOUND, CONTROLLER, make_solver, mpc_advance,
+                         mpc_alphas_np, mpc_inputs, mpc_solver, perturbed,
+                         plant_rows, PROBLEMS, REARMED, record_tol, SENTINEL,
+                         set_table, to_device, trial_logs, UNDEFINED)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["pddp_mpc_advance_f32", "pddp_mpc_advance_f64"]
-SENTINEL = -7.25
-# pddp_problem.h: iLQRState
-UNDEFINED, MAX_REG = 0, 4
+MAX_REG = 4  # pddp_problem.h: iLQRState
 
 
 def test_mpc_entry_points_are_declared_exported_and_bound():
     """CPU: both symbols in the header, the built library and _native._SIGS."""
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name), name
-        assert name in _native.exported_symbols(), name
-        assert name[:-4] in _native._SIGS, name
+    assert_entry_points(SYMBOLS)
     assert len(_native._SIGS["pddp_mpc_advance"]) == 27
     assert _native.lib().pddp_hip_abi_version() == 1
 
@@ -64,19 +57,10 @@ def test_mpc_advance_refuses_before_any_launch():
     call): PDDP_E_BADARG for a null required pointer, a non-positive size and
     t outside [0, T); PDDP_E_UNSUPPORTED for a DEFAULT-encoding problem, both
     dtypes.  The non-null pointers are host words nobody reads."""
-    import pddp_amd
     from pddp_amd import _native
-    from pddp_amd.examples import cartpole
-    enc = pddp_amd.StateEncoding
-    model, cost = cartpole.CartpoleDynamicsModel(0.1), cartpole.CartpoleCost()
-    prob = model.native_problem(enc.IGNORE_UNCERTAINTY, cost)
-    prob_d = model.native_problem(enc.DEFAULT, cost)
-    pp, ppd = ctypes.addressof(prob), ctypes.addressof(prob_d)
-    word = (ctypes.c_double * 2)()
-    q = ctypes.addressof(word)
+    pp, ppd, q = cartpole_pointers()
     lib = _native.lib()
     for ty in ("f32", "f64"):
-        fn = getattr(lib, "pddp_mpc_advance_" + ty)
         #       0     1  2  3  4  5   6  7  8     9     10    11    12    13
         #       table B  N  T  t  z0  U  Z  u_min u_max plant dist  mask  Xlog
         good = [None, 2, 3, 4, 0, q, q, q, None, None, None, None, None, q,
@@ -86,12 +70,7 @@ def test_mpc_advance_refuses_before_any_launch():
                 # 23    24
                 # fresh n_live
                 q, None]
-
-        def call(problem, **change):
-            a = list(good)
-            for k, v in change.items():
-                a[int(k[1:])] = v
-            return fn(problem, *a, None)
+        call = caller(getattr(lib, "pddp_mpc_advance_" + ty), good)
 
         for required in (5, 6, 7, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23):
             assert call(pp, **{"_%d" % required: None}) == -1, (ty, required)
@@ -106,47 +85,15 @@ def test_mpc_advance_refuses_before_any_launch():
 # one advance
 # ---------------------------------------------------------------------------
 
-def _dev(a, dtype):
-    return None if a is None else torch.from_numpy(
-        np.ascontiguousarray(a)).to(dtype=TDT[dtype], device="cuda")
-
-
-def _advance(s, T, t, logs, plant=None, dist=None, mask=None, bounded=True):
-    """pddp_mpc_advance_* itself on the solver's buffers; `logs`: the five
-    trial buffers (Xlog, Ulog, Jcl, state_log, live_log)."""
-    from pddp_amd import _native
-    p = _native.ptr
-    _native.call("pddp_mpc_advance", s.dtype, ctypes.addressof(s.problem),
-                 p(s.batch_table), s.B, s.N, T, t, p(s.z0), p(s.U), p(s.Z),
-                 p(s.u_min if bounded else None),
-                 p(s.u_max if bounded else None), p(plant), p(dist), p(mask),
-                 *[p(x) for x in logs], p(s.mu), p(s.delta), p(s.state),
-                 p(s.iter), p(s.active), p(s.fresh), p(s.n_live), s._s())
-    torch.cuda.synchronize()
-
-
-def _logs(s, T, J0):
-    opts = dict(dtype=s.dtype, device="cuda")
-    return (torch.full((s.B, T + 1, s.n), SENTINEL, **opts),
-            torch.full((s.B, T, s.m), SENTINEL, **opts),
-            torch.full((s.B,), J0, **opts),
-            torch.full((s.B, T), -9, dtype=torch.int32, device="cuda"),
-            torch.full((s.B, T), 9, dtype=torch.uint8, device="cuda"))
-
-
-CONTROLLER = ("mu", "delta", "state", "iter", "active", "fresh")
-REARMED = dict(mu=0.0, delta=2.0, state=UNDEFINED, iter=1, active=1, fresh=1)
-
-
 def _check_advance(problem, dtype, variant, B=5, N=12, T=3):
     from pddp_amd import _native
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
+    s, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
     model_ops = [op] * B
     if variant in ("table", "table_own_model"):
         # (the controllers' models: other rows than the plants')
-        par, xg, ug, model_ops = _perturbed(problem, B, 12)
-        _set_table(s, par, xg, ug)
-    rows, plant_ops = _plant_rows(problem, B, 1, 11, dtype)
+        par, xg, ug, model_ops = perturbed(problem, B, 12)
+        set_table(s, par, xg, ug)
+    rows, plant_ops = plant_rows(problem, B, 1, 11, dtype)
     rows, plant_ops = rows[:, 0], [o[0] for o in plant_ops]
     if variant in ("table_own_model", "own_model"):
         rows, plant_ops = None, model_ops
@@ -159,8 +106,8 @@ def _check_advance(problem, dtype, variant, B=5, N=12, T=3):
         mask[B // 2] = 0
     on = np.ones(B, bool) if mask is None else mask.astype(bool)
     o = orc.load(np_dtype(dtype))
-    tol = _tol(dtype)
-    plant_t, dist_t = _dev(rows, dtype), _dev(dist, dtype)
+    tol = record_tol(dtype)
+    plant_t, dist_t = to_device(rows, dtype), to_device(dist, dtype)
     mask_t = None if mask is None else torch.from_numpy(mask).cuda()
     for t in (0, T - 1):
         # a nominal and two rounds behind it; some trajectories left live
@@ -175,10 +122,10 @@ def _check_advance(problem, dtype, variant, B=5, N=12, T=3):
         pre = {k: getattr(s, k).clone() for k in
                CONTROLLER + ("z0", "U", "Z", "n_live")}
         J0 = 1.5 if t > 0 else SENTINEL
-        logs = _logs(s, T, J0)
+        logs = trial_logs(s, T, J0)
         logs0 = [x.clone() for x in logs]
-        _advance(s, T, t, logs, plant=plant_t, dist=dist_t, mask=mask_t,
-                 bounded=bounded)
+        mpc_advance(s, T, t, logs, plant=plant_t, dist=dist_t, mask=mask_t,
+                    bounded=bounded)
         Xlog, Ulog, Jcl, state_log, live_log = (x.cpu().numpy() for x in logs)
         z_pre, U_pre = pre["z0"].cpu().numpy(), pre["U"].cpu().numpy()
         u = U_pre[:, 0]
@@ -250,7 +197,7 @@ def _check_advance(problem, dtype, variant, B=5, N=12, T=3):
 @pytest.mark.parametrize("problem", PROBLEMS)
 def test_mpc_advance_vs_composed_path_and_oracle(problem, dtype, variant):
     """B = 5, N = 12, T = 3, t in {0, T-1}, a disturbance of +-0.01, plants
-    from _perturbed(problem, B, 11): with plant rows alone, with a model table
+    from perturbed(problem, B, 11): with plant rows alone, with a model table
     whose rows differ from the plants', with plant = NULL (the plant is the
     controller's model: the table's row, and without a table the shared
     problem), unbounded, and with one trajectory masked out."""
@@ -267,36 +214,19 @@ def test_mpc_advance_second_partial_wavefront(dtype):
 # the loop
 # ---------------------------------------------------------------------------
 
-def _mpc_alphas_np():
-    return (10.0 ** torch.linspace(0, -3, 11)).double().numpy()
-
-
-def _inputs(problem, B, N, big_U):
-    """z0, U of _setup (seed 0) without a device: `big_U`: U = 10 randn in
-    place of 0.1 randn, the same draws."""
-    from test_gpu_parity import MEAN0
-    base = orc.make_problem(problem, DT[problem])
-    n, m = base.encoded_size, base.action_size
-    rng = np.random.RandomState(0)
-    z0 = np.asarray(MEAN0[problem], np.float64) + 1e-2 * rng.randn(B, n)
-    U = (10.0 if big_U else 0.1) * rng.randn(B, N, m)
-    return z0, U
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle_trial(problem, B, N, T, big_U, table):
     """The oracle's MPC loop per trajectory, f64: (X, U, states, attempts),
-    the model of trajectory b `_perturbed(problem, B, 12)`'s row with `table`
-    (else the shared problem), its plant `_perturbed(problem, B, 11)`'s."""
-    from test_gpu_parity import BOUND
+    the model of trajectory b `perturbed(problem, B, 12)`'s row with `table`
+    (else the shared problem), its plant `perturbed(problem, B, 11)`'s."""
     o = orc.load(np.float64)
-    z0, U0 = _inputs(problem, B, N, big_U)
-    plant_ops = _perturbed(problem, B, 11)[3]
-    model_ops = _perturbed(problem, B, 12)[3] if table else \
+    z0, U0 = mpc_inputs(problem, B, N, big_U)
+    plant_ops = perturbed(problem, B, 11)[3]
+    model_ops = perturbed(problem, B, 12)[3] if table else \
         [orc.make_problem(problem, DT[problem])] * B
     n, m = z0.shape[1], U0.shape[2]
     u_min, u_max = np.full(m, -BOUND[problem]), np.full(m, BOUND[problem])
-    alphas = _mpc_alphas_np()
+    alphas = mpc_alphas_np()
     X, Ul = np.empty((B, T + 1, n)), np.empty((B, T, m))
     states = np.empty((B, T), np.int32)
     attempts = np.empty((B, T), np.int32)
@@ -317,29 +247,9 @@ def _oracle_trial(problem, B, N, T, big_U, table):
     return X, Ul, states, attempts
 
 
-def _mpc_solver(problem, dtype, B, N, big_U=False, table=False):
-    """A solver with the 11-alpha MPC schedule on `_inputs`, the plants'
-    fields of `_perturbed(problem, B, 11)` as mpc_closed_loop's keywords."""
-    from pddp_amd.controllers.solver import ILQRSolver, mpc_alphas
-    s0, _, _, _, u_min, u_max = _setup(problem, dtype, B, N)
-    td = TDT[dtype]
-    s = ILQRSolver(s0.problem, B, N, td, "cuda", torch.from_numpy(u_min),
-                   torch.from_numpy(u_max), alphas=mpc_alphas(td, "cuda"))
-    z0, U = _inputs(problem, B, N, big_U)
-    s.z0.copy_(torch.from_numpy(z0))
-    s.U.copy_(torch.from_numpy(U))
-    if table:
-        par, xg, ug, _ = _perturbed(problem, B, 12)
-        _set_table(s, par, xg, ug)
-    par, xg, ug, plant_ops = _perturbed(problem, B, 11)
-    kw = dict(params=torch.from_numpy(par), x_goal=torch.from_numpy(xg),
-              u_goal=torch.from_numpy(ug))
-    return s, kw, plant_ops
-
-
 def _check_trial_vs_oracle(problem, big_U, R, table=False, B=5, N=20, T=6):
     Xo, Uo, states, attempts = _oracle_trial(problem, B, N, T, big_U, table)
-    s, kw, plant_ops = _mpc_solver(problem, "f64", B, N, big_U, table)
+    s, kw, plant_ops = mpc_solver(problem, "f64", B, N, big_U, table)
     r = s.mpc_closed_loop(T, R, **kw)
     torch.cuda.synchronize()
     X, U, J = r.X.cpu().numpy(), r.U.cpu().numpy(), r.J.cpu().numpy()
@@ -365,7 +275,7 @@ def _check_trial_vs_oracle(problem, big_U, R, table=False, B=5, N=20, T=6):
 @gpu
 @pytest.mark.parametrize("problem", ["cartpole", "pendulum"])
 def test_mpc_loop_vs_oracle_first_attempts(problem):
-    """B = 5, N = 20, T = 6, z0 and U as in _setup: every control step of
+    """B = 5, N = 20, T = 6, z0 and U as in make_solver: every control step of
     every trajectory is accepted at its first attempt; one round per step."""
     attempts = _oracle_trial(problem, 5, 20, 6, False, False)[3]
     assert (attempts == 1).all(), attempts
@@ -405,15 +315,15 @@ def test_mpc_loop_f32_vs_the_composed_trial():
     pddp_nominal_rollout_batch at N = 1 on the plant rows, a torch shift."""
     from pddp_amd import _native
     B, N, T, R = 64, 25, 5, 2
-    s, _, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N)
-    s2 = _setup("cartpole", "f32", B, N)[0]
-    par, xg, ug, plant_ops = _perturbed("cartpole", B, 11)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N)
+    s2 = make_solver("cartpole", "f32", B, N)[0]
+    par, xg, ug, plant_ops = perturbed("cartpole", B, 11)
     r = s.mpc_closed_loop(T, R, params=torch.from_numpy(par),
                           x_goal=torch.from_numpy(xg),
                           u_goal=torch.from_numpy(ug))
     torch.cuda.synchronize()
     assert s._one_launch is True, "the one-launch round did not apply"
-    rows = _dev(_plant_rows("cartpole", B, 1, 11, "f32")[0][:, 0], "f32")
+    rows = to_device(plant_rows("cartpole", B, 1, 11, "f32")[0][:, 0], "f32")
     z, Un = torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda()
     Xc = torch.empty(B, T + 1, s.n, device="cuda")
     Uc = torch.empty(B, T, s.m, device="cuda")
@@ -466,10 +376,10 @@ def test_mpc_loop_continues_bit_for_bit():
     B, N, T = 5, 20, 6
     rng = np.random.RandomState(6)
     dist = torch.from_numpy(rng.uniform(-0.01, 0.01, (B, T, 4)))
-    whole, kw, plant_ops = _mpc_solver("cartpole", "f64", B, N)
+    whole, kw, plant_ops = mpc_solver("cartpole", "f64", B, N)
     z0 = whole.z0.clone()
     a = whole.mpc_closed_loop(T, 2, z0=z0, disturbance=dist, **kw)
-    halves = _mpc_solver("cartpole", "f64", B, N)[0]
+    halves = mpc_solver("cartpole", "f64", B, N)[0]
     h1 = halves.mpc_closed_loop(3, 2, z0=z0, disturbance=dist[:, :3], **kw)
     h2 = halves.mpc_closed_loop(3, 2, disturbance=dist[:, 3:], **kw)
     torch.cuda.synchronize()
@@ -511,7 +421,7 @@ def test_mpc_loop_refuses_wrong_arguments():
     from pddp_amd.controllers.solver import ILQRSolver
     from pddp_amd.examples import cartpole
     B, N = 3, 8
-    s = _setup("cartpole", "f64", B, N)[0]
+    s = make_solver("cartpole", "f64", B, N)[0]
     ok = dict(steps=2, rounds_per_step=1)
     bad = [dict(z0=torch.zeros(B, 5)), dict(z0=torch.zeros(B + 1, 4)),
            dict(disturbance=torch.zeros(B, 3, 4)),
@@ -534,8 +444,8 @@ def test_mpc_loop_refuses_wrong_arguments():
     with pytest.raises(_native.NativeError):
         sd.mpc_closed_loop(2, 1)
     # `active`: the skipped trajectory NaN / 0, the others as without it
-    s.z0.copy_(torch.from_numpy(_inputs("cartpole", B, N, False)[0]))
-    s.U.copy_(torch.from_numpy(_inputs("cartpole", B, N, False)[1]))
+    s.z0.copy_(torch.from_numpy(mpc_inputs("cartpole", B, N, False)[0]))
+    s.U.copy_(torch.from_numpy(mpc_inputs("cartpole", B, N, False)[1]))
     z0, U0 = s.z0.clone(), s.U.clone()
     full = s.mpc_closed_loop(3, 2)
     s.U.copy_(U0)

@@ -7,17 +7,15 @@ pddp_closed_loop_noisy_*'s generator with S = 1, control step t its step
 step_offset + t, stream 0 the process and stream 1 the measurement noise.  With
 measurement noise the plant's state is `x_true`; z0 / Z[:, 0] hold what the
 controller sees.  Every expected value is the CPU oracle stepped under that
-law with the numpy model of the draws (test_closed_loop_noise.model_draws), so
+law with the numpy model of the draws (solver_util.model_draws), so
 a device draw that differs from the model, a draw of the wrong (rollout, step,
 stream), or a controller that re-plans from the true state fails here.
 
-Bounds: `_tol` (1e-10 / 2e-4) where test_closed_loop_noise.py holds the same
-draws and dynamics to it; the noise-free trial's own bounds
+Bounds: `record_tol` (1e-10 / 2e-4) where test_closed_loop_noise.py holds the
+same draws and dynamics to it; the noise-free trial's own bounds
 (test_mpc_closed_loop.py) for the trials."""
 import ctypes
 import functools
-import os
-import re
 import types
 
 import numpy as np
@@ -25,18 +23,15 @@ import pytest
 import torch
 
 import oracle as orc
+from abi_util import assert_entry_points, caller, cartpole_pointers
 from golden_util import DT, np_dtype, rel_err
-from test_batch_problem import _perturbed, _tol
-from test_closed_loop import _plant_rows
-from test_closed_loop_noise import _draws_call, _std_vec, model_draws
-from test_gpu_parity import _setup
-from test_mpc_closed_loop import (CONTROLLER, REARMED, SENTINEL, UNDEFINED,
-                                  _dev, _inputs, _logs, _mpc_alphas_np,
-                                  _mpc_solver)
-from test_reference_tracking import _loop_solver, _reference, _set_ref
+from solver_util import (BOUND, CONTROLLER, draws_call, loop_solver,
+                         make_solver, model_draws, mpc_alphas_np, mpc_inputs,
+                         mpc_solver, perturbed, plant_rows, REARMED,
+                         record_tol, reference_rows, SENTINEL, set_ref,
+                         std_vec, to_device, trial_logs, UNDEFINED)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["pddp_mpc_advance_noisy_f32", "pddp_mpc_advance_noisy_f64",
            "pddp_mpc_observe_f32", "pddp_mpc_observe_f64"]
 STD = 0.02
@@ -54,13 +49,7 @@ def test_mpc_noise_entry_points_are_declared_exported_and_bound():
     one's arguments and (w_std, v_std, seed, rollout_offset, step_offset,
     x_true, Ylog) behind `disturbance`."""
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name), name
-        assert name in _native.exported_symbols(), name
-        assert name[:-4] in _native._SIGS, name
+    assert_entry_points(SYMBOLS)
     sig = _native._SIGS["pddp_mpc_advance_noisy"]
     assert len(sig) == len(_native._SIGS["pddp_mpc_advance_track"]) + 7 == 37
     assert [i for i, c in enumerate(sig) if c is ctypes.c_uint64] == [18, 19]
@@ -80,19 +69,10 @@ def test_mpc_noise_entry_points_refuse_before_any_launch():
     PDDP_E_UNSUPPORTED for a DEFAULT-encoding problem.  Observe:
     PDDP_E_BADARG for a null x, v_std or y, B or n < 1, n > PDDP_MAX_STATE (8),
     step < 0.  The non-null pointers are host words nobody reads."""
-    import pddp_amd
     from pddp_amd import _native
-    from pddp_amd.examples import cartpole
-    enc = pddp_amd.StateEncoding
-    model, cost = cartpole.CartpoleDynamicsModel(0.1), cartpole.CartpoleCost()
-    prob = model.native_problem(enc.IGNORE_UNCERTAINTY, cost)
-    prob_d = model.native_problem(enc.DEFAULT, cost)
-    pp, ppd = ctypes.addressof(prob), ctypes.addressof(prob_d)
-    word = (ctypes.c_double * 2)()
-    q = ctypes.addressof(word)
+    pp, ppd, q = cartpole_pointers()
     lib = _native.lib()
     for ty in ("f32", "f64"):
-        fn = getattr(lib, "pddp_mpc_advance_noisy_" + ty)
         #       0     1    2    3   4  5  6  7  8   9  10 11    12    13
         #       table ref  len  t0  B  N  T  t  z0  U  Z  u_min u_max plant
         good = [None, None, 0, 0, 2, 3, 4, 0, q, q, q, None, None, None,
@@ -105,12 +85,7 @@ def test_mpc_noise_entry_points_refuse_before_any_launch():
                 # 33    34
                 # fresh n_live
                 q, None]
-
-        def call(problem, **change):
-            a = list(good)
-            for k, v in change.items():
-                a[int(k[1:])] = v
-            return fn(problem, *a, None)
+        call = caller(getattr(lib, "pddp_mpc_advance_noisy_" + ty), good)
 
         assert call(pp, _15=None, _16=None) == -1, ty   # no noise at all
         assert call(pp, _20=None) == -1, ty             # v_std, no x_true
@@ -130,15 +105,9 @@ def test_mpc_noise_entry_points_refuse_before_any_launch():
                        dict(_1=q, _2=5)):
             assert call(ppd, **change) == _native.E_UNSUPPORTED, (ty, change)
 
-        ob = getattr(lib, "pddp_mpc_observe_" + ty)
         #        B  n  x  v  seed off step mask y
         ogood = [2, 4, q, q, 7, 0, 0, None, q]
-
-        def observe(**change):
-            a = list(ogood)
-            for k, v in change.items():
-                a[int(k[1:])] = v
-            return ob(*a, None)
+        observe = caller(getattr(lib, "pddp_mpc_observe_" + ty), ogood)
 
         for i in (2, 3, 8):
             assert observe(**{"_%d" % i: None}) == -1, (ty, i)
@@ -157,7 +126,7 @@ def _noisy_advance(s, T, t, logs, w=None, v=None, seed=7, off=0, step0=0,
                    x_true=None, Ylog=None, plant=None, dist=None, mask=None,
                    ref=None, ref_t0=0, b0=0):
     """pddp_mpc_advance_noisy_* on trajectories b0.. of the solver's buffers;
-    `logs` as test_mpc_closed_loop._logs; w / v: a float for every component
+    `logs` as solver_util.trial_logs; w / v: a float for every component
     or None."""
     from pddp_amd import _native
     p = _native.ptr
@@ -165,7 +134,7 @@ def _noisy_advance(s, T, t, logs, w=None, v=None, seed=7, off=0, step0=0,
     def sl(x):
         return None if x is None else x[b0:]
 
-    w_t, v_t = _std_vec(s, w), _std_vec(s, v)
+    w_t, v_t = std_vec(s, w), std_vec(s, v)
     ref_args = (None, 0, 0) if ref is None else \
         (p(sl(ref)), ref.shape[1], ref_t0)
     _native.call("pddp_mpc_advance_noisy", s.dtype,
@@ -213,9 +182,9 @@ def _check_noisy_advance(problem, dtype, variant, B=5, N=12, T=3, off=0,
     from pddp_amd import _native
     w, v = VARIANTS[variant]
     d = np_dtype(dtype)
-    s, op, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
+    s, op, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
     n = s.n
-    rows, plant_ops = _plant_rows(problem, B, 1, 11, dtype)
+    rows, plant_ops = plant_rows(problem, B, 1, 11, dtype)
     rows, plant_ops = rows[:, 0], [o[0] for o in plant_ops]
     rng = np.random.RandomState(5)
     dist = rng.uniform(-0.01, 0.01, (B, T, n)).astype(d)
@@ -229,20 +198,20 @@ def _check_noisy_advance(problem, dtype, variant, B=5, N=12, T=3, off=0,
     Wn = _unit_draws(B, step0 + T + 1, n, 0, seed, off, dtype)
     Vn = _unit_draws(B, step0 + T + 1, n, 1, seed, off, dtype)
     o = orc.load(d)
-    tol = _tol(dtype)
-    plant_t, dist_t = _dev(rows, dtype), _dev(dist, dtype)
+    tol = record_tol(dtype)
+    plant_t, dist_t = to_device(rows, dtype), to_device(dist, dtype)
     mask_t = None if mask is None else torch.from_numpy(mask).cuda()
     t_on = torch.from_numpy(on).cuda()
     for t in (0, T - 1):
         _prepare(s, z0, U)
         assert bool((s.state != UNDEFINED).any())
         s.n_live.fill_(7)
-        x_true = _dev(xt0, dtype) if v is not None else None
+        x_true = to_device(xt0, dtype) if v is not None else None
         Ylog = torch.full((B, T + 1, n), SENTINEL, dtype=s.dtype,
                           device="cuda") if v is not None else None
         pre = {k: getattr(s, k).clone() for k in STATE}
         J0 = 1.5 if t > 0 else SENTINEL
-        logs = _logs(s, T, J0)
+        logs = trial_logs(s, T, J0)
         logs0 = [x.clone() for x in logs]
         _noisy_advance(s, T, t, logs, w, v, seed, off, step0, x_true, Ylog,
                        plant_t, dist_t, mask_t)
@@ -309,7 +278,7 @@ def _check_noisy_advance(problem, dtype, variant, B=5, N=12, T=3, off=0,
             for x, x0 in zip(logs, logs0):
                 assert torch.equal(x[t_off], x0[t_off])
             if v is not None:
-                assert torch.equal(x_true[t_off], _dev(xt0, dtype)[t_off])
+                assert torch.equal(x_true[t_off], to_device(xt0, dtype)[t_off])
                 assert bool((Ylog[t_off] == SENTINEL).all())
 
 
@@ -347,15 +316,15 @@ def test_noisy_advance_of_a_part_of_the_batch_is_bit_equal(dtype):
     """rollout_offset = 3, step_offset = 2: the launch on trajectories 1..
     with rollout_offset 4 writes, bit for bit, rows 1.. of the full launch."""
     B, N, T, t = 5, 12, 3, 1
-    s, _, z0, U, _, _ = _setup("cartpole", dtype, B, N)
-    xt0 = _dev(z0 + 0.03, dtype)
+    s, _, z0, U, _, _ = make_solver("cartpole", dtype, B, N)
+    xt0 = to_device(z0 + 0.03, dtype)
     got = []
     for b0, off in ((0, 3), (1, 4)):
         _prepare(s, z0, U)
         x_true = xt0.clone()
         Ylog = torch.full((B, T + 1, s.n), SENTINEL, dtype=s.dtype,
                           device="cuda")
-        logs = _logs(s, T, 1.5)
+        logs = trial_logs(s, T, 1.5)
         _noisy_advance(s, T, t, logs, STD, STD, 7, off, 2, x_true, Ylog,
                        b0=b0)
         got.append([x.clone() for x in
@@ -369,13 +338,13 @@ def test_noisy_advance_of_a_part_of_the_batch_is_bit_equal(dtype):
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 @pytest.mark.parametrize("problem", MODELS)
 def test_observe_vs_model_and_bit_equal_to_the_advance(problem, dtype):
-    """pddp_mpc_observe_* is x + v_std * model_draws within _tol, leaves a
+    """pddp_mpc_observe_* is x + v_std * model_draws within record_tol, leaves a
     masked row alone, and is bit-equal to the y the advance wrote for the same
     (rollout, step) from the same x."""
     B, N, T, t, off, step0 = 70, 6, 3, 1, 5, 2
-    s, _, z0, U, _, _ = _setup(problem, dtype, B, N)
+    s, _, z0, U, _, _ = make_solver(problem, dtype, B, N)
     n = s.n
-    x = _dev(z0, dtype)
+    x = to_device(z0, dtype)
     mask = torch.ones(B, dtype=torch.uint8, device="cuda")
     mask[3] = 0
     y = _observe(x, STD, 7, off, 4, mask)
@@ -383,12 +352,12 @@ def test_observe_vs_model_and_bit_equal_to_the_advance(problem, dtype):
     on = mask.bool().cpu().numpy()
     e = rel_err(y.cpu().numpy()[on], want[on])
     print(problem, dtype, e)
-    assert e < _tol(dtype), e
+    assert e < record_tol(dtype), e
     assert bool((y[3] == SENTINEL).all())
     assert not torch.equal(y[mask.bool()], x[mask.bool()])
     s.set_nominal(x, torch.from_numpy(U).cuda())
     x_true = x.clone()
-    logs = _logs(s, T, 1.5)
+    logs = trial_logs(s, T, 1.5)
     _noisy_advance(s, T, t, logs, None, STD, 7, off, step0, x_true)
     assert torch.equal(_observe(x_true, STD, 7, off, step0 + t + 1), s.z0)
 
@@ -402,15 +371,14 @@ def _oracle_noisy_trial(problem, B, N, T, w, v, seed):
     """The oracle's MPC loop per trajectory under the noisy law, f64: (X, Y, U,
     states, attempts) - `fit` from y_t, the plant step from x_t, the model's
     normals scaled by the stds; the shared problem as every controller's
-    model, the plants `_perturbed(problem, B, 11)`'s."""
-    from test_gpu_parity import BOUND
+    model, the plants `perturbed(problem, B, 11)`'s."""
     o = orc.load(np.float64)
-    z0, U0 = _inputs(problem, B, N, False)
-    plant_ops = _perturbed(problem, B, 11)[3]
+    z0, U0 = mpc_inputs(problem, B, N, False)
+    plant_ops = perturbed(problem, B, 11)[3]
     model = orc.make_problem(problem, DT[problem])
     n, m = z0.shape[1], U0.shape[2]
     u_min, u_max = np.full(m, -BOUND[problem]), np.full(m, BOUND[problem])
-    alphas = _mpc_alphas_np()
+    alphas = mpc_alphas_np()
     Wn = _unit_draws(B, T + 1, n, 0, seed, 0, "f64")
     Vn = _unit_draws(B, T + 1, n, 1, seed, 0, "f64")
     X, Y = np.empty((B, T + 1, n)), np.empty((B, T + 1, n))
@@ -452,7 +420,7 @@ def test_noisy_mpc_loop_f64_vs_oracle(problem):
     Xo, Yo, Uo, states, attempts = _oracle_noisy_trial(
         problem, B, N, T, STD, STD, TRIAL_SEED)
     assert (attempts <= TRIAL_R).all(), attempts
-    s, kw, plant_ops = _mpc_solver(problem, "f64", B, N)
+    s, kw, plant_ops = mpc_solver(problem, "f64", B, N)
     r = s.mpc_closed_loop(T, TRIAL_R, process_std=STD, obs_std=STD,
                           seed=TRIAL_SEED, **kw)
     torch.cuda.synchronize()
@@ -483,9 +451,9 @@ def test_noisy_mpc_loop_f32_vs_the_composed_trial():
     scaled draws of closed_loop_draws(steps=), a torch shift."""
     from pddp_amd import _native
     B, N, T, R, seed = 64, 25, 5, 2, 11
-    s, _, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N)
-    s2 = _setup("cartpole", "f32", B, N)[0]
-    par, xg, ug, plant_ops = _perturbed("cartpole", B, 11)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N)
+    s2 = make_solver("cartpole", "f32", B, N)[0]
+    par, xg, ug, plant_ops = perturbed("cartpole", B, 11)
     r = s.mpc_closed_loop(T, R, params=torch.from_numpy(par),
                           x_goal=torch.from_numpy(xg),
                           u_goal=torch.from_numpy(ug), process_std=STD,
@@ -495,7 +463,7 @@ def test_noisy_mpc_loop_f32_vs_the_composed_trial():
     W = STD * s2.closed_loop_draws(1, "process", seed=seed,
                                    steps=T + 1)[:, :, 0]
     V = STD * s2.closed_loop_draws(1, "obs", seed=seed, steps=T + 1)[:, :, 0]
-    rows = _dev(_plant_rows("cartpole", B, 1, 11, "f32")[0][:, 0], "f32")
+    rows = to_device(plant_rows("cartpole", B, 1, 11, "f32")[0][:, 0], "f32")
     x = torch.from_numpy(z0).to(dtype=torch.float32, device="cuda")
     Un = torch.from_numpy(U).to(dtype=torch.float32, device="cuda")
     y = x + V[:, 0]
@@ -558,9 +526,9 @@ def test_noisy_mpc_loop_sees_the_noise_of_closed_loop_draws(problem):
     seed=7, steps=T)[:, :, 0]) at the f64 trial's bounds (two kernels: to
     rounding, not bit for bit)."""
     B, N, T, R = 5, 20, 6, 3
-    a, kw, _ = _mpc_solver(problem, "f64", B, N)
+    a, kw, _ = mpc_solver(problem, "f64", B, N)
     ra = a.mpc_closed_loop(T, R, process_std=STD, seed=7, **kw)
-    b = _mpc_solver(problem, "f64", B, N)[0]
+    b = mpc_solver(problem, "f64", B, N)[0]
     D = STD * b.closed_loop_draws(1, "process", seed=7, steps=T)[:, :, 0]
     assert tuple(D.shape) == (B, T, a.n)
     rb = b.mpc_closed_loop(T, R, disturbance=D.contiguous(), **kw)
@@ -575,7 +543,7 @@ def test_noisy_mpc_loop_sees_the_noise_of_closed_loop_draws(problem):
     Ja, Jb = ra.J.cpu().numpy(), rb.J.cpu().numpy()
     assert (np.abs(Ja - Jb) <= 1e-10 * np.abs(Jb)).all(), (Ja, Jb)
     # (the noise is there)
-    c = _mpc_solver(problem, "f64", B, N)[0]
+    c = mpc_solver(problem, "f64", B, N)[0]
     rc = c.mpc_closed_loop(T, R, **kw)
     assert not np.allclose(rc.X.cpu().numpy(), ra.X.cpu().numpy(), rtol=1e-3,
                            atol=1e-5)
@@ -585,13 +553,13 @@ def test_noisy_mpc_loop_sees_the_noise_of_closed_loop_draws(problem):
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_noisy_mpc_loop_is_reproducible(dtype):
     """The same call twice: every output bit for bit; another seed: another X;
-    stds of exactly 0: the plain trial within _tol; both stds None: bit for
+    stds of exactly 0: the plain trial within record_tol; both stds None: bit for
     bit the call without the keywords."""
     B, N, T, R = 5, 20, 4, 2
     noise = dict(process_std=STD, obs_std=STD, seed=7)
 
     def run(**more):
-        s, kw, _ = _mpc_solver("cartpole", dtype, B, N)
+        s, kw, _ = mpc_solver("cartpole", dtype, B, N)
         r = s.mpc_closed_loop(T, R, **dict(kw, **more))
         torch.cuda.synchronize()
         return s, r
@@ -617,7 +585,7 @@ def test_noisy_mpc_loop_is_reproducible(dtype):
         e = rel_err(getattr(zero, nm).cpu().numpy(),
                     getattr(plain, nm).cpu().numpy())
         print(dtype, nm, e)
-        assert e < _tol(dtype), (nm, e)
+        assert e < record_tol(dtype), (nm, e)
     assert torch.equal(zero.Y, zero.X)
 
 
@@ -630,11 +598,11 @@ def test_noisy_mpc_loop_continues_bit_for_bit():
                  sample_offset=4)
     rng = np.random.RandomState(6)
     dist = torch.from_numpy(rng.uniform(-0.01, 0.01, (B, T, 4)))
-    whole, kw, _ = _mpc_solver("cartpole", "f64", B, N)
+    whole, kw, _ = mpc_solver("cartpole", "f64", B, N)
     kw = dict(kw, **noise)
     z0 = whole.z0.clone()
     a = whole.mpc_closed_loop(T, R, z0=z0, disturbance=dist, **kw)
-    halves = _mpc_solver("cartpole", "f64", B, N)[0]
+    halves = mpc_solver("cartpole", "f64", B, N)[0]
     h1 = halves.mpc_closed_loop(3, R, z0=z0, disturbance=dist[:, :3], **kw)
     assert halves.x_true is not None
     h2 = halves.mpc_closed_loop(3, R, disturbance=dist[:, 3:], step_offset=3,
@@ -653,7 +621,7 @@ def test_noisy_mpc_loop_continues_bit_for_bit():
     assert torch.equal(whole.z0, a.Y[:, T])
     # the first half's cost holds a terminal cost the whole trial's does not
     o = orc.load(np.float64)
-    plant_ops = _perturbed("cartpole", B, 11)[3]
+    plant_ops = perturbed("cartpole", B, 11)[3]
     x3 = h1.X[:, 3].cpu().numpy()
     for b in range(B):
         term = o.cost(plant_ops[b], x3[b], None, terminal=True)[0]
@@ -669,16 +637,16 @@ def test_noisy_mpc_loop_continues_bit_for_bit():
 @gpu
 def test_noisy_mpc_loop_on_a_constant_reference_is_the_untracked_one():
     """f64, both noises: every reference row the problem's own goals - the
-    noisy tracked trial agrees with the noisy untracked one within _tol."""
+    noisy tracked trial agrees with the noisy untracked one within record_tol."""
     B, N, T, R = 3, 8, 6, 2
     noise = dict(process_std=STD, obs_std=STD, seed=7)
-    s = _loop_solver("cartpole", "f64", B, N)
+    s = loop_solver("cartpole", "f64", B, N)
     base = orc.make_problem("cartpole", DT["cartpole"])
     xr = np.tile(np.array(base.x_goal[:base.aug_size]), (B, 4, 1))
     ur = np.tile(np.array(base.u_goal[:base.action_size]), (B, 4, 1))
-    _set_ref(s, xr, ur, 1)
+    set_ref(s, xr, ur, 1)
     r = s.mpc_closed_loop(T, R, **noise)
-    u = _loop_solver("cartpole", "f64", B, N)
+    u = loop_solver("cartpole", "f64", B, N)
     ru = u.mpc_closed_loop(T, R, **noise)
     torch.cuda.synchronize()
     assert s.ref_start == 1 + T
@@ -686,7 +654,7 @@ def test_noisy_mpc_loop_on_a_constant_reference_is_the_untracked_one():
     for nm in ("X", "Y", "U", "J"):
         e = rel_err(getattr(r, nm).cpu().numpy(), getattr(ru, nm).cpu().numpy())
         print(nm, e)
-        assert e < _tol("f64"), (nm, e)
+        assert e < record_tol("f64"), (nm, e)
 
 
 @gpu
@@ -699,22 +667,22 @@ def test_noisy_mpc_loop_with_a_moving_reference_equals_the_composed_trial(
     and the noisy advance, bit for bit."""
     B, N, T, R, L, seed = 3, 8, 6, 2, 10, 7
     problem = "cartpole"
-    xr, ur = _reference(problem, B, L, seed=41)
-    s = _loop_solver(problem, dtype, B, N)
-    _set_ref(s, xr, ur, 1)
+    xr, ur = reference_rows(problem, B, L, seed=41)
+    s = loop_solver(problem, dtype, B, N)
+    set_ref(s, xr, ur, 1)
     r = s.mpc_closed_loop(T, R, process_std=STD, obs_std=STD, seed=seed)
     torch.cuda.synchronize()
     assert s.ref_start == 1 + T
     assert bool(torch.isfinite(r.J).all())
     # the reference matters: the same trial under the problem's one goal
-    s1 = _loop_solver(problem, dtype, B, N)
+    s1 = loop_solver(problem, dtype, B, N)
     r1 = s1.mpc_closed_loop(T, R, process_std=STD, obs_std=STD, seed=seed)
     assert not torch.equal(r1.J, r.J)
-    c = _loop_solver(problem, dtype, B, N)
-    _set_ref(c, xr, ur, 0)
+    c = loop_solver(problem, dtype, B, N)
+    set_ref(c, xr, ur, 0)
     x_true = c.z0.clone()
     c.set_nominal(_observe(x_true, STD, seed, 0, 0), c.U)
-    logs = _logs(c, T, SENTINEL)
+    logs = trial_logs(c, T, SENTINEL)
     Y = torch.full((B, T + 1, c.n), SENTINEL, dtype=c.dtype, device="cuda")
     Y[:, 0] = c.z0
     for t in range(T):
@@ -740,7 +708,7 @@ def test_noisy_mpc_loop_keywords():
     from pddp_amd.controllers.solver import ILQRSolver
     from pddp_amd.examples import cartpole
     B, N, T = 3, 8, 4
-    s = _loop_solver("cartpole", "f64", B, N)
+    s = loop_solver("cartpole", "f64", B, N)
     z0, U0 = s.z0.clone(), s.U.clone()
     v = torch.tensor([0.01, 0.02, 0.03, 0.04], dtype=torch.float64)
     r = s.mpc_closed_loop(T, 2, z0=z0, obs_std=v, seed=5, sample_offset=2,
@@ -789,9 +757,9 @@ def test_noisy_mpc_loop_keywords():
     for which, w in (("process", 0), ("obs", 1)):
         got = s.closed_loop_draws(2, which, seed=7, sample_offset=3, steps=T)
         assert tuple(got.shape) == (B, T, 2, 4)
-        assert torch.equal(got, _draws_call(B, T, 2, 4, w, 7, 3, "f64"))
+        assert torch.equal(got, draws_call(B, T, 2, 4, w, 7, 3, "f64"))
         assert torch.equal(s.closed_loop_draws(2, which, seed=7,
                                                sample_offset=3),
-                           _draws_call(B, N, 2, 4, w, 7, 3, "f64"))
+                           draws_call(B, N, 2, 4, w, 7, 3, "f64"))
     with pytest.raises(_native.NativeError):
         s.closed_loop_draws(1, steps=0)

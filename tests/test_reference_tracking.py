@@ -13,8 +13,6 @@ to float32 like every constant of a pddp_problem) move records and costs by
 parts in ten, orders of magnitude above the bars - the project's own: 1e-10 in
 f64, the records' / line search's 2e-4 in f32.  A kernel that ignores the
 reference, reads a neighbour's row or misses the clamp fails the comparisons."""
-import ctypes
-import os
 import re
 import types
 
@@ -23,18 +21,19 @@ import pytest
 import torch
 
 import oracle as orc
+from abi_util import assert_entry_points, cartpole_pointers, HDR
 from golden_util import DT, FWD_NAMES, np_dtype, rel_err
-from test_batch_problem import _perturbed, _set_table, _tol, _views
-from test_gpu_parity import PROBLEMS, TDT, _setup
+from solver_util import (BOUND, CONTROLLER, fresh_ops, loop_solver,
+                         make_solver, MEAN0, mpc_advance, named_views,
+                         perturbed, PROBLEMS, record_tol, ref_row, ref_tensor,
+                         reference_rows, same_bits, SENTINEL, set_ref,
+                         set_table, TDT, to_device, trial_logs, under_row)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("derivs", "line_search", "mpc_advance")
 NEW_SYMBOLS = ["pddp_%s_track_%s" % (k, t) for k in KINDS
                for t in ("f32", "f64")]
-SENTINEL = -7.25
 COST_NAMES = ("L", "L_z", "L_u", "L_zz", "L_uz", "L_uu")
-CONTROLLER = ("mu", "delta", "state", "iter", "active", "fresh")
 # augmented row i of each model: (state column, 0 copy / 1 sin / 2 cos)
 # (ModelDims of csrc/models.hpp)
 AUG = {"cartpole": ((0, 1, 3, 2, 2), (0, 0, 0, 1, 2)),
@@ -43,41 +42,13 @@ AUG = {"cartpole": ((0, 1, 3, 2, 2), (0, 0, 0, 1, 2)),
        "rendezvous": (tuple(range(8)), (0,) * 8)}
 
 
-def _reference(problem, B, L, seed):
-    """(x_ref [B][L][na], u_ref [B][L][m]): float64 arrays of float32 values."""
-    rng = np.random.RandomState(seed)
-    base = orc.make_problem(problem, DT[problem])
-    na, m = base.aug_size, base.action_size
-    xr = np.array(base.x_goal[:na]) + rng.uniform(-0.5, 0.5, (B, L, na))
-    ur = np.array(base.u_goal[:m]) + rng.uniform(-0.2, 0.2, (B, L, m))
-    return (xr.astype(np.float32).astype(np.float64),
-            ur.astype(np.float32).astype(np.float64))
-
-
-def _row(L, t0, i):
-    return min(t0 + i, L - 1)
-
-
-def _under(op, xr_b, ur_b, row):
-    """`op` with the goals of reference row `row` of its trajectory."""
-    for i in range(op.aug_size):
-        op.x_goal[i] = xr_b[row, i]
-    for i in range(op.action_size):
-        op.u_goal[i] = ur_b[row, i]
-    return op
-
-
-def _fresh_ops(problem, B):
-    return [orc.make_problem(problem, DT[problem]) for _ in range(B)]
-
-
 def _forward_tracked(o, op, z0, U, u_min, u_max, xr_b, ur_b, t0):
     """Oracle.forward's dictionary with every cost entry taken step by step
     under that step's reference row (Z, F_z, F_u read no goal)."""
     f = o.forward(op, z0, U, u_min, u_max)
     N, L = U.shape[0], xr_b.shape[0]
     for t in range(N + 1):
-        _under(op, xr_b, ur_b, _row(L, t0, t))
+        under_row(op, xr_b, ur_b, ref_row(L, t0, t))
         if t < N:
             u = U[t] if u_min is None else np.clip(U[t], u_min, u_max)
             c = o.cost(op, f["Z"][t], u)
@@ -96,23 +67,13 @@ def _cost_tracked(o, op, Zn, Un, xr_b, ur_b, t0):
     N, A, L = Un.shape[0], Un.shape[1], xr_b.shape[0]
     J = np.zeros(A, Zn.dtype)
     for t in range(N + 1):
-        _under(op, xr_b, ur_b, _row(L, t0, t))
+        under_row(op, xr_b, ur_b, ref_row(L, t0, t))
         for a in range(A):
             if t < N:
                 J[a] += o.cost(op, Zn[t, a], Un[t, a])[0]
             else:
                 J[a] += o.cost(op, Zn[t, a], None, terminal=True)[0]
     return J
-
-
-def _set_ref(s, xr, ur, start=0):
-    s.set_reference(torch.from_numpy(xr),
-                    None if ur is None else torch.from_numpy(ur), start)
-
-
-def _same_bits(a, b):
-    return torch.equal(a, b) or bool(
-        ((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
 
 
 # ---------------------------------------------------------------------------
@@ -123,14 +84,8 @@ def test_track_entry_points_are_declared_exported_and_bound():
     """CPU: the six entry points in the header, the built library and
     _native._SIGS; the row layout of the header == _native's constants."""
     from pddp_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "pddp_hip.h")).read()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name), name
-        assert name in _native.exported_symbols(), name
-        assert name[:-4] in _native._SIGS, name
-    defs = dict(re.findall(r"#define\s+(PDDP_REF_\w+)\s+(\d+)", hdr))
+    assert_entry_points(NEW_SYMBOLS)
+    defs = dict(re.findall(r"#define\s+(PDDP_REF_\w+)\s+(\d+)", HDR))
     assert {k: int(v) for k, v in defs.items()} == {
         "PDDP_REF_ROW": _native.REF_ROW,
         "PDDP_REF_X_GOAL": _native.REF_X_GOAL,
@@ -153,16 +108,8 @@ def test_track_entry_points_refuse_before_any_launch():
     null required pointer / a non-positive size of the siblings;
     PDDP_E_UNSUPPORTED for a Gaussian encoding.  The non-null pointers are
     host words nobody reads."""
-    import pddp_amd
     from pddp_amd import _native
-    from pddp_amd.examples import cartpole
-    enc = pddp_amd.StateEncoding
-    model, cost = cartpole.CartpoleDynamicsModel(0.1), cartpole.CartpoleCost()
-    prob = model.native_problem(enc.IGNORE_UNCERTAINTY, cost)
-    prob_d = model.native_problem(enc.DEFAULT, cost)
-    pp, ppd = ctypes.addressof(prob), ctypes.addressof(prob_d)
-    word = (ctypes.c_double * 2)()
-    q = ctypes.addressof(word)
+    pp, ppd, q = cartpole_pointers()
     lib = _native.lib()
     # after (problem, table): ref, ref_len, ref_t0, then the sibling's
     tails = {
@@ -200,7 +147,6 @@ def test_composed_oracle_equals_the_oracle_on_a_constant_reference():
     """CPU: the composition the GPU tests compare against, on a reference
     whose every row is the problem's own goals, is Oracle.forward /
     Oracle.trajectory_cost themselves (f64)."""
-    from test_gpu_parity import BOUND, MEAN0
     o = orc.load(np.float64)
     for problem in PROBLEMS:
         op = orc.make_problem(problem, DT[problem])
@@ -228,20 +174,20 @@ def test_composed_oracle_equals_the_oracle_on_a_constant_reference():
 # ---------------------------------------------------------------------------
 
 def _check_records(problem, dtype, B, N, L, t0, table):
-    s, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
-    ops = _fresh_ops(problem, B)
+    s, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
+    ops = fresh_ops(problem, B)
     if table:
-        par, xg, ug, ops = _perturbed(problem, B, seed=31)
-        _set_table(s, par, xg, ug)
-    xr, ur = _reference(problem, B, L, seed=32)
-    _set_ref(s, xr, ur, t0)
+        par, xg, ug, ops = perturbed(problem, B, seed=31)
+        set_table(s, par, xg, ug)
+    xr, ur = reference_rows(problem, B, L, seed=32)
+    set_ref(s, xr, ur, t0)
     assert tuple(s.reference.shape) == (B, L, 12) and s.ref_start == t0
     assert s.reference.dtype == TDT[dtype] and s.reference.is_cuda
     s.nominal_rollout()
     s.derivs(set_state=False)
-    views = _views(s)
+    views = named_views(s)
     o = orc.load(np_dtype(dtype))
-    tol = _tol(dtype)
+    tol = record_tol(dtype)
     for b in range(B):
         ref = _forward_tracked(o, ops[b], z0[b], U[b], u_min, u_max, xr[b],
                                ur[b], t0)
@@ -297,19 +243,19 @@ def test_track_records_honour_the_mask(dtype):
 
 def _check_search(problem, dtype, B, N, alphas, L, t0, table):
     from pddp_amd.controllers.solver import ILQRSolver
-    s0, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
+    s0, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
     td = TDT[dtype]
     s = s0 if alphas is None else ILQRSolver(
         s0.problem, B, N, td, "cuda", torch.from_numpy(u_min),
         torch.from_numpy(u_max), alphas=alphas.to(td))
     s.z0.copy_(s0.z0)
     s.U.copy_(s0.U)
-    ops = _fresh_ops(problem, B)
+    ops = fresh_ops(problem, B)
     if table:
-        par, xg, ug, ops = _perturbed(problem, B, seed=33)
-        _set_table(s, par, xg, ug)
-    xr, ur = _reference(problem, B, L, seed=34)
-    _set_ref(s, xr, ur, t0)
+        par, xg, ug, ops = perturbed(problem, B, seed=33)
+        set_table(s, par, xg, ug)
+    xr, ur = reference_rows(problem, B, L, seed=34)
+    set_ref(s, xr, ur, t0)
     s.nominal_rollout()
     s.derivs(set_state=False)
     regv = torch.full((B,), 1.0, dtype=torch.float64, device="cuda")
@@ -322,7 +268,7 @@ def _check_search(problem, dtype, B, N, alphas, L, t0, table):
     Uc = s.Uc.permute(1, 0, 2, 3).cpu().numpy()
     Jc = s.Jc.cpu().numpy()
     o = orc.load(np_dtype(dtype))
-    tol = _tol(dtype)
+    tol = record_tol(dtype)
     for b in range(B):
         Zn, Un = o.control_law(ops[b], s.Z[b].cpu().numpy(), U[b],
                                k[b].cpu().numpy(), K[b].cpu().numpy(),
@@ -385,14 +331,14 @@ def test_constant_reference_equals_the_table(problem, dtype):
     u_goal): records, candidates and costs against the _batch_ entry points'
     on the same inputs and gains, then one round() from the same nominal."""
     B, N = 3, 12
-    tol = _tol(dtype)
-    par, xg, ug, _ = _perturbed(problem, B, seed=35)
+    tol = record_tol(dtype)
+    par, xg, ug, _ = perturbed(problem, B, seed=35)
 
     def solver(tracking):
-        s, _, z0, U, _, _ = _setup(problem, dtype, B, N)
-        _set_table(s, par, xg, ug)
+        s, _, z0, U, _, _ = make_solver(problem, dtype, B, N)
+        set_table(s, par, xg, ug)
         if tracking:
-            _set_ref(s, np.repeat(xg[:, None], 4, 1), None, 1)
+            set_ref(s, np.repeat(xg[:, None], 4, 1), None, 1)
         return s, torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda()
 
     s, z0, U = solver(False)
@@ -405,7 +351,7 @@ def test_constant_reference_equals_the_table(problem, dtype):
     for x in (s, st):
         x.nominal_rollout()
         x.derivs(set_state=False)
-        r = {k: v.clone() for k, v in _views(x).items()}
+        r = {k: v.clone() for k, v in named_views(x).items()}
         r["J_opt"] = x.J_opt.clone()
         if gains is None:
             regv = torch.full((B,), 1.0, dtype=torch.float64, device="cuda")
@@ -421,7 +367,7 @@ def test_constant_reference_equals_the_table(problem, dtype):
     for nm in out[0]:
         e = rel_err(out[1][nm].cpu().numpy(), out[0][nm].cpu().numpy())
         print(problem, dtype, nm, e, "same bits:",
-              _same_bits(out[1][nm], out[0][nm]))
+              same_bits(out[1][nm], out[0][nm]))
         assert e < tol, (nm, e)
     # one round from the same nominal
     for x in (s, st):
@@ -434,7 +380,7 @@ def test_constant_reference_equals_the_table(problem, dtype):
         e = rel_err(getattr(st, nm).cpu().numpy(),
                     getattr(s, nm).cpu().numpy())
         print(problem, dtype, "round", nm, e, "same bits:",
-              _same_bits(getattr(st, nm), getattr(s, nm)))
+              same_bits(getattr(st, nm), getattr(s, nm)))
         assert e < tol, (nm, e)
 
 
@@ -455,9 +401,8 @@ def test_cost_vanishes_on_a_feasible_reference(problem):
     augment(Z*) / U*: at (Z*, U*) J <= 1e-20 and |L_z|, |L_u| < 1e-12; from
     U = U* / 2, fit(max_rounds=6) never increases any trajectory's J_opt
     (fewer rounds where every trajectory has left the fit loop by then)."""
-    from test_gpu_parity import BOUND
     B, N = 3, 12
-    s, _, z0, _, u_min, u_max = _setup(problem, "f64", B, N)
+    s, _, z0, _, u_min, u_max = make_solver(problem, "f64", B, N)
     rng = np.random.RandomState(36)
     Us = rng.uniform(-0.8, 0.8, (B, N, s.m)) * BOUND[problem]
     z0t, Ust = torch.from_numpy(z0).cuda(), torch.from_numpy(Us).cuda()
@@ -466,7 +411,7 @@ def test_cost_vanishes_on_a_feasible_reference(problem):
     Zs = s.Z.cpu().numpy()
     xr = _augment(problem, Zs)
     ur = np.concatenate([Us, Us[:, -1:]], 1)
-    _set_ref(s, xr, ur)
+    set_ref(s, xr, ur)
     s.derivs(set_state=False)
     torch.cuda.synchronize()
     _, _, L_z, L_u, _, _, _ = s.record_views()
@@ -492,45 +437,6 @@ def test_cost_vanishes_on_a_feasible_reference(problem):
 # 7. the advance
 # ---------------------------------------------------------------------------
 
-def _logs(s, T, J0=SENTINEL):
-    opts = dict(dtype=s.dtype, device="cuda")
-    return (torch.full((s.B, T + 1, s.n), SENTINEL, **opts),
-            torch.full((s.B, T, s.m), SENTINEL, **opts),
-            torch.full((s.B,), J0, **opts),
-            torch.full((s.B, T), -9, dtype=torch.int32, device="cuda"),
-            torch.full((s.B, T), 9, dtype=torch.uint8, device="cuda"))
-
-
-def _advance(s, T, t, logs, plant=None, dist=None, mask=None, ref=None,
-             ref_t0=0):
-    """pddp_mpc_advance[_track]_* itself on the solver's buffers."""
-    from pddp_amd import _native
-    p = _native.ptr
-    head = (ctypes.addressof(s.problem), p(s.batch_table))
-    name = "pddp_mpc_advance"
-    if ref is not None:
-        head += (p(ref), ref.shape[1], ref_t0)
-        name += "_track"
-    _native.call(name, s.dtype, *head, s.B, s.N, T, t, p(s.z0), p(s.U),
-                 p(s.Z), p(s.u_min), p(s.u_max), p(plant), p(dist), p(mask),
-                 *[p(x) for x in logs], p(s.mu), p(s.delta), p(s.state),
-                 p(s.iter), p(s.active), p(s.fresh), p(s.n_live), s._s())
-    torch.cuda.synchronize()
-
-
-def _dev(a, dtype):
-    return None if a is None else torch.from_numpy(
-        np.ascontiguousarray(a)).to(dtype=TDT[dtype], device="cuda")
-
-
-def _ref_tensor(xr, ur, dtype):
-    B, L = xr.shape[:2]
-    ref = np.zeros((B, L, 12))
-    ref[:, :, :xr.shape[2]] = xr
-    ref[:, :, 8:8 + ur.shape[2]] = ur
-    return _dev(ref, dtype)
-
-
 @gpu
 @pytest.mark.parametrize("variant", ["plain", "mask", "plant", "disturbance"])
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -542,25 +448,25 @@ def test_track_advance_equals_the_advance_on_a_constant_reference(
     row's with a plant, else the table's): z0, U, Z, the logs and the
     controller words of the two launches from the same inputs."""
     B, N, T = 5, 12, 3
-    tol = _tol(dtype)
-    s, _, z0, U, _, _ = _setup(problem, dtype, B, N)
-    par, xg, ug, _ = _perturbed(problem, B, seed=37)
-    _set_table(s, par, xg, ug)
+    tol = record_tol(dtype)
+    s, _, z0, U, _, _ = make_solver(problem, dtype, B, N)
+    par, xg, ug, _ = perturbed(problem, B, seed=37)
+    set_table(s, par, xg, ug)
     plant = dist = mask = None
     if variant == "plant":
-        ppar, xg, ug, _ = _perturbed(problem, B, seed=38)
+        ppar, xg, ug, _ = perturbed(problem, B, seed=38)
         rows = np.zeros((B, 20))
         rows[:, :ppar.shape[1]] = ppar
         rows[:, 8:8 + xg.shape[1]] = xg
         rows[:, 16:16 + ug.shape[1]] = ug
-        plant = _dev(rows, dtype)
+        plant = to_device(rows, dtype)
     if variant == "disturbance":
-        dist = _dev(np.random.RandomState(5).uniform(-0.01, 0.01,
-                                                     (B, T, s.n)), dtype)
+        dist = to_device(np.random.RandomState(5).uniform(-0.01, 0.01,
+                                                          (B, T, s.n)), dtype)
     if variant == "mask":
         mask = torch.tensor([1, 1, 0, 1, 1], dtype=torch.uint8, device="cuda")
-    ref = _ref_tensor(np.repeat(xg[:, None], 2, 1), np.repeat(ug[:, None], 2, 1),
-                      dtype)
+    ref = ref_tensor(np.repeat(xg[:, None], 2, 1), np.repeat(ug[:, None], 2, 1),
+                     dtype)
     for t in (0, T - 1):
         got = []
         for r in (None, ref):
@@ -569,8 +475,8 @@ def test_track_advance_equals_the_advance_on_a_constant_reference(
             s.round(n_iterations=1)
             s.active.copy_(torch.arange(B, device="cuda") % 2)
             s.n_live.fill_(7)
-            logs = _logs(s, T, 1.5 if t > 0 else SENTINEL)
-            _advance(s, T, t, logs, plant, dist, mask, r, 1)
+            logs = trial_logs(s, T, 1.5 if t > 0 else SENTINEL)
+            mpc_advance(s, T, t, logs, plant, dist, mask, r, 1)
             got.append(dict(
                 {k: getattr(s, k).clone() for k in
                  CONTROLLER + ("z0", "U", "Z", "n_live")},
@@ -582,7 +488,7 @@ def test_track_advance_equals_the_advance_on_a_constant_reference(
                     nm not in ("mu", "delta"):
                 e = rel_err(b[nm].cpu().numpy(), a[nm].cpu().numpy())
                 print(problem, dtype, variant, t, nm, e, "same bits:",
-                      _same_bits(a[nm], b[nm]))
+                      same_bits(a[nm], b[nm]))
                 assert e < tol, (t, nm, e)
             else:
                 assert torch.equal(a[nm], b[nm]), (t, nm)
@@ -601,45 +507,31 @@ def test_track_advance_trial_cost_vs_oracle(problem, dtype, L):
     2 + t plus the terminal cost of Xlog[T] under row 2 + T, rows clamped
     (L = 4: the trial runs on the held last row from t = 1 on)."""
     B, N, T = 3, 12, 5
-    s, _, z0, U, _, _ = _setup(problem, dtype, B, N)
-    xr, ur = _reference(problem, B, L, seed=39)
-    ref = _ref_tensor(xr, ur, dtype)
+    s, _, z0, U, _, _ = make_solver(problem, dtype, B, N)
+    xr, ur = reference_rows(problem, B, L, seed=39)
+    ref = ref_tensor(xr, ur, dtype)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
-    logs = _logs(s, T)
+    logs = trial_logs(s, T, SENTINEL)
     for t in range(T):
-        _advance(s, T, t, logs, ref=ref, ref_t0=2 + t)
+        mpc_advance(s, T, t, logs, ref=ref, ref_t0=2 + t)
     X, Ul, J = (x.cpu().numpy() for x in logs[:3])
     o = orc.load(np_dtype(dtype))
-    ops = _fresh_ops(problem, B)
+    ops = fresh_ops(problem, B)
     for b in range(B):
         want = np_dtype(dtype)(0)
         for t in range(T):
-            _under(ops[b], xr[b], ur[b], _row(L, 2 + t, 0))
+            under_row(ops[b], xr[b], ur[b], ref_row(L, 2 + t, 0))
             want += o.cost(ops[b], X[b, t], Ul[b, t])[0]
-        _under(ops[b], xr[b], ur[b], _row(L, 2 + T - 1, 1))
+        under_row(ops[b], xr[b], ur[b], ref_row(L, 2 + T - 1, 1))
         want += o.cost(ops[b], X[b, T], None, terminal=True)[0]
         e = abs(float(J[b]) - float(want)) / abs(float(want))
         print(problem, dtype, L, b, e)
-        assert e < _tol(dtype), (b, e)
+        assert e < record_tol(dtype), (b, e)
 
 
 # ---------------------------------------------------------------------------
 # 8. the loop
 # ---------------------------------------------------------------------------
-
-def _loop_solver(problem, dtype, B, N, table=False):
-    from pddp_amd.controllers.solver import ILQRSolver, mpc_alphas
-    s0, _, z0, U, u_min, u_max = _setup(problem, dtype, B, N)
-    td = TDT[dtype]
-    s = ILQRSolver(s0.problem, B, N, td, "cuda", torch.from_numpy(u_min),
-                   torch.from_numpy(u_max), alphas=mpc_alphas(td, "cuda"))
-    s.z0.copy_(s0.z0)
-    s.U.copy_(s0.U)
-    if table:
-        par, xg, ug, _ = _perturbed(problem, B, seed=40)
-        _set_table(s, par, xg, ug)
-    return s
-
 
 def _assert_same_trial(a, b, sa, sb):
     for nm in ("X", "U", "J", "states", "unfinished"):
@@ -657,25 +549,25 @@ def test_mpc_loop_with_a_moving_reference_equals_the_composed_trial(problem,
     mpc_closed_loop against set_reference_start(1 + t), rounds(R,
     n_iterations=1) and the track advance, bit for bit."""
     B, N, T, R = 3, 8, 6, 2
-    xr, ur = _reference(problem, B, 20, seed=41)
-    s = _loop_solver(problem, dtype, B, N)
-    _set_ref(s, xr, ur, 1)
+    xr, ur = reference_rows(problem, B, 20, seed=41)
+    s = loop_solver(problem, dtype, B, N)
+    set_ref(s, xr, ur, 1)
     r = s.mpc_closed_loop(T, R)
     torch.cuda.synchronize()
     assert s.ref_start == 1 + T
     assert bool(torch.isfinite(r.J).all())
     # the reference matters: the same trial under the problem's one goal
-    s1 = _loop_solver(problem, dtype, B, N)
+    s1 = loop_solver(problem, dtype, B, N)
     r1 = s1.mpc_closed_loop(T, R)
     assert not torch.equal(r1.J, r.J)
-    c = _loop_solver(problem, dtype, B, N)
-    _set_ref(c, xr, ur, 0)
+    c = loop_solver(problem, dtype, B, N)
+    set_ref(c, xr, ur, 0)
     c.set_nominal(c.z0, c.U)
-    logs = _logs(c, T)
+    logs = trial_logs(c, T, SENTINEL)
     for t in range(T):
         c.set_reference_start(1 + t)
         c.rounds(R, n_iterations=1)
-        _advance(c, T, t, logs, ref=c.reference, ref_t0=1 + t)
+        mpc_advance(c, T, t, logs, ref=c.reference, ref_t0=1 + t)
         c._derivs_due = True
     composed = types.SimpleNamespace(X=logs[0], U=logs[1], J=logs[2],
                                      states=logs[3], unfinished=logs[4])
@@ -687,13 +579,13 @@ def test_mpc_loop_with_a_reference_continues_bit_for_bit():
     """f64, a table set: mpc_closed_loop(3) twice, the second with z0 = None,
     is mpc_closed_loop(6) - the window goes on where the first call left it."""
     B, N, T, R = 3, 8, 6, 2
-    xr, ur = _reference("cartpole", B, 20, seed=42)
-    whole = _loop_solver("cartpole", "f64", B, N, table=True)
-    _set_ref(whole, xr, ur, 2)
+    xr, ur = reference_rows("cartpole", B, 20, seed=42)
+    whole = loop_solver("cartpole", "f64", B, N, table=True)
+    set_ref(whole, xr, ur, 2)
     z0 = whole.z0.clone()
     a = whole.mpc_closed_loop(T, R, z0=z0)
-    halves = _loop_solver("cartpole", "f64", B, N, table=True)
-    _set_ref(halves, xr, ur, 2)
+    halves = loop_solver("cartpole", "f64", B, N, table=True)
+    set_ref(halves, xr, ur, 2)
     h1 = halves.mpc_closed_loop(3, R, z0=z0)
     assert halves.ref_start == 5
     h2 = halves.mpc_closed_loop(3, R)
@@ -711,7 +603,7 @@ def test_mpc_loop_with_a_reference_continues_bit_for_bit():
     op = orc.make_problem("cartpole", DT["cartpole"])
     x3 = h1.X[:, 3].cpu().numpy()
     for b in range(B):
-        term = o.cost(_under(op, xr[b], ur[b], 5), x3[b], None,
+        term = o.cost(under_row(op, xr[b], ur[b], 5), x3[b], None,
                       terminal=True)[0]
         want = float(h1.J[b]) - term + float(h2.J[b])
         assert abs(float(a.J[b]) - want) <= 1e-12 * abs(want), b
@@ -723,14 +615,14 @@ def test_mpc_loop_runs_on_the_held_last_row(dtype):
     """A reference of 4 rows under a trial of T = 6 with N = 8 equals, bit
     for bit, the trial with the last row repeated explicitly."""
     B, N, T, R = 3, 8, 6, 2
-    xr, ur = _reference("cartpole", B, 4, seed=43)
+    xr, ur = reference_rows("cartpole", B, 4, seed=43)
     pad = T + N + 2
     xl = np.concatenate([xr, np.repeat(xr[:, -1:], pad, 1)], 1)
     ul = np.concatenate([ur, np.repeat(ur[:, -1:], pad, 1)], 1)
-    short = _loop_solver("cartpole", dtype, B, N)
-    _set_ref(short, xr, ur, 1)
-    long_ = _loop_solver("cartpole", dtype, B, N)
-    _set_ref(long_, xl, ul, 1)
+    short = loop_solver("cartpole", dtype, B, N)
+    set_ref(short, xr, ur, 1)
+    long_ = loop_solver("cartpole", dtype, B, N)
+    set_ref(long_, xl, ul, 1)
     a, b = short.mpc_closed_loop(T, R), long_.mpc_closed_loop(T, R)
     torch.cuda.synchronize()
     _assert_same_trial(a, b, short, long_)
@@ -747,13 +639,13 @@ def test_reference_refusals_plan_and_restoration():
     from pddp_amd.controllers.solver import ILQRSolver
     from pddp_amd.examples import cartpole
     B, N = 20, 10
-    s, _, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N)
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N)
     z0t, Ut = torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda()
     fresh_plan = s._plan(0)
     assert fresh_plan == "one_launch"
-    xr, ur = _reference("cartpole", B, 6, seed=44)
+    xr, ur = reference_rows("cartpole", B, 6, seed=44)
     s._graph = ("a captured round",)
-    _set_ref(s, xr, ur, 2)
+    set_ref(s, xr, ur, 2)
     assert s._plan(0) == "records+separate"
     assert s._derivs_due is True and s._rec_stale is True
     assert s._graph is None
@@ -787,7 +679,7 @@ def test_reference_refusals_plan_and_restoration():
     s.set_batch_problem()
     s.clear_reference()
     assert s.reference is None and s._plan(0) == "records+separate"
-    _set_ref(s, xr, ur)
+    set_ref(s, xr, ur)
     s.clear_batch_problem()
     assert s._plan(0) == "records+separate"
     # ... and back: the plan and the results of a solver that never had one
@@ -825,11 +717,11 @@ def test_captured_round_with_a_reference_and_the_controller_methods():
     replay equals an eager round (f64 cartpole); iLQRController forwards
     set_reference / clear_reference to its solver."""
     B, N = 3, 8
-    xr, ur = _reference("cartpole", B, 12, seed=45)
+    xr, ur = reference_rows("cartpole", B, 12, seed=45)
     out = []
     for graph in (False, True):
-        s = _loop_solver("cartpole", "f64", B, N)
-        _set_ref(s, xr, ur, 1)
+        s = loop_solver("cartpole", "f64", B, N)
+        set_ref(s, xr, ur, 1)
         s.set_nominal(s.z0, s.U)
         if graph:
             s.capture_round()

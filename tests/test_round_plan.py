@@ -27,7 +27,8 @@ import pytest
 import torch
 
 from pddp_amd import _native
-from test_gpu_parity import BOUND, DT, MEAN0
+from golden_util import DT
+from solver_util import BOUND, MEAN0
 
 pytestmark = pytest.mark.gpu
 

@@ -13,9 +13,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from test_gpu_parity import _bnn_real_size_run  # noqa: E402
+from solver_util import bnn_real_size_run  # noqa: E402
 
 if __name__ == "__main__":
-    rows = _bnn_real_size_run()
+    rows = bnn_real_size_run()
     for r in rows:
         print(json.dumps(r))

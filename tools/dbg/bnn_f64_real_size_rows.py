@@ -5,9 +5,9 @@ import sys
 import numpy as np
 import torch
 sys.path[:0] = ["tests", "."]
-from test_gpu_parity import _bnn_real_size_run
+from solver_util import bnn_real_size_run
 raw = {}
-rows = _bnn_real_size_run(torch.float64, raw)
+rows = bnn_real_size_run(torch.float64, raw)
 for r in rows[:-1]:
     print(r["what"], r["r"], "%.3e %.3e %.3e" % (r["hip_vs_f64"], r["hip_vs_f32"], r["ref32_vs_f64"]))
 print(rows[-1])

@@ -1,12 +1,12 @@
 import sys, os
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
 import torch
-import test_gpu_parity as T
+from solver_util import bnn_real_size_run
 from pddp_amd import _native
 lib = _native.lib()
 for deal in (1, 2):
     prev = lib.pddp_bnn_mlp_deal(deal)
-    rows = T._bnn_real_size_run()
+    rows = bnn_real_size_run()
     lib.pddp_bnn_mlp_deal(prev)
     print("deal", deal)
     for r in rows[:-1]:

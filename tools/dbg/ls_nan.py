@@ -4,9 +4,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests"))
 import numpy as np, torch
 import oracle as orc
-from test_gpu_parity import _setup
+from solver_util import make_solver
 B, N = 4096, 100
-s, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=11)
+s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=11)
 s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
 s.mu.fill_(1.0)
 assert s.sweep_nominal()
@@ -28,7 +28,7 @@ for b in [0] + bad:
     print(" max|Z| per alpha (f32)", np.abs(Zn32).max((0, 2)))
     print(" state", int(s.state[b]), "argmin hip", np.argmin(np.nan_to_num(Jc[b], nan=-np.inf)), "argmin o32", np.argmin(J32))
 # the separate line search kernel on the same gains
-s2, *_ = _setup("cartpole", "f32", B, N, seed=11)
+s2, *_ = make_solver("cartpole", "f32", B, N, seed=11)
 s2._nominal_sweep = False
 s2.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
 s2.gains.copy_(s.gains)

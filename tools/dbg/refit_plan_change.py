@@ -4,13 +4,13 @@ import sys
 import torch
 sys.path[:0] = ["tests", "."]
 import pddp_amd
-from test_gpu_parity import _bnn_mpc_controller
+from solver_util import bnn_mpc_controller
 B, N = 32, 20
 enc = pddp_amd.StateEncoding.DEFAULT
 iu = torch.triu_indices(4, 4)
 tri = (0.1 * torch.eye(4))[iu[0], iu[1]].cuda()
 u_min, u_max = torch.tensor([-10.0]), torch.tensor([10.0])
-ctrl, plant, x = _bnn_mpc_controller(B, N, False, P=32, H=64)
+ctrl, plant, x = bnn_mpc_controller(B, N, False, P=32, H=64)
 model = ctrl.model
 z = torch.cat([x, tri.expand(B, -1)], -1)
 us = []

@@ -8,10 +8,10 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "tests"))
-import test_gpu_parity as T  # noqa: E402
+from solver_util import make_solver  # noqa: E402
 
 B, N = int(sys.argv[1]), int(sys.argv[2])
-s, op, z0, U, u_min, u_max = T._setup("cartpole", "f32", B, N, seed=5)
+s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=5)
 s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
 names = ("Z", "U", "L", "J_opt", "mu", "delta", "state", "iter", "active",
          "fresh", "gains", "gains_acc", "Jc", "bwd_status", "n_live", "Zc", "Uc")

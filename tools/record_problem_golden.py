@@ -75,7 +75,7 @@ def digests(a, axes):
 
 
 def table_of(prob, problem, B, seed, td):
-    """tests/test_batch_problem.py's _perturbed(): parameters x U(0.8, 1.2),
+    """tests/solver_util.py's perturbed(): parameters x U(0.8, 1.2),
     dt x U(0.9, 1.1), goals + U(-0.5, 0.5), u_goal + U(-0.2, 0.2), rounded to
     float32, over rows of the shared problem."""
     import torch

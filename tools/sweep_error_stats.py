@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import oracle as orc  # noqa: E402  (the checker)
-from test_gpu_parity import _setup  # noqa: E402
+from solver_util import make_solver  # noqa: E402
 
 
 def rel(a, b):
@@ -54,7 +54,7 @@ def main():
     args = ap.parse_args()
     B, N = args.B, args.N
     out = {"B": B, "N": N, "problem": "cartpole", "cases": []}
-    s, op, z0, U, u_min, u_max = _setup("cartpole", "f32", B, N, seed=5)
+    s, op, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N, seed=5)
     s.set_nominal(torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda())
     s.derivs(mask=s.fresh)
     o32, o64 = orc.load(np.float32), orc.load(np.float64)
