@@ -53,7 +53,7 @@
 // Cholesky directions are per-particle multiples of the mean ones.
 #include <cstdlib>
 
-#include "pddp_common.hpp"
+#include "bnn_mlp_check.hpp"
 
 namespace pddp {
 
@@ -915,36 +915,17 @@ __global__ __launch_bounds__(kMlpThreads) void bnn_mlp_kernel(BnnMlpArgs a) {
 
 template <int H, int W1S, int JVP, int LIVE, int BAL, int PREC = 0>
 static int launch_bnn_mlp_b(const BnnMlpArgs& a, hipStream_t st) {
-  // per device (a process may drive several GPUs): CU count queried once -
-  // hipGetDeviceProperties costs ms - and the > 64 KB dynamic-LDS opt-in,
-  // which is a per-device function attribute
-  constexpr int kMaxDev = 16;
-  static int cus_of[kMaxDev] = {};
-  static bool attr_set[kMaxDev] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev)
-    return PDDP_E_UNSUPPORTED;
-  if (cus_of[dev] == 0) {
-    hipDeviceProp_t prop;
-    cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess
-                      ? prop.multiProcessorCount
-                      : 256;
-  }
-  const int cus = cus_of[dev];
   // memory rows per tile: 32, or (32 / LIVE) whole groups of JVP rows
   constexpr int trows = JVP == 0 ? kMlpTile : (kMlpTile / LIVE) * JVP;
-  const int ntiles = (a.R + trows - 1) / trows;
-  const int grid = ntiles < cus ? ntiles : cus;  // persistent: one per CU
   constexpr size_t lds =
       sizeof(float) * bnn_mlp_lds_floats<H, W1S, BAL, PREC>();
   static_assert(lds <= 160 * 1024, "a workgroup's LDS");
-  if (!attr_set[dev]) {  // more than 64 KB of dynamic LDS needs the opt-in
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)bnn_mlp_kernel<H, W1S, JVP, LIVE, BAL, PREC>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set[dev] = true;
-  }
+  static PersistentKernel state;  // (of this kernel)
+  int grid;
+  if (int rc = state.prepare(
+          (const void*)bnn_mlp_kernel<H, W1S, JVP, LIVE, BAL, PREC>, lds,
+          (a.R + trows - 1) / trows, grid))
+    return rc;
   PDDP_LAUNCH((bnn_mlp_kernel<H, W1S, JVP, LIVE, BAL, PREC>), dim3(grid),
                      dim3(kMlpThreads), lds, st, a);
   return launch_status();
@@ -999,6 +980,34 @@ static int launch_bnn_mlp(const BnnMlpArgs& a, hipStream_t st) {
                       : launch_bnn_mlp_w<H, 16, JVP, LIVE>(a, st);
 }
 
+template <int JVP = 0, int LIVE = JVP>
+static int launch_bnn_mlp_h(const BnnMlpArgs& a, hipStream_t st) {
+  switch (a.H) {
+    case 64: return launch_bnn_mlp<64, JVP, LIVE>(a, st);
+    case 128: return launch_bnn_mlp<128, JVP, LIVE>(a, st);
+    case 200: return launch_bnn_mlp<200, JVP, LIVE>(a, st);
+  }
+  return PDDP_E_UNSUPPORTED;
+}
+
+// Every entry point: group 0 the plain network, else forward mode
+static int bnn_mlp_impl(const BnnMlpArgs& a, int group, int live, void* stream) {
+  if (int rc = bnn_mlp_check(a, group, live, kMlpW1Max, kMlpMaxOut)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  switch (group) {
+    case 0: return launch_bnn_mlp_h<>(a, st);
+    case 8:
+      // packed forms: 8 groups of 4 live rows or 5 groups of 6 per tile
+      // (pendulum: 1 + 2 + 1 rows, cartpole: 1 + 4 + 1); anything else runs 4
+      // groups of 8
+      if (live <= 4) return launch_bnn_mlp_h<8, 4>(a, st);
+      if (live <= 6) return launch_bnn_mlp_h<8, 6>(a, st);
+      return launch_bnn_mlp_h<8, 8>(a, st);
+    case 16: return launch_bnn_mlp_h<16, 16>(a, st);
+    default: return launch_bnn_mlp_h<32, 32>(a, st);
+  }
+}
+
 }  // namespace pddp
 
 extern "C" {
@@ -1029,11 +1038,6 @@ int pddp_bnn_mlp_f32(int R, int P, int in_dim, int H, int out_dim,
                      const float* MT1, const float* W2, const float* b2,
                      const float* MT2, const float* W3, const float* b3,
                      float* Y, void* stream) {
-  if (R <= 0 || P <= 0 || in_dim <= 0 || H <= 0 || out_dim <= 0 || !X || !W1 ||
-      !b1 || !MT1 || !W2 || !b2 || !MT2 || !W3 || !b3 || !Y)
-    return PDDP_E_BADARG;
-  if (in_dim >= pddp::kMlpW1Max || out_dim > pddp::kMlpMaxOut)
-    return PDDP_E_UNSUPPORTED;
   return pddp_bnn_mlp_rows_f32(R, P, in_dim, H, out_dim, X, W1, b1, MT1, W2, b2,
                                MT2, W3, b3, Y, nullptr, stream);
 }
@@ -1043,59 +1047,9 @@ int pddp_bnn_mlp_rows_f32(int R, int P, int in_dim, int H, int out_dim,
                           const float* MT1, const float* W2, const float* b2,
                           const float* MT2, const float* W3, const float* b3,
                           float* Y, const int32_t* live_rows, void* stream) {
-  if (R <= 0 || P <= 0 || in_dim <= 0 || H <= 0 || out_dim <= 0 || !X || !W1 ||
-      !b1 || !MT1 || !W2 || !b2 || !MT2 || !W3 || !b3 || !Y)
-    return PDDP_E_BADARG;
-  if (in_dim >= pddp::kMlpW1Max || out_dim > pddp::kMlpMaxOut)
-    return PDDP_E_UNSUPPORTED;
-  const pddp::BnnMlpArgs a{R, P, in_dim, H, out_dim, X, W1, b1, MT1, W2,
-                           b2, MT2, W3, b3, Y, live_rows};
-  hipStream_t st = (hipStream_t)stream;
-  switch (H) {
-    case 64: return pddp::launch_bnn_mlp<64>(a, st);
-    case 128: return pddp::launch_bnn_mlp<128>(a, st);
-    case 200: return pddp::launch_bnn_mlp<200>(a, st);
-  }
-  return PDDP_E_UNSUPPORTED;
-}
-
-static int bnn_mlp_jvp_impl(int R, int P, int group, int live, int in_dim,
-                            int H, int out_dim, const float* X, const float* W1,
-                            const float* b1, const float* MT1, const float* W2,
-                            const float* b2, const float* MT2, const float* W3,
-                            const float* b3, float* Y, void* stream,
-                            const int32_t* live_rows = nullptr) {
-  if (R <= 0 || P <= 0 || in_dim <= 0 || H <= 0 || out_dim <= 0 || !X || !W1 ||
-      !b1 || !MT1 || !W2 || !b2 || !MT2 || !W3 || !b3 || !Y)
-    return PDDP_E_BADARG;
-  if ((group != 8 && group != 16 && group != 32) || R % group != 0 ||
-      live < 1 || live > group)
-    return PDDP_E_BADARG;
-  if (in_dim >= pddp::kMlpW1Max || out_dim > pddp::kMlpMaxOut)
-    return PDDP_E_UNSUPPORTED;
-  const pddp::BnnMlpArgs a{R, P, in_dim, H, out_dim, X, W1, b1, MT1, W2,
-                           b2, MT2, W3, b3, Y, live_rows};
-  hipStream_t st = (hipStream_t)stream;
-#define PDDP_MLP_H(G, L)                                             \
-  switch (H) {                                                       \
-    case 64: return pddp::launch_bnn_mlp<64, G, L>(a, st);           \
-    case 128: return pddp::launch_bnn_mlp<128, G, L>(a, st);         \
-    case 200: return pddp::launch_bnn_mlp<200, G, L>(a, st);         \
-  }                                                                  \
-  return PDDP_E_UNSUPPORTED
-  if (group == 8) {
-    // packed forms: 8 groups of 4 live rows or 5 groups of 6 per tile
-    // (pendulum: 1 + 2 + 1 rows, cartpole: 1 + 4 + 1); anything else runs 4
-    // groups of 8
-    if (live <= 4) { PDDP_MLP_H(8, 4); }
-    if (live <= 6) { PDDP_MLP_H(8, 6); }
-    PDDP_MLP_H(8, 8);
-  } else if (group == 16) {
-    PDDP_MLP_H(16, 16);
-  } else {
-    PDDP_MLP_H(32, 32);
-  }
-#undef PDDP_MLP_H
+  return pddp::bnn_mlp_impl({R, P, in_dim, H, out_dim, X, W1, b1, MT1, W2, b2,
+                             MT2, W3, b3, Y, live_rows},
+                            0, 1, stream);
 }
 
 int pddp_bnn_mlp_jvp_f32(int R, int P, int group, int in_dim, int H,
@@ -1103,8 +1057,9 @@ int pddp_bnn_mlp_jvp_f32(int R, int P, int group, int in_dim, int H,
                          const float* MT1, const float* W2, const float* b2,
                          const float* MT2, const float* W3, const float* b3,
                          float* Y, void* stream) {
-  return bnn_mlp_jvp_impl(R, P, group, group, in_dim, H, out_dim, X, W1, b1, MT1,
-                          W2, b2, MT2, W3, b3, Y, stream);
+  return pddp_bnn_mlp_jvp_rows_f32(R, P, group, group, in_dim, H, out_dim, X, W1,
+                                   b1, MT1, W2, b2, MT2, W3, b3, Y, nullptr,
+                                   stream);
 }
 
 int pddp_bnn_mlp_jvp_live_f32(int R, int P, int group, int live, int in_dim,
@@ -1113,8 +1068,9 @@ int pddp_bnn_mlp_jvp_live_f32(int R, int P, int group, int live, int in_dim,
                               const float* W2, const float* b2, const float* MT2,
                               const float* W3, const float* b3, float* Y,
                               void* stream) {
-  return bnn_mlp_jvp_impl(R, P, group, live, in_dim, H, out_dim, X, W1, b1, MT1,
-                          W2, b2, MT2, W3, b3, Y, stream);
+  return pddp_bnn_mlp_jvp_rows_f32(R, P, group, live, in_dim, H, out_dim, X, W1,
+                                   b1, MT1, W2, b2, MT2, W3, b3, Y, nullptr,
+                                   stream);
 }
 
 int pddp_bnn_mlp_jvp_rows_f32(int R, int P, int group, int live, int in_dim,
@@ -1123,8 +1079,11 @@ int pddp_bnn_mlp_jvp_rows_f32(int R, int P, int group, int live, int in_dim,
                               const float* W2, const float* b2, const float* MT2,
                               const float* W3, const float* b3, float* Y,
                               const int32_t* live_rows, void* stream) {
-  return bnn_mlp_jvp_impl(R, P, group, live, in_dim, H, out_dim, X, W1, b1, MT1,
-                          W2, b2, MT2, W3, b3, Y, stream, live_rows);
+  // (group 0 is the plain network's word: not a group)
+  if (group == 0) return PDDP_E_BADARG;
+  return pddp::bnn_mlp_impl({R, P, in_dim, H, out_dim, X, W1, b1, MT1, W2, b2,
+                             MT2, W3, b3, Y, live_rows},
+                            group, live, stream);
 }
 
 }  // extern "C"

@@ -58,10 +58,9 @@
 // through the ReLUs linearised at the group's first row.  Groups are whole
 // inside a 16-row tile; rows k >= live of a group are neither read nor
 // written.
-#include <atomic>
 #include <type_traits>
 
-#include "pddp_common.hpp"
+#include "bnn_mlp_check.hpp"
 
 namespace pddp {
 
@@ -505,33 +504,13 @@ __global__ __launch_bounds__(kMlp64Threads) void bnn_mlp_f64_kernel(BnnMlpArgs64
 
 template <int H, int G, bool SMALL>
 static int launch_bnn_mlp_f64_s(const BnnMlpArgs64& a, hipStream_t st) {
-  constexpr int kMaxDev = 16;
-  // (first use from several host threads: both caches are idempotent - every
-  // writer stores the same value - and atomic, so a racing reader sees either
-  // "unset" and repeats the query / the opt-in, or the value)
-  static std::atomic<int> cus_of[kMaxDev] = {};
-  static std::atomic<bool> attr_set[kMaxDev] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev)
-    return PDDP_E_UNSUPPORTED;
-  if (cus_of[dev] == 0) {
-    hipDeviceProp_t prop;
-    cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess
-                      ? prop.multiProcessorCount
-                      : 256;
-  }
-  const int cus = cus_of[dev];
-  const int ntiles = (a.R + kMlp64Tile - 1) / kMlp64Tile;
-  const int grid = ntiles < cus ? ntiles : cus;  // persistent: one per CU
   constexpr size_t lds = sizeof(double) * Mlp64Shape<H>::lds_doubles;
   static_assert(lds <= 160 * 1024, "a workgroup's LDS");
-  if (!attr_set[dev]) {  // more than 64 KB of dynamic LDS needs the opt-in
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)bnn_mlp_f64_kernel<H, G, SMALL>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set[dev] = true;
-  }
+  static PersistentKernel state;  // (of this kernel)
+  int grid;
+  if (int rc = state.prepare((const void*)bnn_mlp_f64_kernel<H, G, SMALL>, lds,
+                             (a.R + kMlp64Tile - 1) / kMlp64Tile, grid))
+    return rc;
   PDDP_LAUNCH((bnn_mlp_f64_kernel<H, G, SMALL>), dim3(grid), dim3(kMlp64Threads), lds,
               st, a);
   return launch_status();
@@ -559,19 +538,9 @@ static int bnn_mlp_f64_impl(int R, int P, int group, int live, int in_dim, int H
                             const double* b2, const double* MT2, const double* W3,
                             const double* b3, double* Y, const int32_t* live_rows,
                             void* stream) {
-  if (R <= 0 || P <= 0 || in_dim <= 0 || H <= 0 || out_dim <= 0 || !X || !W1 ||
-      !b1 || !MT1 || !W2 || !b2 || !MT2 || !W3 || !b3 || !Y)
-    return PDDP_E_BADARG;
-  if (group != 0 &&
-      ((group != 8 && group != 16 && group != 32) || R % group != 0 || live < 1 ||
-       live > group))
-    return PDDP_E_BADARG;
-  if (in_dim >= kMlp64W1Max || out_dim > kMlp64MaxOut || group == 32)
-    return PDDP_E_UNSUPPORTED;
-  // (the masks are read 32 bytes at a time)
-  if ((((uintptr_t)MT1 | (uintptr_t)MT2) & 31) != 0) return PDDP_E_BADARG;
   const BnnMlpArgs64 a{R, P, in_dim, H, out_dim, live, X, W1, b1, MT1,
                        W2, b2, MT2, W3, b3, Y, live_rows};
+  if (int rc = bnn_mlp_check(a, group, live, kMlp64W1Max, kMlp64MaxOut)) return rc;
   hipStream_t st = (hipStream_t)stream;
   switch (group) {
     case 0: return launch_bnn_mlp_f64_h<0>(a, st);

@@ -1391,12 +1391,21 @@ PDDP_DEV void gp_step_body(const Args<T>& A, const Roll<T>& RL = Roll<T>(), cons
   PDDP_GP_MARK(6);
 }
 
-// The chunked form's launchers (gp_step_chunked.hip).  `rows_per_launch` > 0
-// overrides the cost model's slice (pddp_gp_step_force_rows_per_launch)
+// ---- host side --------------------------------------------------------------------
+// The built (state_size, d) pairs - pendulum, cartpole, double cartpole - for
+// the entry points, the queries (gp_step.hip: for_shape) and the chunked
+// kernels' instantiations
+#define PDDP_GP_SHAPES(X) X(2, 4) X(4, 6) X(6, 9)
+
+// The chunked form's kernels (gp_step_chunked.hip); the launcher is gp_step.hip's
+template <typename T>
+using ChunkedStepKernel = void (*)(Args<T>, Chunk);
+template <typename T>
+using ChunkedRollKernel = void (*)(Args<T>, Roll<T>, Chunk);
 template <typename T, int E, int D>
-int launch_chunked(const Args<T>& a, bool jac, int C, int rows_per_launch, hipStream_t st);
+ChunkedStepKernel<T> chunked_step_kernel(bool jac);
 template <typename T, int E, int D>
-int launch_roll_chunked(Args<T> a, Roll<T> r, int C, int rows_per_launch, hipStream_t st);
+ChunkedRollKernel<T> chunked_roll_kernel();
 
 }  // namespace gp
 }  // namespace pddp

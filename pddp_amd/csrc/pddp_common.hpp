@@ -5,6 +5,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "../../include/pddp_hip.h"
@@ -99,6 +100,14 @@ inline int launch_status() {
   return e == hipSuccess ? 0 : (int)e;
 }
 
+// More than 64 KB of dynamic LDS needs the opt-in: a function attribute, per
+// device
+inline int allow_dyn_lds(const void* kernel, size_t lds_bytes) {
+  const hipError_t e = hipFuncSetAttribute(
+      kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 // A launch with `lds_bytes` of dynamic LDS, which may exceed the 64 KB a
 // kernel gets by default: allow it (on every call), then launch through
 // PDDP_LAUNCH.  The arguments convert to the kernel's parameter types here.
@@ -106,12 +115,41 @@ template <typename... P>
 int launch_dyn_lds(void (*kernel)(P...), dim3 grid, dim3 block,
                    size_t lds_bytes, hipStream_t st,
                    std::common_type_t<P>... args) {
-  const hipError_t e = hipFuncSetAttribute(
-      (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-      (int)lds_bytes);
-  if (e != hipSuccess) return (int)e;
+  if (int rc = allow_dyn_lds((const void*)kernel, lds_bytes)) return rc;
   PDDP_LAUNCH(kernel, grid, block, lds_bytes, st, args...);
   return launch_status();
 }
+
+// The per-device state of a persistent kernel with such an opt-in (a process
+// may drive several GPUs): the CU count, queried once per device -
+// hipGetDeviceProperties costs ms - and "this kernel has its opt-in on this
+// device", one PersistentKernel per kernel.  First use from several host
+// threads: both caches are idempotent - every writer stores the same value -
+// and atomic, so a racing reader sees either "unset" and repeats the query /
+// the opt-in, or the value.
+constexpr int kMaxDev = 16;
+struct PersistentKernel {
+  std::atomic<bool> opted[kMaxDev] = {};
+  // grid: one workgroup per CU of the current device, no more than `tiles`
+  int prepare(const void* kernel, size_t lds_bytes, int tiles, int& grid) {
+    static std::atomic<int> cus_of[kMaxDev] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev)
+      return PDDP_E_UNSUPPORTED;
+    if (cus_of[dev] == 0) {
+      hipDeviceProp_t prop;
+      cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess
+                        ? prop.multiProcessorCount
+                        : 256;
+    }
+    const int cus = cus_of[dev];
+    grid = tiles < cus ? tiles : cus;
+    if (!opted[dev]) {
+      if (int rc = allow_dyn_lds(kernel, lds_bytes)) return rc;
+      opted[dev] = true;
+    }
+    return 0;
+  }
+};
 
 }  // namespace pddp
