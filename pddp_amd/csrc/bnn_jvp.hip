@@ -19,7 +19,8 @@
 //   jvp_moments :  network output rows -> out_p (the particle cloud carried to
 //                  step t + 1), M, C, U' = chol(C), and per direction k
 //                  dM_k = mean_p dout_pk,
-//                  dC_k = (S_k + S_k^T) / (P - 1),  S_k = sum_p dout_pk (out_p - M)^T,
+//                  dC_k = (S_k + S_k^T) / (P - 1),
+//                  S_k = sum_p (dout_pk - dM_k) (out_p - M)^T,
 //                  dU'_k = Phi(U'^-T dC_k U'^-1) U'   (Phi: upper triangle, half
 //                  the diagonal - the differential of the Cholesky factor),
 //                  column k of (F_z | F_u) = (dM_k | triu(dU'_k)).
@@ -211,9 +212,12 @@ __global__ __launch_bounds__(64) void bnn_jvp_moments_kernel(BnnJvpV<T> s) {
   for (int d = 0; d < D; ++d) M[d] = across_slices(M[d]) / (T)P;
 
   // ---- covariance, and this lane's tangent sums
-  T C[kJvpMaxD][kJvpMaxD], S[kJvpMaxD][kJvpMaxD], dM[kJvpMaxD];
+  // (SD = sum_p (out_p - M): zero but for the rounding of M, which S_k sees
+  // times the whole tangent - below)
+  T C[kJvpMaxD][kJvpMaxD], S[kJvpMaxD][kJvpMaxD], dM[kJvpMaxD], SD[kJvpMaxD];
   for (int i = 0; i < D; ++i) {
     dM[i] = 0.f;
+    SD[i] = 0.f;
     for (int j = 0; j < D; ++j) { C[i][j] = 0.f; S[i][j] = 0.f; }
   }
   for (int p = slice; p < P; p += NS) {
@@ -235,17 +239,24 @@ __global__ __launch_bounds__(64) void bnn_jvp_moments_kernel(BnnJvpV<T> s) {
     }
     for (int i = 0; i < D; ++i) {
       dM[i] += dout[i];
+      SD[i] += dev[i];
       for (int j = 0; j < D; ++j) {
         C[i][j] += dev[i] * dev[j];
         S[i][j] += dout[i] * dev[j];
       }
     }
   }
+  for (int i = 0; i < D; ++i) SD[i] = across_slices(SD[i]);
   for (int i = 0; i < D; ++i) {
     dM[i] = across_slices(dM[i]) / (T)P;
     for (int j = 0; j < D; ++j) {
       C[i][j] = across_slices(C[i][j]) / (T)(P - 1);
-      S[i][j] = across_slices(S[i][j]);
+      // S_k = sum_p (dout_pk - dM_k) (out_p - M)^T, as differentiating the
+      // centred particles gives it: the same sum when SD is zero; with the
+      // rounding of M left in SD, `sum_p dout_pk dev_p` alone carries dout_k SD
+      // - an error of eps |M| / |dev| in F_z for a mean direction (dout ~ 1),
+      // 3e-6 in f32 for a cloud 1.5 from the origin and 0.04 wide
+      S[i][j] = across_slices(S[i][j]) - dM[i] * SD[j];
     }
   }
   if (slice != 0) return;  // (every slice holds the totals; one writes)
@@ -315,8 +326,10 @@ __global__ __launch_bounds__(64) void bnn_jvp_moments_kernel(BnnJvpV<T> s) {
   } else {
     // encode()'s fall-back: the diagonal of standard deviations
     // (modules.py:380-386 -> encoding.py:99-141)
+    // (above the diagonal Uc still holds what the last failed attempt left)
     for (int i = 0; i < D; ++i) {
       const T sdev = sqrt_(C[i][i]);
+      for (int j = i + 1; j < D; ++j) Uc[i][j] = 0.f;
       Uc[i][i] = sdev;
       dU[i][i] = (S[i][i] + S[i][i]) / (T)(P - 1) / (2.f * sdev);
     }
@@ -370,12 +383,14 @@ namespace pddp {
 template <typename T>
 static int bnn_jvp_check(const BnnJvpV<T>* s) {
   if (s == nullptr) return PDDP_E_BADARG;
-  if (s->B <= 0 || s->P <= 1 || s->N <= 0 || s->t < 0 || s->t >= s->N ||
+  if (s->B <= 0 || s->P <= 1 || s->N <= 0 || s->t < 0 || s->t > s->N ||
       !s->Z || !s->U || !s->X_mean || !s->X_std_inv || !s->dX_mean ||
       !s->dX_std || !s->Xp || !s->eps || !s->F)
     return PDDP_E_BADARG;
   const int n = s->D + s->D * (s->D + 1) / 2;
-  if (s->D < 1 || s->D > 6 || s->m < 1 || n + s->m > 31 ||
+  // (t = N is a step of the trajectory - the moment step takes it - but the
+  // terminal state has no Jacobian)
+  if (s->t == s->N || s->D < 1 || s->D > 6 || s->m < 1 || n + s->m > 31 ||
       s->D + s->m > kNetRows - 1 || s->n_ang < 0 || s->n_ang > 2 ||
       s->n_non < 0 || s->n_non + s->n_ang != s->D ||
       s->in_dim != s->n_non + 2 * s->n_ang + s->m || s->out_dim < s->D ||
