@@ -149,8 +149,8 @@ PDDP_DEV f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
   return __builtin_elementwise_fma(a, b, c);
 }
 // sincos_poly with the sine's and the cosine's polynomials side by side:
-// (s, c)
-PDDP_DEV f32x2 sincos_poly_pk(float r, int q) {
+// (s, c) before the quadrant is applied
+PDDP_DEV f32x2 sincos_poly_pk(float r) {
   // (z, r): z = r r in the low half, which the splats read without a move
   f32x2 zr = f32x2{r * r, r};
   const f32x2 p = zr.yx * zr.xx;  // (r z, z z)
@@ -158,12 +158,29 @@ PDDP_DEV f32x2 sincos_poly_pk(float r, int q) {
                    f32x2{8.3321608736e-3f, -1.388731625493765e-3f});
   w = pk_fma(zr.xx, w, f32x2{-1.6666654611e-1f, 4.166664568298827e-2f});
   zr.x = __builtin_fmaf(zr.x, -0.5f, 1.0f);  // (1 - z / 2, r)
-  const f32x2 sc = pk_fma(p, w, zr.yx);
-  const bool swap = (q & 1) != 0;
-  const unsigned ss = ((unsigned)q & 2u) << 30;
-  const unsigned cs = (((unsigned)q + 1u) & 2u) << 30;
-  return f32x2{__uint_as_float(__float_as_uint(swap ? sc.y : sc.x) ^ ss),
-               __uint_as_float(__float_as_uint(swap ? sc.x : sc.y) ^ cs)};
+  return pk_fma(p, w, zr.yx);
+}
+// The quadrant q of (s, c): odd ones swap the two, q & 2 negates the sine,
+// (q + 1) & 2 the cosine.  Integer logic issued by hand: a mask of q's low bit
+// and two bitwise selects - from C++ the compiler makes a compare and two
+// v_cndmask of it, one instruction more and a trip through VCC on the state's
+// chain (0.95 us per round of the round kernel).
+// ONE statement: the compiler keeps an asm statement's result one instruction
+// away from its reader.
+// (v_bitop3 0x6c: src1 ^ (src0 & src2); 2.0 is the word 1 << 30)
+PDDP_DEV f32x2 sincos_quadrant_pk(f32x2 sc, int q) {
+  float s, c;
+  int odd, sh;
+  asm("v_bfe_i32 %[odd], %[q], 0, 1\n\t"
+      "v_lshlrev_b32 %[sh], 30, %[q]\n\t"
+      "v_bfi_b32 %[s], %[odd], %[y], %[x]\n\t"
+      "v_bfi_b32 %[c], %[odd], %[x], %[y]\n\t"
+      "v_bitop3_b32 %[s], %[sh], %[s], %[sign] bitop3:0x6c\n\t"
+      "v_add_u32 %[sh], 2.0, %[sh]\n\t"
+      "v_bitop3_b32 %[c], %[sh], %[c], %[sign] bitop3:0x6c"
+      : [odd] "=&v"(odd), [sh] "=&v"(sh), [s] "=&v"(s), [c] "=&v"(c)
+      : [q] "v"(q), [x] "v"(sc.x), [y] "v"(sc.y), [sign] "s"(0x80000000u));
+  return f32x2{s, c};
 }
 // sincos_ on the paired polynomials: the same reduction, the same fall-back
 PDDP_DEV f32x2 sincos_pk(float x) {
@@ -171,9 +188,16 @@ PDDP_DEV f32x2 sincos_pk(float x) {
   const double kd = __builtin_rint(xd * 0.63661977236758138243);  // 2 / pi
   double rd = __builtin_fma(kd, -1.57079632679489655800e+00, xd);
   rd = __builtin_fma(kd, -6.12323399573676603587e-17, rd);
-  const f32x2 sc = sincos_poly_pk((float)rd, (int)kd);
-  float s = sc.x, c = sc.y;
+  const f32x2 p = sincos_poly_pk((float)rd);
+  // (the test for the fall-back is issued between the polynomials' last
+  // multiply-add and the statement that reads its result: a packed result
+  // wants one instruction before its reader too, and left to the scheduler
+  // that instruction was an s_nop)
+  __builtin_amdgcn_sched_barrier(0);
   const bool big = fabsf(x) >= kTrigCoreLimit;
+  __builtin_amdgcn_sched_barrier(0);
+  const f32x2 sc = sincos_quadrant_pk(p, (int)kd);
+  float s = sc.x, c = sc.y;
   if (__builtin_expect(__any(big), 0)) {
     float sl, cl;
     sincosf(x, &sl, &cl);

@@ -67,6 +67,18 @@ PDDP_DEV float bsel(int mask, float a, float b) {  // mask ? a : b, bitwise
   asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "v"(b));
   return r;
 }
+// bsel(splat(w), a, b) as ONE statement: between two statements the compiler
+// keeps a result one instruction away from its reader, for want of which it
+// issues an s_nop - a caution about asm results, no rule of the hardware for
+// two 32-bit VALU operations
+PDDP_DEV float bsel_sign(int w, float a, float b) {
+  float r;
+  asm("v_ashrrev_i32 %0, 31, %1\n\t"
+      "v_bfi_b32 %0, %0, %2, %3"
+      : "=&v"(r)
+      : "v"(w), "v"(a), "v"(b));
+  return r;
+}
 
 // What a sweep needs to evaluate its records itself: the nominal trajectory
 // instead of `a.rec`, and where the stage costs and their sum go.
@@ -89,6 +101,7 @@ using n4::group_sum;
 using n4::kGain;
 using n4::mul_nc;
 using n4d::bsel;
+using n4d::bsel_sign;
 using n4d::f32x4;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x3 __attribute__((ext_vector_type(3)));
@@ -210,6 +223,12 @@ PDDP_DEV f32x2 quz_products(f32x2 a, float b) {
       : "v"(a), "v"(lo_word(b)));
   return r;
 }
+// a b, rounded on its own (no empty asm statement behind it: for operands of
+// a multiply-add that is written out)
+PDDP_DEV float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
 struct QpLean1 {
   float x, inv;
   int free_w;  // flag in the sign bit
@@ -257,7 +276,7 @@ struct QpLean1 {
     // ---- iteration 1: exit tests
     const int conv = sgn(fma_(-1e-8f, __builtin_fabsf(f0), -num));
     const int ncl1 = (sgn(d1.y) & ~sgn(d1.x) & ~sgn(g1)) | (~sgn(d1.y) & sgn(g1));
-    x = bsel(splat(done0), xs, x1);
+    x = bsel_sign(done0, xs, x1);
     // free = (done0 & !ncl0) | (!done0 & (conv | !ncl1)), done0 = ncl0 | small0
     free_w = ~ncl0 & (small0 | conv | ~ncl1);
   }
@@ -1038,7 +1057,16 @@ PDDP_DEV bool elem_sweep_body(const RiccatiArgs<T>& a, const GenArgs<T>& gen,
     // ---- value update (ilqr.py:664-672 with K = -s Quz):
     // V' = sym(Qzz) + c Quz Quz^T,  V_z' = Qz + w Quz
     // (every term symmetric in (i, j) bit for bit: a + b == b + a)
-    V = fma_(T(0.5), n4::opaque(q.Qzz + QzzT), mul_nc(c, QQ));
+    if constexpr (F32) {
+      // (the sum and the product without the empty asm statements: the
+      // multiply-add below is written out, there is nothing for the compiler
+      // to contract them into, and it keeps an asm statement's result one
+      // instruction away from its reader - for these two, which V's
+      // multiply-add reads at once, with an s_nop: DESIGN.md 3.1h, round 11)
+      V = fma_(T(0.5), q.Qzz + QzzT, mul_rounded(c, QQ));
+    } else {
+      V = fma_(T(0.5), n4::opaque(q.Qzz + QzzT), mul_nc(c, QQ));
+    }
     vc = fma_(wv, Quzc, q.Qzc);
   };
 
