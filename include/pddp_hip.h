@@ -684,6 +684,53 @@ int pddp_line_search_weighted_f64(const pddp_problem* problem,
                                   const int32_t* bwd_status, double* Zc,
                                   double* Uc, double* Jc, void* stream);
 
+/* ---- a reference tracked under per-trajectory cost weights
+ * (csrc/track_weights.hip): pddp_derivs_track_* / pddp_line_search_track_*
+ * with the diagonals of Q, Q_term and R of trajectory b REPLACED by row b of
+ * `weights`.  `ref`, ref_len, ref_t0 in the reference's layout and law above
+ * (row min(ref_t0 + i, ref_len - 1), the last row held), `weights`
+ * [B][PDDP_WEIGHT_ROW] in the weights' layout above.  table
+ * [B][PDDP_BATCH_ROW], nullable: the model parameters of trajectory b are row
+ * b's (its goal fields are not read), else `problem`'s.  Every other argument
+ * and every result as the _track_ entry points.  The hand-over between two MPC
+ * control steps and the closed-loop rollouts report under the shared matrices:
+ * pddp_mpc_advance_track_* / pddp_mpc_advance_noisy_* / pddp_closed_loop_track_*
+ * serve unchanged.
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY.
+ * PDDP_E_BADARG: weights == NULL, ref == NULL, ref_len < 1, ref_t0 < 0 and
+ * everything the siblings answer it for (B * A > 0x7fffffff included);
+ * PDDP_E_UNSUPPORTED: any other encoding or model; both before any HIP
+ * call. */
+int pddp_derivs_track_weighted_f32(const pddp_problem* problem,
+                                   const float* table, const float* ref,
+                                   int ref_len, int ref_t0,
+                                   const float* weights, int B, int N,
+                                   const float* Z, const float* U,
+                                   const float* u_min, const float* u_max,
+                                   const uint8_t* mask, float* rec, float* L,
+                                   float* J, int32_t* state, void* stream);
+int pddp_derivs_track_weighted_f64(const pddp_problem* problem,
+                                   const double* table, const double* ref,
+                                   int ref_len, int ref_t0,
+                                   const double* weights, int B, int N,
+                                   const double* Z, const double* U,
+                                   const double* u_min, const double* u_max,
+                                   const uint8_t* mask, double* rec, double* L,
+                                   double* J, int32_t* state, void* stream);
+int pddp_line_search_track_weighted_f32(
+    const pddp_problem* problem, const float* table, const float* ref,
+    int ref_len, int ref_t0, const float* weights, int B, int N, int A,
+    const float* Z, const float* U, const float* gains, const float* alphas,
+    const float* u_min, const float* u_max, const uint8_t* active,
+    const int32_t* bwd_status, float* Zc, float* Uc, float* Jc, void* stream);
+int pddp_line_search_track_weighted_f64(
+    const pddp_problem* problem, const double* table, const double* ref,
+    int ref_len, int ref_t0, const double* weights, int B, int N, int A,
+    const double* Z, const double* U, const double* gains,
+    const double* alphas, const double* u_min, const double* u_max,
+    const uint8_t* active, const int32_t* bwd_status, double* Zc, double* Uc,
+    double* Jc, void* stream);
+
 /* ---- pddp_closed_loop_* / pddp_closed_loop_noisy_* ALONG A REFERENCE
  * (csrc/closed_loop.hip): the same S rollouts per trajectory, costed
  * under a goal per time step.  Rollout (b, s) takes

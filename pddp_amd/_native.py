@@ -103,6 +103,10 @@ _SIGS = {
                          _P, _P],
     "pddp_derivs_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] * 10,
     "pddp_line_search_weighted": [_P, _P, _P] + [c_int] * 3 + [_P] * 12,
+    "pddp_derivs_track_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] +
+                                  [c_int] * 2 + [_P] * 10,
+    "pddp_line_search_track_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] +
+                                       [c_int] * 3 + [_P] * 12,
     "pddp_search_accept": [_P, c_int, c_int, c_int] + [_P] * 11 +
                           [c_double, c_double, c_int] +
                           [_P] * 11,
@@ -168,6 +172,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_mpc_advance_track",
           "pddp_mpc_advance_noisy", "pddp_mpc_observe",
           "pddp_derivs_weighted", "pddp_line_search_weighted",
+          "pddp_derivs_track_weighted", "pddp_line_search_track_weighted",
           "pddp_pack_best", "pddp_sweep_nominal", "pddp_gp_step",
           "pddp_gp_step_masked",
           "pddp_gp_rollout")

@@ -317,21 +317,28 @@ class iLQRController(Controller):
         head, tail = X[..., :-1, :, :], X[..., 1:, :, :]  # (the time axis)
         return (head, U, tail - head), J
 
-    def set_reference(self, x_ref, u_ref=None, start=0):
+    def set_reference(self, x_ref, u_ref=None, start=0, keep_weights=False):
         """A goal per time step for the solver of the last fit / step:
         `ILQRSolver.set_reference` (its arguments; with a fit without batch
-        axis, [1][L][.]).  `mpc_closed_loop` then follows the reference."""
-        self._fitted_solver().set_reference(x_ref, u_ref, start)
+        axis, [1][L][.]).  `mpc_closed_loop` then follows the reference.
+        `keep_weights=True` (passed on only when set): the reference is
+        tracked under the weights of `set_batch_weights`."""
+        kw = dict(keep_weights=True) if keep_weights else {}
+        self._fitted_solver().set_reference(x_ref, u_ref, start, **kw)
 
     def clear_reference(self):
         """`ILQRSolver.clear_reference` of the solver of the last fit / step."""
         self._fitted_solver().clear_reference()
 
-    def set_batch_weights(self, q=None, q_term=None, r=None, check=True):
+    def set_batch_weights(self, q=None, q_term=None, r=None, check=True,
+                          keep_reference=False):
         """Per-trajectory diagonals of Q, Q_term, R for the solver of the last
         fit / step: `ILQRSolver.set_batch_weights` (its arguments; with a fit
-        without batch axis, [1][.])."""
-        self._fitted_solver().set_batch_weights(q, q_term, r, check)
+        without batch axis, [1][.]).  `keep_reference=True` (passed on only
+        when set): a reference of `set_reference` stays and is tracked under
+        the weights."""
+        kw = dict(keep_reference=True) if keep_reference else {}
+        self._fitted_solver().set_batch_weights(q, q_term, r, check, **kw)
 
     def clear_batch_weights(self):
         """`ILQRSolver.clear_batch_weights` of the solver of the last fit /

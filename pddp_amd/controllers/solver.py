@@ -53,7 +53,14 @@ pddp_*_track_* entry points, every round is records+separate, and
 `set_batch_weights()` gives every trajectory its own diagonals of Q, Q_term
 and R (`batch_weights`): derivs and line search are then the pddp_*_weighted_*
 entry points, with the table's address or NULL, and every round is
-records+separate.  Weights and a reference refuse each other.
+records+separate.
+
+Weights and a reference are held at once where the second setter is told to
+keep the first (`set_reference(keep_weights=True)`,
+`set_batch_weights(keep_reference=True)`): derivs and line search are then the
+pddp_*_track_weighted_* entry points (csrc/track_weights.hip), with the table's
+address or NULL, the reference window and the weights; every round is
+records+separate.  Without the keyword the second setter refuses.
 """
 import ctypes
 import functools
@@ -398,7 +405,7 @@ class ILQRSolver(object):
         self._problem_changed()
 
     @_on_device
-    def set_reference(self, x_ref, u_ref=None, start=0):
+    def set_reference(self, x_ref, u_ref=None, start=0, keep_weights=False):
         """A goal per time step (reference tracking): `x_ref` [B][L][na] in
         augmented coordinates, `u_ref` [B][L][m] (default: in every row the
         table's `u_goal` if a table is set, else the shared problem's).
@@ -416,13 +423,20 @@ class ILQRSolver(object):
         nominal, the one-launch round and the fused search take one goal per
         trajectory and refuse; so does `closed_loop()` unless it is told to
         follow the reference (`track=True`).  The nominal rollout reads no
-        goal: the current nominal stays as it is."""
+        goal: the current nominal stays as it is.
+
+        While per-trajectory cost weights are set (`set_batch_weights`) the
+        call is refused unless `keep_weights=True`: the reference is then
+        tracked under every trajectory's own diagonals - records and line
+        search are the pddp_*_track_weighted_* entry points, everything else
+        as above.  (`mpc_closed_loop()` and `closed_loop(track=True)` still
+        REPORT under the shared Q, Q_term, R.)"""
         self._need_sample_problem("set_reference")
-        if self.batch_weights is not None:
+        if self.batch_weights is not None and not keep_weights:
             raise _native.NativeError(
                 "set_reference: per-trajectory cost weights are set "
-                "(set_batch_weights); weights together with a reference are "
-                "not supported - clear_batch_weights() first")
+                "(set_batch_weights); keep_weights=True tracks the reference "
+                "under them, clear_batch_weights() drops them first")
         N_ = _native
         B, na, m = self.B, self.problem.aug_size, self.m
         opts = dict(dtype=self.dtype, device=self.device)
@@ -479,7 +493,8 @@ class ILQRSolver(object):
         self._restore_plan()
 
     @_on_device
-    def set_batch_weights(self, q=None, q_term=None, r=None, check=True):
+    def set_batch_weights(self, q=None, q_term=None, r=None, check=True,
+                          keep_reference=False):
         """Per-trajectory cost weights: `q`, `q_term` [B][na] (augmented
         coordinates) and `r` [B][m] REPLACE the diagonals of Q, Q_term and R
         for trajectory b; a block not given keeps the shared diagonal.  The
@@ -494,8 +509,10 @@ class ILQRSolver(object):
         nominal rollout reads no cost: the current nominal stays as it is.
         `closed_loop()`, `closed_loop_draws()` and `mpc_closed_loop()` stay
         available; the costs they REPORT are under the shared problem's Q,
-        Q_term, R.  Weights and a reference (`set_reference`) refuse each
-        other.
+        Q_term, R.  While a reference is set (`set_reference`) the call is
+        refused unless `keep_reference=True`: the reference is then tracked
+        under the weights - records and line search are the
+        pddp_*_track_weighted_* entry points, the table's goals are not read.
 
         `check` (default): every trajectory's matrices are tested on the
         host, in float64, once - one copy of [B][20] numbers.  The symmetrised
@@ -507,11 +524,11 @@ class ILQRSolver(object):
         then answers with NOT_PD / MAX_REG states that look like a tuning
         result.)"""
         self._need_sample_problem("set_batch_weights")
-        if self.reference is not None:
+        if self.reference is not None and not keep_reference:
             raise _native.NativeError(
                 "set_batch_weights: a reference is set (set_reference); "
-                "weights together with a reference are not supported - "
-                "clear_reference() first")
+                "keep_reference=True tracks it under the weights, "
+                "clear_reference() drops it first")
         weights = self._write_fields(
             "set_batch_weights", self._shared_weights_row().repeat(self.B, 1),
             self._weight_blocks(q, q_term, r))
@@ -589,11 +606,16 @@ class ILQRSolver(object):
         `_batch` one, with the table, while a table is set; for a kernel that
         reads the `goals` (records, line search) the `_weighted` one, with the
         table's address or NULL and the weights, while weights are set, and
-        the `_track` one, likewise with `_ref_window()`, while a reference is
-        (the two exclude each other).  The addresses are looked up at the
-        call: a tensor may be replaced between two calls."""
+        the `_track` one, likewise with `_ref_window()`, while a reference is;
+        with both the `_track_weighted` one: the table's address or NULL, the
+        window, the weights.  The addresses are looked up at the call: a
+        tensor may be replaced between two calls."""
         p = _native.ptr
-        if goals and self.batch_weights is not None:
+        if goals and self.batch_weights is not None and \
+                self.reference is not None:
+            suffix, lead = "_track_weighted", (p(self.batch_table),) + \
+                self._ref_window() + (p(self.batch_weights),)
+        elif goals and self.batch_weights is not None:
             suffix, lead = "_weighted", (p(self.batch_table),
                                          p(self.batch_weights))
         elif goals and self.reference is not None:
@@ -993,7 +1015,9 @@ class ILQRSolver(object):
         With per-trajectory cost weights (`set_batch_weights`) the call is
         NOT refused and its kernels are unchanged: `J` and `stats` are under
         the shared problem's Q, Q_term, R and the plant row's goals, whatever
-        weights each policy was fitted under - the common yardstick."""
+        weights each policy was fitted under - the common yardstick (with
+        `track=True` while both are set: under the shared matrices along the
+        reference)."""
         if track:
             if self.reference is None:
                 raise _native.NativeError(
@@ -1169,7 +1193,10 @@ class ILQRSolver(object):
         inside the trial optimise under each trajectory's weights; the cost
         the trial reports (`J`) is under the shared problem's Q, Q_term, R
         and the plant row's goals - the common yardstick.  The advance kernel
-        is unchanged.
+        is unchanged.  With weights AND a reference the rounds run the
+        pddp_*_track_weighted_* kernels on the window at `ref_start + t`; the
+        advance is the tracked one, unchanged: `J` is under the shared
+        matrices along the reference.
 
         `process_std`, `obs_std` (each a scalar or [n]; None: none of it):
         noise drawn inside the advance (pddp_mpc_advance_noisy_*,

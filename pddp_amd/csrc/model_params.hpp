@@ -3,7 +3,7 @@
 // numbers on the Python side, tests/test_mpc_closed_loop.py compares the two),
 // and the writers of a per-trajectory row over the shared problem.  The one
 // copy of each: problem_kernels.hip, closed_loop.hip, mpc_advance.hip,
-// tracking.hip and weights.hip include this file.
+// tracking.hip, weights.hip, track_weights.hip include it.
 #pragma once
 
 #include "models.hpp"

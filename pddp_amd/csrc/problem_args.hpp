@@ -68,9 +68,10 @@ struct LineSearchArgs {
 };
 
 // Host side of every entry point that takes one of the blocks above
-// (problem_kernels.hip, tracking.hip, weights.hip): the argument test, the grid
-// of the per-candidate line search, and the carrier of a block together with
-// a form's per-trajectory data through PDDP_DISPATCH_MODEL.
+// (problem_kernels.hip, tracking.hip, weights.hip, track_weights.hip): the
+// argument test, the grid of the per-candidate line search, and the carrier
+// of a block together with a form's per-trajectory data through
+// PDDP_DISPATCH_MODEL.
 template <typename T>
 inline bool args_ok(const DerivArgs<T>& a) {
   return !(a.B <= 0 || a.N <= 0 || !a.Z || !a.U || !a.rec || !a.L || !a.J);

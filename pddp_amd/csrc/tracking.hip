@@ -21,7 +21,8 @@
 // loops are the included texts of problem_kernels.hip - derivs_body.inc,
 // line_search_body.inc - with the goals of `P` taken from a reference row
 // (PDDP_COPY, ref_args.hpp) at the texts' hook points, where those kernels read
-// one problem; the row writer is model_params.hpp's.
+// one problem: track_goal_hooks.inc, which track_weights.hip includes as
+// well; the row writer is model_params.hpp's.
 #include <type_traits>
 #include "models.hpp"
 #include "problem_args.hpp"
@@ -32,13 +33,13 @@ namespace pddp {
 
 // For the two kernels below: `P` is the shared problem with the model
 // parameters of row b of the table, where one is given, written over it (the
-// goals come step by step), and the texts' PDDP_GOALS(point) is the kernel's
-// PDDP_GOALS_<point>.
+// goals come step by step), and the texts' PDDP_GOALS(point) is
+// track_goal_hooks.inc's PDDP_GOALS_<point>.
 #define PDDP_PROBLEM_OF_B                                                      \
   ProblemT<T> P = shared;                                                      \
   if (goals.table != nullptr)                                                  \
     write_params<T, MODEL>(P, goals.table + (size_t)b * PDDP_BATCH_ROW);
-#define PDDP_GOALS(point) PDDP_GOALS_##point
+#include "track_goal_hooks.inc"
 
 // --------------------------------------------------------------------------
 // derivative records: one workgroup per trajectory, one lane per time step,
@@ -52,13 +53,7 @@ template <typename T, int MODEL>
 __global__ __launch_bounds__(kDerivThreads) void track_derivs_kernel(
     ProblemT<T> shared, DerivArgs<T> a, RefArgs<T> goals) {
 #define PDDP_SPLIT_TERMINAL 1
-#define PDDP_GOALS_TAKE_X                                                      \
-  const T* row = ref_row(goals, b, t);                                         \
-  PDDP_COPY(D::na, P.goal, row + PDDP_REF_X_GOAL)
-#define PDDP_GOALS_TAKE_U PDDP_COPY(m, P.ugoal, row + PDDP_REF_U_GOAL)
 #include "derivs_body.inc"
-#undef PDDP_GOALS_TAKE_U
-#undef PDDP_GOALS_TAKE_X
 #undef PDDP_SPLIT_TERMINAL
 }
 
@@ -72,25 +67,15 @@ __global__ __launch_bounds__(kDerivThreads) void track_derivs_kernel(
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kWave) void track_line_search_kernel(
     ProblemT<T> shared, LineSearchArgs<T> a, RefArgs<T> goals) {
-#define PDDP_GOALS_TAKE_FIRST                                                  \
-  const T* row0 = ref_row(goals, b, 0);                                        \
-  PDDP_COPY(D::na, P.goal, row0 + PDDP_REF_X_GOAL)                             \
-  PDDP_COPY(m, P.ugoal, row0 + PDDP_REF_U_GOAL)
-#define PDDP_GOALS_NEXT_ROW const T* row = ref_row(goals, b, t + 1);
-#define PDDP_GOALS_PREFETCH_NEXT                                               \
-  T xg2[D::na], ug2[m];                                                        \
-  PDDP_COPY(D::na, xg2, row + PDDP_REF_X_GOAL)                                 \
-  PDDP_COPY(m, ug2, row + PDDP_REF_U_GOAL)
-#define PDDP_GOALS_TAKE_NEXT                                                   \
-  PDDP_COPY(m, P.ugoal, ug2)                                                   \
-  PDDP_COPY(D::na, P.goal, xg2)
 #include "line_search_body.inc"
+}
+
 #undef PDDP_GOALS_TAKE_NEXT
 #undef PDDP_GOALS_PREFETCH_NEXT
 #undef PDDP_GOALS_NEXT_ROW
 #undef PDDP_GOALS_TAKE_FIRST
-}
-
+#undef PDDP_GOALS_TAKE_U
+#undef PDDP_GOALS_TAKE_X
 #undef PDDP_GOALS
 #undef PDDP_PROBLEM_OF_B
 

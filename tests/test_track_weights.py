@@ -1,0 +1,828 @@
+"""A reference tracked under per-trajectory cost weights (ILQRSolver with
+set_reference AND set_batch_weights, the pddp_*_track_weighted_* entry points
+of csrc/track_weights.hip): a goal per time step and every trajectory's own
+diagonals of Q, Q_term and R in the derivative records, the line search, the
+rounds of an MPC trial and a captured round.
+
+Every expected value is composed from Oracle.cost / Oracle.forward /
+Oracle.control_law with the problem of THAT trajectory - `perturbed()` where a
+table is used, the three diagonals overwritten as tests/test_batch_weights.py
+draws them (`_weights`) - and its goals taken row by row (`under_row`), as
+tests/test_reference_tracking.py composes them.  Horizon index i reads row
+min(ref_t0 + i, ref_len - 1).
+
+Weights and references move records and costs by parts in ten, orders of
+magnitude above the bars - the project's own, `record_tol`: 1e-10 in f64, 2e-4
+in f32.  A kernel that ignores one of the two, reads a neighbour's row, indexes
+one table with the other's stride or misses the clamp fails the comparisons."""
+import ctypes
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import oracle as orc
+from abi_util import assert_entry_points, cartpole_pointers
+from golden_util import DT, FWD_NAMES, np_dtype, rel_err
+from solver_util import (BOUND, CONTROLLER, fresh_ops, loop_solver,
+                         make_solver, MEAN0, mpc_advance, named_views,
+                         perturbed, PROBLEMS, record_tol, ref_row,
+                         reference_rows, same_bits, SENTINEL, set_ref,
+                         set_table, std_vec, TDT, trial_logs, under_row)
+
+gpu = pytest.mark.gpu
+KINDS = ("derivs", "line_search")
+NEW_SYMBOLS = ["pddp_%s_track_weighted_%s" % (k, t) for k in KINDS
+               for t in ("f32", "f64")]
+COST_NAMES = ("L", "L_z", "L_u", "L_zz", "L_uz", "L_uu")
+STATE = CONTROLLER + ("z0", "U", "Z")
+STD = 0.02
+
+
+# ---------------------------------------------------------------------------
+# the per-trajectory problems and the composed oracle
+# ---------------------------------------------------------------------------
+
+def _weights(problem, B, seed, ops=None):
+    """(q [B][na], q_term [B][na], r [B][m]) as float64 arrays of float32
+    values, and the oracle's problem of every trajectory: `ops` (default: the
+    shared problem B times) with the three diagonals overwritten.  q = shared
+    diagonal x U(1, 2) + U(0, 0.5), q_term and r = shared diagonal x U(0.5, 2);
+    the rendezvous' Q_term is Q with off-diagonal entries of -1 against
+    diagonals of 1 - scaled DOWN it is indefinite - and is drawn upward only,
+    as q."""
+    rng = np.random.RandomState(seed)
+    base = orc.make_problem(problem, DT[problem])
+    na, m = base.aug_size, base.action_size
+    dq = np.array([base.Q[i * 8 + i] for i in range(na)])
+    dqt = np.array([base.Q_term[i * 8 + i] for i in range(na)])
+    dr = np.array([base.R[i * 4 + i] for i in range(m)])
+    q = dq * rng.uniform(1.0, 2.0, (B, na)) + rng.uniform(0.0, 0.5, (B, na))
+    qt = dqt * rng.uniform(0.5, 2.0, (B, na))
+    Qt = np.array(base.Q_term).reshape(8, 8)[:na, :na]
+    if np.any(Qt - np.diag(np.diag(Qt))):
+        qt = dqt * rng.uniform(1.0, 2.0, (B, na)) + \
+            rng.uniform(0.0, 0.5, (B, na))
+    r = dr * rng.uniform(0.5, 2.0, (B, m))
+    q, qt, r = (a.astype(np.float32).astype(np.float64) for a in (q, qt, r))
+    if ops is None:
+        ops = fresh_ops(problem, B)
+    for b, op in enumerate(ops):
+        for i in range(na):
+            op.Q[i * 8 + i] = q[b, i]
+            op.Q_term[i * 8 + i] = qt[b, i]
+        for i in range(m):
+            op.R[i * 4 + i] = r[b, i]
+    return q, qt, r, ops
+
+
+def _set_weights(s, q, qt, r, **kw):
+    s.set_batch_weights(q=torch.from_numpy(q), q_term=torch.from_numpy(qt),
+                        r=torch.from_numpy(r), **kw)
+
+
+def _forward_tracked(o, op, z0, U, u_min, u_max, xr_b, ur_b, t0):
+    """Oracle.forward's dictionary with every cost entry taken step by step
+    under that step's reference row (Z, F_z, F_u read no goal)."""
+    f = o.forward(op, z0, U, u_min, u_max)
+    N, L = U.shape[0], xr_b.shape[0]
+    for t in range(N + 1):
+        under_row(op, xr_b, ur_b, ref_row(L, t0, t))
+        if t < N:
+            u = U[t] if u_min is None else np.clip(U[t], u_min, u_max)
+            c = o.cost(op, f["Z"][t], u)
+        else:
+            c = o.cost(op, f["Z"][t], None, terminal=True)
+        for nm, v in zip(COST_NAMES, c):
+            if v is not None:
+                f[nm][t] = v
+    return f
+
+
+def _cost_tracked(o, op, Zn, Un, xr_b, ur_b, t0):
+    """[A] trajectory costs of candidates Zn [N+1][A][n], Un [N][A][m]: the
+    sum of Oracle.cost under each step's row plus the terminal cost under
+    row N, accumulated in the run's dtype in t order."""
+    N, A, L = Un.shape[0], Un.shape[1], xr_b.shape[0]
+    J = np.zeros(A, Zn.dtype)
+    for t in range(N + 1):
+        under_row(op, xr_b, ur_b, ref_row(L, t0, t))
+        for a in range(A):
+            if t < N:
+                J[a] += o.cost(op, Zn[t, a], Un[t, a])[0]
+            else:
+                J[a] += o.cost(op, Zn[t, a], None, terminal=True)[0]
+    return J
+
+
+def _both(s, problem, B, L, t0, table, seeds):
+    """A table (where asked for), a reference read from row t0 on and weights
+    on `s`; returns (xr, ur, the oracle's problem of every trajectory)."""
+    ops = None
+    if table:
+        par, xg, ug, ops = perturbed(problem, B, seed=seeds[0])
+        set_table(s, par, xg, ug)
+    xr, ur = reference_rows(problem, B, L, seed=seeds[1])
+    set_ref(s, xr, ur, t0)
+    q, qt, r, ops = _weights(problem, B, seed=seeds[2], ops=ops)
+    _set_weights(s, q, qt, r, keep_reference=True)
+    assert s.reference is not None and s.batch_weights is not None
+    assert (s.batch_table is not None) == table
+    return xr, ur, ops
+
+
+def _unit_gains(s):
+    """The gains of one sweep at reg = 1 on the solver's records."""
+    s.backward(reg=torch.full((s.B,), 1.0, dtype=torch.float64, device="cuda"))
+    assert int(s.bwd_status.abs().sum()) == 0
+
+
+# ---------------------------------------------------------------------------
+# without a GPU
+# ---------------------------------------------------------------------------
+
+def test_track_weighted_entry_points_are_declared_exported_and_bound():
+    """CPU: the four entry points in the header, the built library,
+    exported_symbols() and _native._SIGS, each its _track sibling's arguments
+    plus one pointer; the ABI version stays 1."""
+    from pddp_amd import _native
+    assert_entry_points(NEW_SYMBOLS)
+    for kind in KINDS:
+        sig = _native._SIGS["pddp_%s_track_weighted" % kind]
+        sib = _native._SIGS["pddp_%s_track" % kind]
+        assert len(sig) == len(sib) + 1, kind
+        # (problem, table, ref, ref_len, ref_t0), weights, the sibling's rest
+        assert sig[:5] == sib[:5] and sig[5] is ctypes.c_void_p and \
+            sig[6:] == sib[5:], kind
+    assert ctypes.CDLL(_native.LIB_PATH).pddp_hip_abi_version() == 1
+
+
+def test_track_weighted_entry_points_refuse_before_any_launch():
+    """CPU (no device is touched: every answer comes before the first HIP
+    call): PDDP_E_BADARG for weights = NULL, ref = NULL, ref_len = 0,
+    ref_t0 = -1 and for a null required pointer / a non-positive size of the
+    siblings; PDDP_E_UNSUPPORTED for a Gaussian encoding, with and without a
+    table.  The non-null pointers are host words nobody reads."""
+    from pddp_amd import _native
+    pp, ppd, q = cartpole_pointers()
+    lib = _native.lib()
+    # after (problem, table, ref, ref_len, ref_t0, weights): the sibling's
+    tails = {
+        # B N Z U u_min u_max mask rec L J state
+        "derivs": [2, 3, q, q, None, None, None, q, q, q, None],
+        # B N A Z U gains alphas u_min u_max active bwd_status Zc Uc Jc
+        "line_search": [2, 3, 4, q, q, q, q, None, None, None, None, q, q, q]}
+    for ty in ("f32", "f64"):
+        for kind, tail in tails.items():
+            fn = getattr(lib, "pddp_%s_track_weighted_%s" % (kind, ty))
+
+            def call(problem, table=None, ref=q, ref_len=5, ref_t0=0,
+                     weights=q, tail=tail):
+                return fn(problem, table, ref, ref_len, ref_t0, weights,
+                          *tail, None)
+
+            # (never the good call: it would launch on host words)
+            assert call(pp, weights=None) == -1, (kind, ty)
+            assert call(pp, ref=None) == -1, (kind, ty)
+            assert call(pp, ref_len=0) == -1, (kind, ty)
+            assert call(pp, ref_t0=-1) == -1, (kind, ty)
+            assert call(None) == -1, (kind, ty)
+            assert call(ppd) == _native.E_UNSUPPORTED, (kind, ty)
+            assert call(ppd, table=q) == _native.E_UNSUPPORTED, (kind, ty)
+            assert call(pp, table=q, weights=None) == -1, (kind, ty)
+            for i, v in enumerate(tail):
+                if v is None:
+                    continue  # nullable
+                bad = list(tail)
+                bad[i] = None if v == q else 0
+                assert call(pp, tail=bad) == -1, (kind, ty, i)
+
+
+def test_composed_oracle_equals_the_oracle_of_the_weighted_problem():
+    """CPU: the composition the GPU tests compare against - per-trajectory
+    diagonals, a reference whose every row is the problem's own goals - is
+    Oracle.forward / Oracle.trajectory_cost of the weighted problem (f64)."""
+    o = orc.load(np.float64)
+    B = 2
+    for problem in PROBLEMS:
+        _, _, _, ops = _weights(problem, B, seed=30)
+        _, _, _, plain = _weights(problem, B, seed=30)  # (goals never touched)
+        rng = np.random.RandomState(1)
+        for b in range(B):
+            op = ops[b]
+            n, m, na = op.encoded_size, op.action_size, op.aug_size
+            z0 = np.asarray(MEAN0[problem], np.float64) + 1e-2 * rng.randn(n)
+            U = 2.0 * BOUND[problem] * rng.randn(7, m)  # (some rows clamp)
+            u_min = np.full(m, -BOUND[problem])
+            u_max = np.full(m, BOUND[problem])
+            xr = np.tile(np.array(op.x_goal[:na]), (3, 1))
+            ur = np.tile(np.array(op.u_goal[:m]), (3, 1))
+            want = o.forward(plain[b], z0, U, u_min, u_max)
+            got = _forward_tracked(o, op, z0, U, u_min, u_max, xr, ur, 1)
+            for nm in FWD_NAMES:
+                assert rel_err(got[nm], want[nm]) < 1e-13, (problem, b, nm)
+            Zn = np.stack([want["Z"], want["Z"] * 1.01], 1)
+            Un = np.stack([np.clip(U, u_min, u_max)] * 2, 1)
+            J = o.trajectory_cost(plain[b], Zn, Un)
+            Jt = _cost_tracked(o, op, Zn, Un, xr, ur, 2)
+            assert rel_err(Jt, J) < 1e-13, (problem, b)
+        # the weights matter to the oracle: trajectory 0 under trajectory 1's
+        J0 = o.trajectory_cost(plain[0], Zn, Un)
+        assert abs(J0 - J).max() > 1e-3 * abs(J).max(), problem
+
+
+# ---------------------------------------------------------------------------
+# records
+# ---------------------------------------------------------------------------
+
+@gpu
+@pytest.mark.parametrize("table", [False, True])
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", PROBLEMS)
+def test_track_weighted_records_vs_oracle(problem, dtype, table):
+    """B = 6, N = 70: a second, ragged chunk of the 64-lane staging and the J
+    sum across chunks; a reference of 20 rows read from row 3 on: the held
+    last row from horizon index 16 on, the terminal row included.  `rec`
+    pre-filled with NaN."""
+    B, N, L, t0 = 6, 70, 20, 3
+    s, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
+    xr, ur, ops = _both(s, problem, B, L, t0, table, (31, 32, 33))
+    assert tuple(s.reference.shape) == (B, L, 12) and s.ref_start == t0
+    assert tuple(s.batch_weights.shape) == (B, 20)
+    s.nominal_rollout()
+    s._rec.fill_(float("nan"))
+    s.derivs(set_state=False)
+    views = named_views(s)
+    o = orc.load(np_dtype(dtype))
+    tol = record_tol(dtype)
+    for b in range(B):
+        ref = _forward_tracked(o, ops[b], z0[b], U[b], u_min, u_max, xr[b],
+                               ur[b], t0)
+        for nm in FWD_NAMES:
+            e = rel_err(views[nm][b].cpu().numpy(), ref[nm])
+            print(problem, dtype, table, b, nm, e)
+            assert e < tol, (b, nm, e)
+        Jb = ref["L"].sum()
+        assert abs(float(s.J_opt[b]) - Jb) <= tol * abs(Jb), b
+
+
+# ---------------------------------------------------------------------------
+# line search
+# ---------------------------------------------------------------------------
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", PROBLEMS)
+def test_track_weighted_line_search_vs_oracle(problem, dtype):
+    """B = 5, N = 12 with 10, 11 and 17 step sizes: a wavefront's lanes
+    straddle trajectories, the last wavefront is ragged; a reference of 6 rows
+    read from row 2 on: the held row inside the horizon and under the terminal
+    cost.  The 11 once more with a table."""
+    from pddp_amd.controllers.solver import (ILQRSolver, fit_alphas,
+                                             mpc_alphas)
+    B, N, L, t0 = 5, 12, 6, 2
+    s0, _, z0, U, u_min, u_max = make_solver(problem, dtype, B, N)
+    td = TDT[dtype]
+    o = orc.load(np_dtype(dtype))
+    tol = record_tol(dtype)
+    for alphas, table in (
+            (fit_alphas(td, "cuda"), False), (mpc_alphas(td, "cuda"), False),
+            (torch.linspace(1.0, 0.01, 17).to(td), False),
+            (mpc_alphas(td, "cuda"), True)):
+        s = ILQRSolver(s0.problem, B, N, td, "cuda", torch.from_numpy(u_min),
+                       torch.from_numpy(u_max), alphas=alphas)
+        s.z0.copy_(s0.z0)
+        s.U.copy_(s0.U)
+        xr, ur, ops = _both(s, problem, B, L, t0, table, (34, 35, 36))
+        s.nominal_rollout()
+        s.derivs(set_state=False)
+        _unit_gains(s)
+        for t in (s.Zc, s.Uc, s.Jc):
+            t.fill_(float("nan"))
+        s.line_search()
+        k, K = s.gain_views()
+        A = s.A
+        assert A == alphas.numel()
+        Zc = s.Zc.permute(1, 0, 2, 3).cpu().numpy()  # (N+1, B, A, n)
+        Uc = s.Uc.permute(1, 0, 2, 3).cpu().numpy()
+        Jc = s.Jc.cpu().numpy()
+        for b in range(B):
+            Zn, Un = o.control_law(ops[b], s.Z[b].cpu().numpy(), U[b],
+                                   k[b].cpu().numpy(), K[b].cpu().numpy(),
+                                   s.alphas.cpu().numpy(), u_min, u_max)
+            J = _cost_tracked(o, ops[b], Zn, Un, xr[b], ur[b], t0)
+            e = (rel_err(Zc[:, b], Zn), rel_err(Uc[:, b], Un),
+                 rel_err(Jc[b], J))
+            print(problem, dtype, A, table, b, e)
+            assert max(e) < tol, (A, table, b, e)
+
+
+# ---------------------------------------------------------------------------
+# degenerate cases: one of the two says nothing new
+# ---------------------------------------------------------------------------
+
+def _records_and_candidates(solvers, B):
+    """Records, J_opt and - on the first solver's gains - candidates of every
+    solver, each from its own nominal rollout of the same z0, U."""
+    out, gains = [], None
+    for x in solvers:
+        x.nominal_rollout()
+        x._rec.fill_(float("nan"))
+        x.derivs(set_state=False)
+        r = {k: v.clone() for k, v in named_views(x).items()}
+        r["J_opt"] = x.J_opt.clone()
+        if gains is None:
+            _unit_gains(x)
+            gains = x.gains.clone()
+        else:
+            x.gains.copy_(gains)
+            x.bwd_status.zero_()
+        for t in (x.Zc, x.Uc, x.Jc):
+            t.fill_(float("nan"))
+        x.line_search()
+        r.update(Zc=x.Zc.clone(), Uc=x.Uc.clone(), Jc=x.Jc.clone())
+        out.append(r)
+    torch.cuda.synchronize()
+    return out
+
+
+def _assert_close(what, want, got, tol):
+    for nm in want:
+        e = rel_err(got[nm].cpu().numpy(), want[nm].cpu().numpy())
+        print(*what, nm, e, "same bits:", same_bits(got[nm], want[nm]))
+        assert e < tol, (nm, e)
+
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", PROBLEMS)
+def test_shared_diagonals_under_a_reference_equal_the_track_kernels(problem,
+                                                                    dtype):
+    """Every weights row the shared diagonals, next to a reference and a
+    table: records and candidates against the _track entry points' on the same
+    inputs and gains (to rounding: these are other kernels)."""
+    B, N = 5, 12
+    par, xg, ug, _ = perturbed(problem, B, seed=37)
+    xr, ur = reference_rows(problem, B, 6, seed=38)
+    solvers = []
+    for weighted in (False, True):
+        s = make_solver(problem, dtype, B, N)[0]
+        set_table(s, par, xg, ug)
+        set_ref(s, xr, ur, 2)
+        if weighted:
+            s.set_batch_weights(keep_reference=True)
+        solvers.append(s)
+    assert solvers[0].batch_weights is None
+    assert solvers[1].batch_weights is not None
+    want, got = _records_and_candidates(solvers, B)
+    _assert_close((problem, dtype), want, got, record_tol(dtype))
+
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", PROBLEMS)
+def test_weights_under_a_constant_reference_equal_the_weighted_kernels(
+        problem, dtype):
+    """Every reference row the table's goals (u_ref left to its default, the
+    table's u_goal), next to weights: records and candidates against the
+    _weighted entry points', which read the goals from the table."""
+    B, N = 5, 12
+    par, xg, ug, _ = perturbed(problem, B, seed=39)
+    q, qt, r, _ = _weights(problem, B, seed=40)
+    solvers = []
+    for tracking in (False, True):
+        s = make_solver(problem, dtype, B, N)[0]
+        set_table(s, par, xg, ug)
+        if tracking:
+            set_ref(s, np.repeat(xg[:, None], 4, 1), None, 1)
+        _set_weights(s, q, qt, r, keep_reference=tracking)
+        solvers.append(s)
+    assert solvers[0].reference is None and solvers[1].reference is not None
+    want, got = _records_and_candidates(solvers, B)
+    _assert_close((problem, dtype), want, got, record_tol(dtype))
+
+
+# ---------------------------------------------------------------------------
+# row ownership and masks
+# ---------------------------------------------------------------------------
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", ["cartpole", "double_cartpole"])
+def test_swapped_trajectories_swap_the_outputs(problem, dtype):
+    """Trajectories 1 and 3 swapped in the nominal, the gains, the reference,
+    the weights and the table swap the outputs of both kernels bit for bit
+    (one table indexed with another's stride does not survive this)."""
+    B, N, L, t0 = 5, 12, 6, 2
+    perm = [0, 3, 2, 1, 4]
+    par, xg, ug, _ = perturbed(problem, B, seed=41)
+    xr, ur = reference_rows(problem, B, L, seed=42)
+    q, qt, r, _ = _weights(problem, B, seed=43)
+    s = make_solver(problem, dtype, B, N)[0]
+    set_table(s, par, xg, ug)
+    set_ref(s, xr, ur, t0)
+    _set_weights(s, q, qt, r, keep_reference=True)
+    a = _records_and_candidates([s], B)[0]
+    s2 = make_solver(problem, dtype, B, N)[0]
+    set_table(s2, par[perm], xg[perm], ug[perm])
+    set_ref(s2, xr[perm], ur[perm], t0)
+    _set_weights(s2, q[perm], qt[perm], r[perm], keep_reference=True)
+    s2.Z.copy_(s.Z[perm])
+    s2.U.copy_(s.U[perm])
+    s2._rec.fill_(float("nan"))
+    s2.derivs(set_state=False)
+    b = {k: v.clone() for k, v in named_views(s2).items()}
+    b["J_opt"] = s2.J_opt.clone()
+    s2.gains.copy_(s.gains[perm])
+    s2.bwd_status.zero_()
+    for t in (s2.Zc, s2.Uc, s2.Jc):
+        t.fill_(float("nan"))
+    s2.line_search()
+    b.update(Zc=s2.Zc.clone(), Uc=s2.Uc.clone(), Jc=s2.Jc.clone())
+    torch.cuda.synchronize()
+    for nm in a:
+        assert bool(torch.isfinite(a[nm]).all()), nm
+        assert torch.equal(b[nm], a[nm][perm]), nm
+    # (the swap is seen: the two trajectories' outputs differ)
+    assert not torch.equal(a["Jc"][1], a["Jc"][3])
+    assert not torch.equal(a["L"][1], a["L"][3])
+
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", PROBLEMS)
+def test_track_weighted_kernels_honour_their_masks(problem, dtype):
+    B, N = 5, 12
+    s = make_solver(problem, dtype, B, N)[0]
+    _both(s, problem, B, 6, 2, True, (44, 45, 46))
+    s.nominal_rollout()
+    s.derivs(set_state=False)
+    _unit_gains(s)
+    want = dict(rec=s._rec.clone(), L=s.L.clone(), J=s.J_opt.clone())
+    mask = torch.tensor([1, 0, 1, 1, 0], dtype=torch.uint8, device="cuda")
+    off = mask == 0
+    for t in (s._rec, s.L, s.J_opt):
+        t.fill_(SENTINEL)
+    s.derivs(mask, set_state=False)
+    torch.cuda.synchronize()
+    for t, nm in ((s._rec, "rec"), (s.L, "L"), (s.J_opt, "J")):
+        assert bool((t[off] == SENTINEL).all()), nm
+        assert torch.equal(t[~off], want[nm][~off]), nm
+    # line search: active[b] == 0, bwd_status[b] != 0
+    s._rec.copy_(want["rec"])
+    s.L.copy_(want["L"])
+    s.line_search()
+    full = dict(Zc=s.Zc.clone(), Uc=s.Uc.clone(), Jc=s.Jc.clone())
+    active = torch.tensor([1, 1, 0, 1, 1], dtype=torch.uint8, device="cuda")
+    s.bwd_status[4] = 2
+    skipped = np.array([False, False, True, False, True])
+    for t in (s.Zc, s.Uc, s.Jc):
+        t.fill_(SENTINEL)
+    s.line_search(active=active)
+    torch.cuda.synchronize()
+    for nm in ("Zc", "Uc", "Jc"):
+        t = getattr(s, nm)
+        assert bool((t[skipped] == SENTINEL).all()), nm
+        assert torch.equal(t[~skipped], full[nm][~skipped]), nm
+
+
+# ---------------------------------------------------------------------------
+# plan and lifecycle
+# ---------------------------------------------------------------------------
+
+def _round_calls(s, monkeypatch):
+    """The records / sweep / search / accept entry points one round() calls
+    through _native.call, in order (an entry point called twice in a row -
+    stale records brought up to date ahead of the masked launch - once)."""
+    from pddp_amd import _native
+    log = []
+    real = _native.call
+
+    def call(name, dtype, *args):
+        entry = "%s_%s" % (name, _native.suffix(dtype))
+        if not log or log[-1] != entry:
+            log.append(entry)
+        return real(name, dtype, *args)
+
+    monkeypatch.setattr(_native, "call", call)
+    s.round()
+    monkeypatch.undo()
+    return [e for e in log if any(k in e for k in (
+        "derivs", "backward", "sweep", "line_search", "search", "accept"))]
+
+
+@gpu
+def test_track_weights_plan_and_lifecycle(monkeypatch):
+    from pddp_amd import _native
+    from pddp_amd.controllers.solver import ILQRSolver
+    B, N = 20, 10
+    s, _, z0, U, u_min, u_max = make_solver("cartpole", "f32", B, N)
+    z0t, Ut = torch.from_numpy(z0).cuda(), torch.from_numpy(U).cuda()
+    fresh_plan = s._plan(0)
+    assert fresh_plan == "one_launch"
+    xr, ur = reference_rows("cartpole", B, 6, seed=47)
+    q, qt, r, _ = _weights("cartpole", B, seed=48)
+    # without the keyword the second setter refuses, as ever
+    _set_weights(s, q, qt, r)
+    with pytest.raises(_native.NativeError, match="reference") as err:
+        set_ref(s, xr, ur, 2)
+    assert "keep_weights" in str(err.value)
+    assert s.reference is None
+    # ... with it both are held: weights first
+    s._graph = ("a captured round",)
+    s.set_reference(torch.from_numpy(xr), torch.from_numpy(ur), 2,
+                    keep_weights=True)
+    assert s.reference is not None and s.batch_weights is not None
+    assert s.ref_start == 2 and s._plan(0) == "records+separate"
+    assert s._derivs_due is True and s._rec_stale is True
+    assert s._graph is None
+    # ... and the reference first
+    o2 = make_solver("cartpole", "f32", B, N)[0]
+    set_ref(o2, xr, ur, 2)
+    with pytest.raises(_native.NativeError, match="reference") as err:
+        _set_weights(o2, q, qt, r)
+    assert "keep_reference" in str(err.value)
+    assert o2.batch_weights is None
+    o2._graph = ("a captured round",)
+    _set_weights(o2, q, qt, r, keep_reference=True)
+    assert o2.reference is not None and o2.batch_weights is not None
+    assert o2._plan(0) == "records+separate" and o2._graph is None
+    assert (o2._one_launch, o2._nominal_sweep, o2._fused) == (False,) * 3
+    assert torch.equal(o2.reference, s.reference)
+    assert torch.equal(o2.batch_weights, s.batch_weights)
+    # a round is derivs, sweep, line search, accept on the new entry points
+    s.set_nominal(z0t, Ut)
+    assert _round_calls(s, monkeypatch) == [
+        "pddp_derivs_track_weighted_f32", "pddp_riccati_backward_variant_f32",
+        "pddp_line_search_track_weighted_f32", "pddp_accept_f32"]
+    assert not s._one_launch_applied() and not s._nominal_sweep_applied()
+    assert s._plan(0) == "records+separate"
+    o2.set_nominal(z0t, Ut)
+    o2.round()
+    torch.cuda.synchronize()
+    for nm in ("Z", "U", "J_opt", "state", "mu", "delta"):
+        assert torch.equal(getattr(o2, nm), getattr(s, nm)), nm
+    # the one-problem launches refuse
+    for call in (lambda: s.sweep_nominal(),
+                 lambda: s.round_nominal(5e-6, 1e10, 50),
+                 lambda: s.search_accept(5e-6, 1e10, 50),
+                 lambda: s.closed_loop()):
+        with pytest.raises(_native.NativeError):
+            call()
+    # moving the window drops a captured round
+    s._graph = ("a captured round",)
+    s.set_reference_start(3)
+    assert s.ref_start == 3 and s._graph is None and s._derivs_due is True
+    # the reference cleared: the weights' entry points; the weights cleared
+    # instead: the reference's
+    s.clear_reference()
+    assert s.reference is None and s.ref_start == 0
+    assert s._plan(0) == "records+separate"
+    s.set_nominal(z0t, Ut)
+    assert _round_calls(s, monkeypatch) == [
+        "pddp_derivs_weighted_f32", "pddp_riccati_backward_variant_f32",
+        "pddp_line_search_weighted_f32", "pddp_accept_f32"]
+    o2.clear_batch_weights()
+    assert o2.batch_weights is None and o2._plan(0) == "records+separate"
+    o2.set_nominal(z0t, Ut)
+    assert _round_calls(o2, monkeypatch) == [
+        "pddp_derivs_track_f32", "pddp_riccati_backward_variant_f32",
+        "pddp_line_search_track_f32", "pddp_accept_f32"]
+    # both gone: the plan and the results of a solver that never had either
+    s.clear_batch_weights()
+    o2.clear_reference()
+    s3 = ILQRSolver(s.problem, B, N, torch.float32, "cuda",
+                    torch.from_numpy(u_min), torch.from_numpy(u_max))
+    s3.set_nominal(z0t, Ut)
+    s3.round()
+    for x in (s, o2):
+        assert x._plan(0) == fresh_plan
+        x.set_nominal(z0t, Ut)
+        x.round()
+        assert x._one_launch_applied()
+        torch.cuda.synchronize()
+        for nm in ("Z", "U", "J_opt", "state", "iter", "mu", "delta",
+                   "active", "fresh"):
+            assert torch.equal(getattr(x, nm), getattr(s3, nm)), nm
+
+
+# ---------------------------------------------------------------------------
+# MPC trials
+# ---------------------------------------------------------------------------
+
+def _noisy_advance(s, T, t, logs, w, v, seed, x_true, Ylog, ref, ref_t0,
+                   step_offset=0):
+    """pddp_mpc_advance_noisy_* itself on the solver's buffers; `logs` as
+    solver_util.trial_logs; control step t is step `step_offset` + t of the
+    generator."""
+    from pddp_amd import _native
+    p = _native.ptr
+    _native.call("pddp_mpc_advance_noisy", s.dtype,
+                 ctypes.addressof(s.problem), p(s.batch_table), p(ref),
+                 ref.shape[1], ref_t0, s.B, s.N, T, t, p(s.z0), p(s.U),
+                 p(s.Z), p(s.u_min), p(s.u_max), None, None,
+                 p(std_vec(s, w)), p(std_vec(s, v)), seed, 0, step_offset,
+                 p(x_true),
+                 p(Ylog), None, *[p(x) for x in logs], p(s.mu), p(s.delta),
+                 p(s.state), p(s.iter), p(s.active), p(s.fresh), p(s.n_live),
+                 s._s())
+    torch.cuda.synchronize()
+
+
+def _observe(x, v, seed):
+    from pddp_amd import _native
+    p = _native.ptr
+    B, n = x.shape
+    v_t = torch.full((n,), v, dtype=x.dtype, device="cuda")
+    y = torch.full_like(x, SENTINEL)
+    _native.call("pddp_mpc_observe", x.dtype, B, n, p(x), p(v_t), seed, 0, 0,
+                 None, p(y), _native.stream_handle())
+    torch.cuda.synchronize()
+    return y
+
+
+def _trial_solver(problem, dtype, B, N, xr, ur, start, w):
+    s = loop_solver(problem, dtype, B, N)
+    set_ref(s, xr, ur, start)
+    if w is not None:
+        _set_weights(s, *w, keep_reference=True)
+    return s
+
+
+def _assert_same_trial(r, logs, s, c):
+    for nm, want in zip(("X", "U", "J", "states", "unfinished"), logs):
+        assert torch.equal(getattr(r, nm), want), nm
+    for nm in STATE:
+        assert torch.equal(getattr(s, nm), getattr(c, nm)), nm
+
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", ["cartpole", "pendulum"])
+def test_mpc_trial_with_both_is_the_composed_trial(problem, dtype):
+    """B = 4, N = 12, 3 control steps of 2 rounds, a reference of 8 rows from
+    row 1 on (the window runs onto the held row): mpc_closed_loop against
+    set_reference_start(1 + t), rounds(2, n_iterations=1) and
+    pddp_mpc_advance_track_* called directly, bit for bit; then a second call
+    with z0 = None against the composition continued."""
+    B, N, T, R, L, start = 4, 12, 3, 2, 8, 1
+    xr, ur = reference_rows(problem, B, L, seed=49)
+    w = _weights(problem, B, seed=50)[:3]
+    s = _trial_solver(problem, dtype, B, N, xr, ur, start, w)
+    c = _trial_solver(problem, dtype, B, N, xr, ur, 0, w)
+    for call in range(2):
+        r = s.mpc_closed_loop(T, R)
+        torch.cuda.synchronize()
+        assert s.ref_start == start + T * (call + 1)
+        assert s._plan(0) == "records+separate"
+        assert bool(torch.isfinite(r.J).all())
+        c.set_nominal(c.z0, c.U)
+        logs = trial_logs(c, T, SENTINEL)
+        for t in range(T):
+            t0 = start + T * call + t
+            c.set_reference_start(t0)
+            c.rounds(R, n_iterations=1)
+            mpc_advance(c, T, t, logs, ref=c.reference, ref_t0=t0)
+            c._derivs_due = True
+        _assert_same_trial(r, logs, s, c)
+        if call == 0:
+            first = r
+    # the weights matter: the same trial along the reference alone
+    s1 = _trial_solver(problem, dtype, B, N, xr, ur, start, None)
+    r1 = s1.mpc_closed_loop(T, R)
+    torch.cuda.synchronize()
+    assert not torch.equal(r1.U, first.U)
+
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", ["cartpole", "pendulum"])
+def test_noisy_mpc_trial_with_both_is_the_composed_trial(problem, dtype):
+    """The same trial under process and measurement noise drawn on the device:
+    against pddp_mpc_observe_*, the rounds and pddp_mpc_advance_noisy_* with
+    the window, bit for bit; then a second call with z0 = None and
+    step_offset = 3 against the composition continued - the window at row
+    1 + 3 + t under the generator's step 3 + t, no new first observation."""
+    B, N, T, R, L, start, seed = 4, 12, 3, 2, 8, 1, 7
+    xr, ur = reference_rows(problem, B, L, seed=51)
+    w = _weights(problem, B, seed=52)[:3]
+    s = _trial_solver(problem, dtype, B, N, xr, ur, start, w)
+    c = _trial_solver(problem, dtype, B, N, xr, ur, 0, w)
+    x_true = c.z0.clone()
+    for call in range(2):
+        r = s.mpc_closed_loop(T, R, process_std=STD, obs_std=STD, seed=seed,
+                              step_offset=T * call)
+        torch.cuda.synchronize()
+        assert s.ref_start == start + T * (call + 1)
+        assert bool(torch.isfinite(r.J).all())
+        # (the first observation is drawn once; later the controller holds it)
+        c.set_nominal(_observe(x_true, STD, seed) if call == 0 else c.z0, c.U)
+        logs = trial_logs(c, T, SENTINEL)
+        Y = torch.full((B, T + 1, c.n), SENTINEL, dtype=c.dtype, device="cuda")
+        Y[:, 0] = c.z0
+        for t in range(T):
+            t0 = start + T * call + t
+            c.set_reference_start(t0)
+            c.rounds(R, n_iterations=1)
+            _noisy_advance(c, T, t, logs, STD, STD, seed, x_true, Y,
+                           c.reference, t0, step_offset=T * call)
+            c._derivs_due = True
+        _assert_same_trial(r, logs, s, c)
+        assert torch.equal(r.Y, Y)
+        assert torch.equal(s.x_true, x_true)
+        if call == 0:
+            first = r
+    # (the continued trial drew other measurement normals than the first)
+    assert not torch.equal(r.Y[:, 1:] - r.X[:, 1:],
+                           first.Y[:, 1:] - first.X[:, 1:])
+
+
+# ---------------------------------------------------------------------------
+# the yardstick and the captured round
+# ---------------------------------------------------------------------------
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", PROBLEMS)
+def test_closed_loop_along_the_reference_reports_under_the_shared_matrices(
+        problem, dtype):
+    """closed_loop(track=True, samples=4) with both set: J and stats bit-equal
+    to an un-weighted solver's that holds the same Z, U, gains and
+    reference."""
+    B, N, S = 5, 12, 4
+    s = make_solver(problem, dtype, B, N)[0]
+    xr, ur, _ = _both(s, problem, B, 6, 2, False, (0, 53, 54))
+    s.nominal_rollout()
+    s.derivs(set_state=False)
+    _unit_gains(s)
+    s2 = make_solver(problem, dtype, B, N)[0]
+    set_ref(s2, xr, ur, 2)
+    for nm in ("Z", "U", "gains"):
+        getattr(s2, nm).copy_(getattr(s, nm))
+    got = s.closed_loop(track=True, samples=S, accepted=False)
+    want = s2.closed_loop(track=True, samples=S, accepted=False)
+    torch.cuda.synchronize()
+    assert s.ref_start == 2 and s.batch_weights is not None
+    assert bool(torch.isfinite(got.J).all())
+    assert torch.equal(got.J, want.J)
+    assert torch.equal(got.stats, want.stats)
+    # (the gains are those of the weighted cost: another policy than s2's own)
+    s2.derivs(set_state=False)
+    _unit_gains(s2)
+    assert not torch.equal(s2.gains, s.gains)
+
+
+@gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("problem", PROBLEMS)
+def test_captured_round_with_both_equals_the_eager_round(problem, dtype):
+    """capture_round with a reference and weights captures the window as it
+    stands and both addresses: a replay equals an eager round bit for bit, and
+    is another round than the one along the reference alone; setting the
+    weights again drops the graph."""
+    B, N = 3, 8
+    xr, ur = reference_rows(problem, B, 12, seed=55)
+    w = _weights(problem, B, seed=56)[:3]
+    out = []
+    for graph in (False, True):
+        s = _trial_solver(problem, dtype, B, N, xr, ur, 1, w)
+        s.set_nominal(s.z0, s.U)
+        if graph:
+            s.capture_round()
+            assert s._graph is not None and not s._graph_nominal
+            s.set_nominal(s.z0, s.U)
+            s.replay_round()
+        else:
+            s.round()
+        torch.cuda.synchronize()
+        out.append(s)
+    for nm in ("Z", "U", "J_opt", "state", "mu", "delta"):
+        assert torch.equal(getattr(out[0], nm), getattr(out[1], nm)), nm
+    assert bool(torch.isfinite(out[1].J_opt).all())
+    alone = _trial_solver(problem, dtype, B, N, xr, ur, 1, None)
+    alone.set_nominal(alone.z0, alone.U)
+    alone.round()
+    assert not torch.equal(alone.J_opt, out[1].J_opt)
+    _set_weights(out[1], *w, keep_reference=True)
+    assert out[1]._graph is None
+
+
+def test_controller_methods_forward_the_new_keywords():
+    """iLQRController forwards keep_weights / keep_reference to its solver,
+    and only when they are set (a fake solver: no device)."""
+    from pddp_amd.controllers.ilqr import iLQRController
+    calls = []
+    ctl = iLQRController.__new__(iLQRController)
+    ctl._solver = types.SimpleNamespace(
+        set_reference=lambda *a, **k: calls.append(("ref", a, k)),
+        set_batch_weights=lambda *a, **k: calls.append(("w", a, k)))
+    ctl.set_reference("x", "u", 3)
+    ctl.set_reference("x", "u", 3, keep_weights=True)
+    ctl.set_batch_weights("q", "qt", "r", False)
+    ctl.set_batch_weights("q", "qt", "r", False, keep_reference=True)
+    assert calls == [
+        ("ref", ("x", "u", 3), {}),
+        ("ref", ("x", "u", 3), {"keep_weights": True}),
+        ("w", ("q", "qt", "r", False), {}),
+        ("w", ("q", "qt", "r", False), {"keep_reference": True})]
