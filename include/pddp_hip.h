@@ -412,6 +412,91 @@ int pddp_closed_loop_draws_f64(int B, int N, int S, int n, int which,
                                uint64_t seed, uint64_t sample_offset,
                                double* W /* [B][N][S][n] */, void* stream);
 
+/* ---- sampled shooting: S perturbed copies of every trajectory's action
+ * sequence rolled out open loop, the cheapest found inside the launch and only
+ * its states and actions written (csrc/shoot.hip; the reference has no
+ * counterpart).  Candidate (b, s), with r = sample_offset + b S + s (uint64)
+ * and t = 0 .. N-1:
+ *
+ *   x_0  = z0[b]
+ *   xi_t = the m unit normals of (seed, r, t, stream 2): the draws of
+ *          pddp_closed_loop_noisy_* above with counter
+ *          (r & 0xffffffff, r >> 32, t, (2 << 16) | k), components beyond m
+ *          discarded
+ *   e_0  = xi_0;  e_t = fma(beta, e_{t-1}, gamma xi_t)     (AR(1), unit variance)
+ *          beta = smooth, gamma = sqrt(1 - beta^2) formed on the host in double,
+ *          both then cast to the run's type; gamma xi_t is rounded, then ONE fma
+ *   u_t  = clamp(fma(a_std, e_t, U[b][t]))     s >= 1
+ *   u_t  = clamp(U[b][t])                      s == 0: the base sequence is a
+ *          candidate, so the result is never worse than where it started
+ *   J += l(x_t, u_t);  x_{t+1} = f_b(x_t, u_t);  then J += l_f(x_N)
+ *
+ * The clamped action is what is applied, costed and written (bounds NULL
+ * together: no clamp).  pddp_shoot_batch_* takes `table` [B][PDDP_BATCH_ROW]:
+ * trajectory b runs row b's parameters and goals, as pddp_line_search_batch_*.
+ * z0 [B][n]; U [B][N][m] the base sequence; a_std [m], of the run's type,
+ * entries >= 0 the caller's business; smooth in [0, 1).
+ *
+ * Jc [B][S] out: every candidate's cost.  best [B] out: the s of the lowest
+ * FINITE Jc[b][s], ties to the lower s; no finite cost: best[b] = -1,
+ * J_best[b] = +inf and row b of Z_out / U_out is not written.  J_best [B] out,
+ * nullable: the bits of Jc[b][best[b]].  Z_out [B][N+1][n], U_out [B][N][m]
+ * out, both or neither: the winner's states and applied actions - the winner
+ * is rolled out a second time inside the launch by the instructions that
+ * summed its cost, with their stores enabled; no [B][N][S][.] tensor exists.
+ * The argmin meets in an order that depends on S alone (the lane's own
+ * candidates in s order, a butterfly over its lane group comparing (J, s)
+ * lexicographically, then the wavefronts in their order; no atomics): a
+ * trajectory gets the same bits wherever it sits in the batch, and run alone
+ * with sample_offset + b S it gets the draws it had in the batch.
+ * active [B] nullable: trajectories with active[b] == 0 are skipped, nothing of
+ * theirs is read or written.
+ *
+ * pddp_shoot_draws_* writes the unit normals xi, E [B][N][S][m], through the
+ * rollouts' own device function: for tests and to replay a candidate.
+ * (pddp_closed_loop_draws_* keeps to streams 0 and 1.)
+ *
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY.
+ * PDDP_E_BADARG: a null required pointer (problem, z0, U, a_std, Jc, best; the
+ * table of _batch_); non-positive B, N or S; B S > 0x7fffffff; exactly one of
+ * Z_out / U_out; U_out == U or Z_out == z0 (the caller owns a second buffer);
+ * smooth outside [0, 1) or NaN; draws: a null E, a non-positive size,
+ * m > PDDP_MAX_ACTION.  PDDP_E_UNSUPPORTED: any other encoding.  All before
+ * any HIP call. */
+int pddp_shoot_f32(const pddp_problem* problem, int B, int N, int S,
+                   const float* z0, const float* U, const float* u_min,
+                   const float* u_max, const float* a_std, double smooth,
+                   uint64_t seed, uint64_t sample_offset,
+                   const uint8_t* active, float* Jc, int32_t* best,
+                   float* J_best, float* Z_out, float* U_out, void* stream);
+int pddp_shoot_f64(const pddp_problem* problem, int B, int N, int S,
+                   const double* z0, const double* U, const double* u_min,
+                   const double* u_max, const double* a_std, double smooth,
+                   uint64_t seed, uint64_t sample_offset,
+                   const uint8_t* active, double* Jc, int32_t* best,
+                   double* J_best, double* Z_out, double* U_out, void* stream);
+int pddp_shoot_batch_f32(const pddp_problem* problem, const float* table,
+                         int B, int N, int S, const float* z0, const float* U,
+                         const float* u_min, const float* u_max,
+                         const float* a_std, double smooth, uint64_t seed,
+                         uint64_t sample_offset, const uint8_t* active,
+                         float* Jc, int32_t* best, float* J_best, float* Z_out,
+                         float* U_out, void* stream);
+int pddp_shoot_batch_f64(const pddp_problem* problem, const double* table,
+                         int B, int N, int S, const double* z0,
+                         const double* U, const double* u_min,
+                         const double* u_max, const double* a_std,
+                         double smooth, uint64_t seed, uint64_t sample_offset,
+                         const uint8_t* active, double* Jc, int32_t* best,
+                         double* J_best, double* Z_out, double* U_out,
+                         void* stream);
+int pddp_shoot_draws_f32(int B, int N, int S, int m, uint64_t seed,
+                         uint64_t sample_offset, float* E /* [B][N][S][m] */,
+                         void* stream);
+int pddp_shoot_draws_f64(int B, int N, int S, int m, uint64_t seed,
+                         uint64_t sample_offset, double* E /* [B][N][S][m] */,
+                         void* stream);
+
 /* ---- pddp.py:209-245 _apply_controller(mpc=True) with ilqr.py:355-362
  * forward(mpc=True) as the controller, batched and with the sample models as
  * the plant: the hand-over between two control steps of a receding-horizon

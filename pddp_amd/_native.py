@@ -70,6 +70,8 @@ _P = c_void_p  # (then: pieces of the closed-loop and hand-over signatures)
 _REF, _NOISE = [_P, c_int, c_int], [_P, _P, c_uint64, c_uint64]
 _LOOP, _LOOP_OUT = [c_int] * 3 + [_P] * 7, [_P] * 6
 _STEP, _STEP_OUT = [c_int] * 4 + [_P] * 7, [_P] * 14
+# (sampled shooting: shapes, z0 .. a_std, smooth, seed, offset, mask, outputs)
+_SHOOT = [c_int] * 3 + [_P] * 5 + [c_double, c_uint64, c_uint64] + [_P] * 7
 _SIGS = {
     "pddp_hip_abi_version": [],
     "pddp_hip_device_count": [],
@@ -93,6 +95,9 @@ _SIGS = {
     "pddp_closed_loop_noisy": [_P] + _LOOP + _NOISE + _LOOP_OUT,
     "pddp_closed_loop_draws": [c_int] * 5 + [c_uint64, c_uint64, _P, _P],
     "pddp_closed_loop_track": [_P] + _REF + _LOOP + _NOISE + _LOOP_OUT,
+    "pddp_shoot": [_P] + _SHOOT,
+    "pddp_shoot_batch": [_P, _P] + _SHOOT,
+    "pddp_shoot_draws": [c_int] * 4 + [c_uint64, c_uint64, _P, _P],
     "pddp_mpc_advance": [_P, _P] + _STEP + _STEP_OUT,
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
@@ -168,6 +173,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_line_search_batch", "pddp_closed_loop", "pddp_mpc_advance",
           "pddp_closed_loop_noisy", "pddp_closed_loop_draws",
           "pddp_closed_loop_track",
+          "pddp_shoot", "pddp_shoot_batch", "pddp_shoot_draws",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
           "pddp_mpc_advance_noisy", "pddp_mpc_observe",

@@ -1127,6 +1127,106 @@ class ILQRSolver(object):
                      int(sample_offset), _native.ptr(W), self._s())
         return W
 
+    def _action_std(self, std, what="shoot"):
+        """[m] device vector of a perturbation level given as a scalar or [m]
+        (`_noise_std`, of the action's length)."""
+        std = torch.as_tensor(std, dtype=self.dtype, device=self.device)
+        if std.dim() == 0:
+            std = std.repeat(self.m)
+        if tuple(std.shape) != (self.m,):
+            raise _native.NativeError(
+                "%s: std has shape %s, expected a scalar or (%d,)" % (
+                    what, tuple(std.shape), self.m))
+        return std.contiguous()
+
+    @_on_device
+    def shoot(self, samples, std, smooth=0.0, seed=0, sample_offset=0,
+              active=None, adopt=True, events=None):
+        """Sampled shooting around the current action sequence
+        (pddp_shoot_*, csrc/shoot.hip): S = `samples` candidates per
+        trajectory, candidate 0 the sequence `U` itself, candidate s >= 1
+        u_t = clamp(U[b][t] + std (.) e_t) with e an AR(1) of unit variance,
+        e_t = smooth e_{t-1} + sqrt(1 - smooth^2) xi_t, over the unit normals
+        xi of (`seed`, `sample_offset` + b S + s, t) - `shoot_draws` returns
+        them.  Each is rolled out open loop from `z0` under the solver's own
+        model, cost and bounds (row b of `batch_table` while a table is set);
+        the cheapest finite one is found inside the launch and only its
+        states and actions are written.  `std`: a scalar or [m]; `smooth` in
+        [0, 1); `active` [B] uint8: trajectories with 0 are skipped.
+
+        Returns an object with `J` [B][S], `best` [B] int32 (-1: no candidate
+        of that trajectory had a finite cost) and `J_best` [B] (the bits of
+        J[b, best[b]]; +inf with best == -1); of a masked trajectory NaN, -1,
+        NaN.  Never worse than the start: J_best <= J[:, 0].
+
+        `adopt=True`: `U` and `Z` take the winners' rows in place (a
+        device-side select on `best`, no host synchronisation; trajectories
+        with best == -1 or masked keep theirs) and the controller state is
+        re-armed as `set_nominal` does, so the next round starts with records.
+        No rollout is launched: `Z` already is the rollout of `U`.  `z0`,
+        `x_true`, the plan, the table and a captured graph's buffers stay.
+        `adopt=False`: nothing of the solver is touched; the object also has
+        `Z` [B][N+1][n] and `U` [B][N][m], the winners (NaN rows where there
+        is none).  `events`: a (start, stop) pair for the dispatch.
+
+        While a reference (`set_reference`) or per-trajectory cost weights
+        (`set_batch_weights`) are set the call is refused: the candidates
+        would be costed under another objective than the line search's."""
+        self._need_sample_problem("shoot")
+        if self.reference is not None:
+            raise _native.NativeError(
+                "shoot costs its candidates under ONE goal per trajectory; "
+                "with a reference (set_reference) the line search's objective "
+                "is another one")
+        if self.batch_weights is not None:
+            raise _native.NativeError(
+                "shoot costs its candidates under the shared Q, Q_term, R; "
+                "with per-trajectory weights (set_batch_weights) the line "
+                "search's objective is another one")
+        B, N, n, m = self.B, self.N, self.n, self.m
+        S = int(samples)
+        if S < 1:
+            raise _native.NativeError("shoot: %d samples" % S)
+        a_std = self._action_std(std)
+        self._check_active("shoot", active)
+        masked = active is not None
+        out = types.SimpleNamespace(
+            J=self._out(masked, B, S),
+            best=self._out(masked, B, dtype=torch.int32, fill=-1),
+            J_best=self._out(masked, B))
+        # (the winners' buffers: the caller's with adopt=False, rows without a
+        # winner NaN; else scratch the select below reads)
+        Zw = self._out(not adopt, B, N + 1, n)
+        Uw = self._out(not adopt, B, N, m)
+        p = _native.ptr
+        self._launch(events, self._problem_call, "pddp_shoot", B, N, S,
+                     p(self.z0), p(self.U), p(self.u_min), p(self.u_max),
+                     p(a_std), float(smooth), int(seed), int(sample_offset),
+                     p(active), p(out.J), p(out.best), p(out.J_best), p(Zw),
+                     p(Uw), self._s())
+        if not adopt:
+            out.Z, out.U = Zw, Uw
+            return out
+        won = (out.best >= 0).reshape(B, 1, 1)
+        torch.where(won, Uw, self.U, out=self.U)
+        torch.where(won, Zw, self.Z, out=self.Z)
+        self.reset_controller_state()
+        return out
+
+    @_on_device
+    def shoot_draws(self, samples, seed=0, sample_offset=0):
+        """The unit normals xi `shoot(samples, seed=, sample_offset=)` draws,
+        E [B][N][S][m] (pddp_shoot_draws_*): to look at, or to replay, a
+        candidate."""
+        S = int(samples)
+        if S < 1:
+            raise _native.NativeError("shoot_draws: %d samples" % S)
+        E = torch.empty(self.B, self.N, S, self.m, dtype=self.dtype,
+                        device=self.device)
+        _native.call("pddp_shoot_draws", self.dtype, self.B, self.N, S, self.m,
+                     int(seed), int(sample_offset), _native.ptr(E), self._s())
+        return E
+
     def _plant_table(self, what, params, x_goal, u_goal):
         """[B][BATCH_ROW] plant rows of a trial whose fields are [B][.]: a
         field not given is `batch_table`'s if a table is set, else the shared
