@@ -497,6 +497,85 @@ int pddp_shoot_draws_f64(int B, int N, int S, int m, uint64_t seed,
                          uint64_t sample_offset, double* E /* [B][N][S][m] */,
                          void* stream);
 
+/* ---- sampled shooting with a softmin-weighted (MPPI) update: the candidates
+ * of pddp_shoot_* above, and instead of the cheapest one the weighted mean of
+ * all their perturbations added to the base sequence, that sequence rolled out
+ * and costed inside the launch (csrc/mppi.hip; the reference has no
+ * counterpart).  Trajectory b, candidate s, r = sample_offset + b S + s:
+ *
+ *   Jc[b][s], best[b], J_best[b]   pddp_shoot_*'s law, word for word (stream 2,
+ *                                  the AR(1) with explicit fmas, candidate 0 the
+ *                                  base, the clamp, the lowest finite cost, ties
+ *                                  to the lower s)
+ *   a_s   = (Jc[b][s] - J_best[b]) / lam[b]    (the difference, then the quotient)
+ *   w_s   = exp(-a_s) where Jc[b][s] is finite, else 0     (w_best = 1: eta >= 1)
+ *   eta   = sum_s w_s;   W[b][s] = w_s / eta
+ *   ebar_t = (sum_{s>=1} w_s e_{s,t}) / eta    e_{s,t}: the RAW AR(1) value,
+ *                                  before a_std and the clamp; every product is
+ *                                  rounded before it is summed; candidate 0 adds
+ *                                  w_0 to eta and nothing to the sum
+ *   Uw[b][t] = clamp(fma(a_std, ebar_t, U[b][t]))
+ *   Zw[b]    = the open-loop rollout of Uw[b] from z0[b] under f_b;  J_w[b] = its
+ *              cost (stage costs in t order, then the terminal one)
+ *
+ * The order of every sum depends on S alone, never on b or B.  With G the lane
+ * group of S (pddp_closed_loop_*'s mapping: S rounded up to a power of two up to
+ * 64, then to whole wavefronts up to 256) lane l of the group holds the
+ * candidates s = l, l + G, ... ("turns").  eta: a lane's own weights in s order,
+ * then the group.  sum_s w_s e_{s,t}, per step t and component: the group's sum
+ * of turn 0, then that of turn 1 added to it, and so on.  A sum over the group
+ * is a butterfly over its lanes of a wavefront with partner distances 1, 2, 4,
+ * ... (both partners form the same sum; lanes without a candidate, and
+ * candidates whose weight is 0, add +0), then the wavefronts in their order.
+ * No atomics: a trajectory's outputs are the same bits wherever it sits in the
+ * batch, and with sample_offset + b0 S they are the same bits when trajectories
+ * b0.. run alone.
+ *
+ * Arguments beside pddp_shoot_*'s: lam [B], one temperature per trajectory in
+ * cost units; lam[b] <= 0 or NaN is treated as "no finite candidate".  W [B][S]
+ * out, nullable.  J_w [B] out.  Z_out [B][N+1][n] / U_out [B][N][m], both or
+ * neither, receive Zw / Uw (shoot's aliasing rules); with S > 256 the running
+ * sum over a lane's turns is kept in U_out, so both are required then.  Without
+ * a finite candidate: best[b] = -1, J_best[b] = J_w[b] = +inf, row b of W is
+ * zeros and row b of Z_out / U_out is not written (Jc[b] is).  active [B]
+ * nullable: nothing of a skipped trajectory is read or written.
+ *
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY.
+ * PDDP_E_BADARG: pddp_shoot_*'s list; a null lam or J_w; S > 256 without
+ * Z_out / U_out.  PDDP_E_UNSUPPORTED: any other encoding.  All before any HIP
+ * call. */
+int pddp_mppi_f32(const pddp_problem* problem, int B, int N, int S,
+                  const float* z0, const float* U, const float* u_min,
+                  const float* u_max, const float* a_std, const float* lam,
+                  double smooth, uint64_t seed, uint64_t sample_offset,
+                  const uint8_t* active, float* Jc, int32_t* best,
+                  float* J_best, float* W, float* J_w, float* Z_out,
+                  float* U_out, void* stream);
+int pddp_mppi_f64(const pddp_problem* problem, int B, int N, int S,
+                  const double* z0, const double* U, const double* u_min,
+                  const double* u_max, const double* a_std, const double* lam,
+                  double smooth, uint64_t seed, uint64_t sample_offset,
+                  const uint8_t* active, double* Jc, int32_t* best,
+                  double* J_best, double* W, double* J_w, double* Z_out,
+                  double* U_out, void* stream);
+int pddp_mppi_batch_f32(const pddp_problem* problem, const float* table,
+                        int B, int N, int S, const float* z0, const float* U,
+                        const float* u_min, const float* u_max,
+                        const float* a_std, const float* lam, double smooth,
+                        uint64_t seed, uint64_t sample_offset,
+                        const uint8_t* active, float* Jc, int32_t* best,
+                        float* J_best, float* W, float* J_w, float* Z_out,
+                        float* U_out, void* stream);
+int pddp_mppi_batch_f64(const pddp_problem* problem, const double* table,
+                        int B, int N, int S, const double* z0,
+                        const double* U, const double* u_min,
+                        const double* u_max, const double* a_std,
+                        const double* lam, double smooth, uint64_t seed,
+                        uint64_t sample_offset, const uint8_t* active,
+                        double* Jc, int32_t* best, double* J_best, double* W,
+                        double* J_w, double* Z_out, double* U_out,
+                        void* stream);
+
 /* ---- pddp.py:209-245 _apply_controller(mpc=True) with ilqr.py:355-362
  * forward(mpc=True) as the controller, batched and with the sample models as
  * the plant: the hand-over between two control steps of a receding-horizon

@@ -72,6 +72,8 @@ _LOOP, _LOOP_OUT = [c_int] * 3 + [_P] * 7, [_P] * 6
 _STEP, _STEP_OUT = [c_int] * 4 + [_P] * 7, [_P] * 14
 # (sampled shooting: shapes, z0 .. a_std, smooth, seed, offset, mask, outputs)
 _SHOOT = [c_int] * 3 + [_P] * 5 + [c_double, c_uint64, c_uint64] + [_P] * 7
+# (its weighted update: lam after a_std; W and J_w after J_best)
+_MPPI = [c_int] * 3 + [_P] * 6 + [c_double, c_uint64, c_uint64] + [_P] * 9
 _SIGS = {
     "pddp_hip_abi_version": [],
     "pddp_hip_device_count": [],
@@ -98,6 +100,8 @@ _SIGS = {
     "pddp_shoot": [_P] + _SHOOT,
     "pddp_shoot_batch": [_P, _P] + _SHOOT,
     "pddp_shoot_draws": [c_int] * 4 + [c_uint64, c_uint64, _P, _P],
+    "pddp_mppi": [_P] + _MPPI,
+    "pddp_mppi_batch": [_P, _P] + _MPPI,
     "pddp_mpc_advance": [_P, _P] + _STEP + _STEP_OUT,
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
@@ -174,6 +178,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_closed_loop_noisy", "pddp_closed_loop_draws",
           "pddp_closed_loop_track",
           "pddp_shoot", "pddp_shoot_batch", "pddp_shoot_draws",
+          "pddp_mppi", "pddp_mppi_batch",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
           "pddp_mpc_advance_noisy", "pddp_mpc_observe",

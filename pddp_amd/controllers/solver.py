@@ -1227,6 +1227,107 @@ class ILQRSolver(object):
                      int(seed), int(sample_offset), _native.ptr(E), self._s())
         return E
 
+    @_on_device
+    def mppi(self, samples, std, temperature, smooth=0.0, seed=0,
+             sample_offset=0, iterations=1, active=None, adopt=True,
+             events=None):
+        """Sampled shooting with a softmin-weighted (MPPI) update of the
+        action sequence (pddp_mppi_*, csrc/mppi.hip): `shoot`'s S = `samples`
+        candidates, costed by the same law, and instead of the cheapest one
+        the sequence U + std (.) sum_s W[b][s] e_s, clamped, with
+        W[b][s] = softmin_s(J[b][s] / temperature[b]) over the finite costs;
+        that sequence is rolled out and costed inside the launch.  `std`,
+        `smooth`, `seed`, `sample_offset`, `active`: as `shoot`.
+        `temperature`: a float or [B], in cost units, > 0 (a trajectory whose
+        temperature is not is treated as one without a finite candidate).
+
+        `iterations` launches follow each other on private copies of U and Z:
+        iteration k draws with `sample_offset` + k B S and takes the weighted
+        rows of the trajectories it `improved` (a device-side select, no host
+        synchronisation), so the call is never worse than its start.
+
+        Returns an object with `J` [B][S], `best` [B] int32, `J_best` [B],
+        `W` [B][S], `J_w` [B] (the cost of the weighted sequence; +inf with
+        best == -1), `ess` [B] = 1 / sum_s W^2, `improved` [B] bool =
+        isfinite(J_w) & (J_w <= J[:, 0]) - those of the LAST iteration; of a
+        masked trajectory NaN / -1 / False - and `J_trace`
+        [iterations + 1][B]: the base's cost, then the cost carried after each
+        iteration.
+
+        `adopt=True`: `U` and `Z` take the carried rows in place - the
+        weighted ones where an iteration improved, their own elsewhere - and
+        the controller state is re-armed, as `shoot` does.  `adopt=False`:
+        nothing of the solver is touched; the object also has `Z` and `U`, the
+        carried rows.  `events`: a (start, stop) pair for the dispatch, with
+        one iteration only.
+
+        Refused while a reference or per-trajectory cost weights are set, as
+        `shoot` is."""
+        self._need_sample_problem("mppi")
+        if self.reference is not None:
+            raise _native.NativeError(
+                "mppi costs its candidates under ONE goal per trajectory; "
+                "with a reference (set_reference) the line search's objective "
+                "is another one")
+        if self.batch_weights is not None:
+            raise _native.NativeError(
+                "mppi costs its candidates under the shared Q, Q_term, R; "
+                "with per-trajectory weights (set_batch_weights) the line "
+                "search's objective is another one")
+        B, N, n, m = self.B, self.N, self.n, self.m
+        S, K = int(samples), int(iterations)
+        if S < 1:
+            raise _native.NativeError("mppi: %d samples" % S)
+        if K < 1:
+            raise _native.NativeError("mppi: %d iterations" % K)
+        if events is not None and K > 1:
+            raise _native.NativeError(
+                "mppi: events time ONE dispatch, %d iterations are %d" % (K, K))
+        a_std = self._action_std(std, "mppi")
+        lam = torch.as_tensor(temperature, dtype=self.dtype,
+                              device=self.device)
+        if lam.dim() == 0:
+            lam = lam.repeat(B)
+        if tuple(lam.shape) != (B,):
+            raise _native.NativeError(
+                "mppi: temperature has shape %s, expected a scalar or (%d,)"
+                % (tuple(lam.shape), B))
+        lam = lam.contiguous()
+        self._check_active("mppi", active)
+        masked = active is not None
+        p = _native.ptr
+        U, Z = self.U.clone(), self.Z.clone()
+        J_trace = torch.empty(K + 1, B, dtype=self.dtype, device=self.device)
+        for k in range(K):
+            out = types.SimpleNamespace(
+                J=self._out(masked, B, S),
+                best=self._out(masked, B, dtype=torch.int32, fill=-1),
+                J_best=self._out(masked, B), W=self._out(masked, B, S),
+                J_w=self._out(masked, B))
+            # (rows without a weighted sequence are never selected)
+            Zw, Uw = self._out(False, B, N + 1, n), self._out(False, B, N, m)
+            self._launch(events, self._problem_call, "pddp_mppi", B, N, S,
+                         p(self.z0), p(U), p(self.u_min), p(self.u_max),
+                         p(a_std), p(lam), float(smooth), int(seed),
+                         int(sample_offset) + k * B * S, p(active), p(out.J),
+                         p(out.best), p(out.J_best), p(out.W), p(out.J_w),
+                         p(Zw), p(Uw), self._s())
+            out.improved = torch.isfinite(out.J_w) & (out.J_w <= out.J[:, 0])
+            if k == 0:
+                J_trace[0] = out.J[:, 0]
+            take = out.improved.reshape(B, 1, 1)
+            U, Z = torch.where(take, Uw, U), torch.where(take, Zw, Z)
+            J_trace[k + 1] = torch.where(out.improved, out.J_w, J_trace[k])
+        out.ess = 1.0 / (out.W * out.W).sum(dim=1)
+        out.J_trace = J_trace
+        if not adopt:
+            out.Z, out.U = Z, U
+            return out
+        self.U.copy_(U)
+        self.Z.copy_(Z)
+        self.reset_controller_state()
+        return out
+
     def _plant_table(self, what, params, x_goal, u_goal):
         """[B][BATCH_ROW] plant rows of a trial whose fields are [B][.]: a
         field not given is `batch_table`'s if a table is set, else the shared
