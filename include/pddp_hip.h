@@ -576,6 +576,101 @@ int pddp_mppi_batch_f64(const pddp_problem* problem, const double* table,
                         double* J_w, double* Z_out, double* U_out,
                         void* stream);
 
+/* ---- a receding-horizon MPPI trial, every control step inside ONE launch:
+ * plan by K iterations of pddp_mppi_*'s law around the plan U, apply the first
+ * action to the plant, observe, shift the plan (csrc/mppi_trial.hip; the
+ * reference has no counterpart).  Trajectory b is live when active is NULL or
+ * active[b] != 0; control step c runs over t0 .. t0 + count - 1 of TT:
+ *
+ *   1. plan.  For k = 0 .. K-1: pddp_mppi_*'s law above, word for word, from
+ *      x_0 = z0[b] under the controller's model (the shared problem with row b
+ *      of `table` written over it), the base U[b], candidate (b, s) rollout
+ *        r = cand_offset + (c K + k) iter_stride + b S + s          (uint64)
+ *      of stream 2: Jc, best, J_best, eta, the weights, Uw (into U_work) and
+ *      J_w.  J0_log[b][c][k] = Jc[b][0]; Jw_log[b][c][k] = J_w;
+ *      took = isfinite(J_w) && J_w <= Jc[b][0]; where it holds U[b] = Uw, else
+ *      U[b] stays (no finite candidate, or lam[b] not positive: J_w = +inf).
+ *      ess_log[b][c] = eta^2 / sum_s w_s^2 of the last iteration (w and w^2
+ *      summed together, in eta's order), 0 without a finite candidate;
+ *      plan_log[b][c] = U[b] after the K iterations.
+ *   2. apply (pddp_mpc_advance_noisy_*'s steps 2 - 4).  x = x_true[b] with
+ *      v_std, else z0[b]; u = clamp(U[b][0]); Xlog[b][c] = x; Ulog[b][c] = u;
+ *      Jcl[b] (read if c > 0, else 0) += l(x, u) under the plant row's goals;
+ *      x' = f_plant(x, u) + disturbance[b][c], then with w_std
+ *      x' = fma(w_std, w(seed, rollout_offset + b, step_offset + c, stream 0),
+ *      x') per component; at c == TT-1: Xlog[b][TT] = x', Jcl[b] += l_f(x').
+ *   3. observe.  With v_std: x_true[b] = x', y' = fma(v_std, v(seed,
+ *      rollout_offset + b, step_offset + c + 1, stream 1), x'),
+ *      Ylog[b][c+1] = y'.  z0[b] = y', or x' without v_std.
+ *   4. shift.  U[b][i] = U[b][i+1], the last row repeated: plain copies of
+ *      unclamped words.
+ *
+ * After the last control step of the launch Z[b] is the rollout of the shifted
+ * U[b], clamped, from z0[b] under the controller's model (the advance's step
+ * 6).  No iLQR controller state is an argument.
+ *
+ * iter_stride: a solver passes B S, so that iteration (c, k) draws what
+ * pddp_mppi_* draws with sample_offset = cand_offset + (c K + k) B S.  A run
+ * of trajectories b0.. alone passes the ORIGINAL B S, cand_offset + b0 S and
+ * rollout_offset + b0 and gets the same bits; so do count control steps in
+ * one launch and in several (t0 advanced; z0, U, x_true, Jcl carried).
+ *
+ * Arguments, in this order:
+ *   problem, table, plant     [B][PDDP_BATCH_ROW] or NULL each (plant NULL: the
+ *                             controller's model)
+ *   B, N, S, K, TT, t0, count
+ *   z0 [B][n]                 in: what the controller sees at step t0; out: at
+ *                             step t0 + count
+ *   U [B][N][m]               in: the plan (unclamped words); out: shifted
+ *   Z [B][N+1][n]             out, written once
+ *   U_work [B][N][m]          workspace: the weighted sequence of an iteration
+ *                             (S > 256: also the running sum of a lane's turns)
+ *   u_min, u_max, a_std [m], lam [B], smooth      pddp_mppi_*'s
+ *   seed                      ONE key: stream 2 the candidates, 0 / 1 the noises
+ *   cand_offset, iter_stride  (uint64)
+ *   disturbance [B][TT][n], w_std [n], v_std [n]  nullable each
+ *   rollout_offset (uint64), step_offset, x_true [B][n]
+ *                             pddp_mpc_advance_noisy_*'s, same meaning
+ *   active [B]                nullable: nothing of a skipped trajectory is read
+ *                             or written
+ *   Jc, log_costs             Jc workspace [B][S]; log_costs != 0:
+ *                             [B][TT][K][S], every iteration's costs kept
+ *   Xlog [B][TT+1][n], Ulog [B][TT][m], Jcl [B]
+ *   Ylog [B][TT+1][n]         nullable, written with v_std only (rows c + 1)
+ *   J0_log [B][TT][K], Jw_log [B][TT][K], ess_log [B][TT],
+ *   plan_log [B][TT][N][m]    nullable each
+ *   stream
+ *
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY.
+ * PDDP_E_BADARG: pddp_mppi_*'s list (a null problem, z0, U, a_std, lam or Jc;
+ * non-positive B, N or S; B S > 0x7fffffff; smooth outside [0, 1) or NaN);
+ * K < 1, TT < 1, t0 < 0, count < 1, t0 + count > TT; a null Z, U_work, Xlog,
+ * Ulog or Jcl; U_work == U; v_std without x_true; step_offset < 0 or
+ * step_offset + TT beyond an int.  PDDP_E_UNSUPPORTED: any other encoding.  All
+ * before any HIP call. */
+int pddp_mppi_trial_f32(
+    const pddp_problem* problem, const float* table, const float* plant, int B,
+    int N, int S, int K, int TT, int t0, int count, float* z0, float* U,
+    float* Z, float* U_work, const float* u_min, const float* u_max,
+    const float* a_std, const float* lam, double smooth, uint64_t seed,
+    uint64_t cand_offset, uint64_t iter_stride, const float* disturbance,
+    const float* w_std, const float* v_std, uint64_t rollout_offset,
+    int step_offset, float* x_true, const uint8_t* active, float* Jc,
+    int log_costs, float* Xlog, float* Ulog, float* Jcl, float* Ylog,
+    float* J0_log, float* Jw_log, float* ess_log, float* plan_log,
+    void* stream);
+int pddp_mppi_trial_f64(
+    const pddp_problem* problem, const double* table, const double* plant,
+    int B, int N, int S, int K, int TT, int t0, int count, double* z0,
+    double* U, double* Z, double* U_work, const double* u_min,
+    const double* u_max, const double* a_std, const double* lam, double smooth,
+    uint64_t seed, uint64_t cand_offset, uint64_t iter_stride,
+    const double* disturbance, const double* w_std, const double* v_std,
+    uint64_t rollout_offset, int step_offset, double* x_true,
+    const uint8_t* active, double* Jc, int log_costs, double* Xlog,
+    double* Ulog, double* Jcl, double* Ylog, double* J0_log, double* Jw_log,
+    double* ess_log, double* plan_log, void* stream);
+
 /* ---- pddp.py:209-245 _apply_controller(mpc=True) with ilqr.py:355-362
  * forward(mpc=True) as the controller, batched and with the sample models as
  * the plant: the hand-over between two control steps of a receding-horizon

@@ -102,6 +102,12 @@ _SIGS = {
     "pddp_shoot_draws": [c_int] * 4 + [c_uint64, c_uint64, _P, _P],
     "pddp_mppi": [_P] + _MPPI,
     "pddp_mppi_batch": [_P, _P] + _MPPI,
+    # (a whole MPPI trial: problem, table, plant; B N S K TT t0 count; z0 ..
+    # lam; smooth, seed, cand_offset, iter_stride; disturbance, w_std, v_std;
+    # rollout_offset, step_offset; x_true, active, Jc; log_costs; the logs)
+    "pddp_mppi_trial": [_P] * 3 + [c_int] * 7 + [_P] * 8 +
+                       [c_double] + [c_uint64] * 3 + [_P] * 3 +
+                       [c_uint64, c_int] + [_P] * 3 + [c_int] + [_P] * 9,
     "pddp_mpc_advance": [_P, _P] + _STEP + _STEP_OUT,
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
@@ -178,7 +184,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_closed_loop_noisy", "pddp_closed_loop_draws",
           "pddp_closed_loop_track",
           "pddp_shoot", "pddp_shoot_batch", "pddp_shoot_draws",
-          "pddp_mppi", "pddp_mppi_batch",
+          "pddp_mppi", "pddp_mppi_batch", "pddp_mppi_trial",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
           "pddp_mpc_advance_noisy", "pddp_mpc_observe",

@@ -1264,16 +1264,7 @@ class ILQRSolver(object):
         Refused while a reference or per-trajectory cost weights are set, as
         `shoot` is."""
         self._need_sample_problem("mppi")
-        if self.reference is not None:
-            raise _native.NativeError(
-                "mppi costs its candidates under ONE goal per trajectory; "
-                "with a reference (set_reference) the line search's objective "
-                "is another one")
-        if self.batch_weights is not None:
-            raise _native.NativeError(
-                "mppi costs its candidates under the shared Q, Q_term, R; "
-                "with per-trajectory weights (set_batch_weights) the line "
-                "search's objective is another one")
+        self._one_sampled_objective("mppi")
         B, N, n, m = self.B, self.N, self.n, self.m
         S, K = int(samples), int(iterations)
         if S < 1:
@@ -1284,15 +1275,7 @@ class ILQRSolver(object):
             raise _native.NativeError(
                 "mppi: events time ONE dispatch, %d iterations are %d" % (K, K))
         a_std = self._action_std(std, "mppi")
-        lam = torch.as_tensor(temperature, dtype=self.dtype,
-                              device=self.device)
-        if lam.dim() == 0:
-            lam = lam.repeat(B)
-        if tuple(lam.shape) != (B,):
-            raise _native.NativeError(
-                "mppi: temperature has shape %s, expected a scalar or (%d,)"
-                % (tuple(lam.shape), B))
-        lam = lam.contiguous()
+        lam = self._temperature("mppi", temperature)
         self._check_active("mppi", active)
         masked = active is not None
         p = _native.ptr
@@ -1328,6 +1311,123 @@ class ILQRSolver(object):
         self.reset_controller_state()
         return out
 
+    def _one_sampled_objective(self, what):
+        """`mppi`'s and `mppi_closed_loop`'s refusal while a reference or
+        per-trajectory cost weights are set."""
+        if self.reference is not None:
+            raise _native.NativeError(
+                "%s costs its candidates under ONE goal per trajectory; "
+                "with a reference (set_reference) the line search's objective "
+                "is another one" % what)
+        if self.batch_weights is not None:
+            raise _native.NativeError(
+                "%s costs its candidates under the shared Q, Q_term, R; "
+                "with per-trajectory weights (set_batch_weights) the line "
+                "search's objective is another one" % what)
+
+    def _temperature(self, what, temperature):
+        """[B] device vector of a temperature given as a float or [B]."""
+        lam = torch.as_tensor(temperature, dtype=self.dtype,
+                              device=self.device)
+        if lam.dim() == 0:
+            lam = lam.repeat(self.B)
+        if tuple(lam.shape) != (self.B,):
+            raise _native.NativeError(
+                "%s: temperature has shape %s, expected a scalar or (%d,)"
+                % (what, tuple(lam.shape), self.B))
+        return lam.contiguous()
+
+    @_on_device
+    def mppi_closed_loop(self, steps, samples, std, temperature, iterations=1,
+                         smooth=0.0, seed=0, candidate_offset=0, z0=None,
+                         params=None, x_goal=None, u_goal=None,
+                         disturbance=None, process_std=None, obs_std=None,
+                         sample_offset=0, step_offset=0, active=None,
+                         log_costs=False, events=None):
+        """A receding-horizon MPPI trial of every trajectory on its own plant,
+        all `steps` control steps in ONE launch (pddp_mppi_trial_*,
+        csrc/mppi_trial.hip): per control step `iterations` iterations of
+        `mppi`'s law around the plan `U` from what the controller sees - an
+        iteration's weighted sequence replaces the plan where it `took`,
+        isfinite(J_w) & (J_w <= J[:, 0]) - then clamp(U[b][0]) is applied to
+        plant b, the trial is logged, the next state observed and the plan
+        shifted by one (the last row repeated).  `samples`, `std`,
+        `temperature`, `smooth`: as `mppi`.  Iteration k of control step c
+        draws its candidates as `mppi(seed=, sample_offset=candidate_offset +
+        (c iterations + k) B samples)` does.
+
+        The plant (`params`, `x_goal`, `u_goal`), `disturbance`, the noise
+        (`process_std`, `obs_std` with `seed`, `sample_offset`, `step_offset`),
+        the start (`z0`; with `obs_std` the TRUE start, `x_true` and the first
+        observation), continuation with `z0=None` and `active` are
+        `mpc_closed_loop`'s, word for word: an MPPI trial and an iLQR trial
+        with the same `seed`, `sample_offset` and `step_offset` run under the
+        same normals (`seed` also keys the candidates, on a stream of their
+        own).
+
+        Returns an object with `X` [B][steps+1][n], `U` [B][steps][m], `J`
+        [B], `Y` [B][steps+1][n] (None without `obs_std`) as
+        `mpc_closed_loop`; `J0`, `J_w` [B][steps][iterations]: the cost of the
+        plan and of the weighted sequence in every iteration; `took` (bool,
+        from the two); `ess` [B][steps]: the effective sample size of each
+        step's last iteration (0 without a finite candidate); `plans`
+        [B][steps][N][m]: the plan each step applied the first row of; with
+        `log_costs` `Jc` [B][steps][iterations][samples], else None.  Of a
+        masked trajectory NaN / False.  No host synchronisation; `events`: a
+        (start, stop) pair attached to the one launch.
+
+        Afterwards `z0` is what the controller sees at step `steps`, `U` the
+        shifted plan and `Z` its rollout, all in place, and the controller
+        state is re-armed: `rounds()` polishes with iLQR, a second call with
+        `z0=None`, `step_offset=steps` and `candidate_offset` advanced by
+        steps * iterations * B * samples continues the trial.
+
+        Refused while a reference or per-trajectory cost weights are set, as
+        `mppi` is."""
+        what = "mppi_closed_loop"
+        self._need_sample_problem(what)
+        self._one_sampled_objective(what)
+        B, N, n, m = self.B, self.N, self.n, self.m
+        T, S, K = int(steps), int(samples), int(iterations)
+        if S < 1:
+            raise _native.NativeError("%s: %d samples" % (what, S))
+        if K < 1:
+            raise _native.NativeError("%s: %d iterations" % (what, K))
+        if T < 1:
+            raise _native.NativeError("%s: %d steps" % (what, T))
+        a_std = self._action_std(std, what)
+        lam = self._temperature(what, temperature)
+        step_offset, w_std, v_std, z0, disturbance = self._trial_inputs(
+            what, T, z0, disturbance, process_std, obs_std, step_offset,
+            active)
+        plant = self._plant_table(what, params, x_goal, u_goal)
+        masked = active is not None
+        out = types.SimpleNamespace(
+            X=self._out(masked, B, T + 1, n), U=self._out(masked, B, T, m),
+            J=self._out(masked, B), Y=None, J0=self._out(masked, B, T, K),
+            J_w=self._out(masked, B, T, K), ess=self._out(masked, B, T),
+            plans=self._out(masked, B, T, N, m),
+            Jc=self._out(masked, B, T, K, S) if log_costs else None)
+        x_true = self._trial_start(T, z0, v_std, seed, sample_offset,
+                                   step_offset, active, out)
+        U_work = self._out(False, B, N, m)
+        Jc = out.Jc if log_costs else self._out(False, B, S)
+        p = _native.ptr
+        self._launch(
+            events, _native.call, "pddp_mppi_trial", self.dtype, self._pp,
+            p(self.batch_table), p(plant), B, N, S, K, T, 0, T, p(self.z0),
+            p(self.U), p(self.Z), p(U_work), p(self.u_min), p(self.u_max),
+            p(a_std), p(lam), float(smooth), int(seed), int(candidate_offset),
+            B * S, p(disturbance), p(w_std), p(v_std), int(sample_offset),
+            step_offset, p(x_true), p(active), p(Jc), int(bool(log_costs)),
+            p(out.X), p(out.U), p(out.J), p(out.Y), p(out.J0), p(out.J_w),
+            p(out.ess), p(out.plans), self._s())
+        out.took = torch.isfinite(out.J_w) & (out.J_w <= out.J0)
+        # (the plan is a new nominal: records at the next round's start)
+        self.reset_controller_state()
+        self._derivs_due = True
+        return out
+
     def _plant_table(self, what, params, x_goal, u_goal):
         """[B][BATCH_ROW] plant rows of a trial whose fields are [B][.]: a
         field not given is `batch_table`'s if a table is set, else the shared
@@ -1336,6 +1436,72 @@ class ILQRSolver(object):
             return None
         return self._write_fields(what, self._base_table().clone(),
                                   self._row_blocks(params, x_goal, u_goal))
+
+    def _trial_inputs(self, what, T, z0, disturbance, process_std, obs_std,
+                      step_offset, active):
+        """The checks a trial's entry (`mpc_closed_loop`, `mppi_closed_loop`)
+        makes on its start, disturbance, noise levels, step offset and mask:
+        (step_offset, w_std, v_std, z0, disturbance) as the launches take
+        them."""
+        B, n = self.B, self.n
+        if isinstance(step_offset, bool) or \
+                not isinstance(step_offset, numbers.Integral) or \
+                step_offset < 0:
+            raise _native.NativeError(
+                "%s: step_offset is %r, expected an integer >= 0"
+                % (what, step_offset))
+        step_offset = int(step_offset)
+        w_std = self._noise_std("process_std", process_std, what)
+        v_std = self._noise_std("obs_std", obs_std, what)
+        opts = dict(dtype=self.dtype, device=self.device)
+        if z0 is not None:
+            z0 = torch.as_tensor(z0).to(**opts)
+            if tuple(z0.shape) != (B, n):
+                raise _native.NativeError(
+                    "%s: z0 has shape %s, expected (%d, %d)" % (
+                        what, tuple(z0.shape), B, n))
+        if disturbance is not None:
+            disturbance = torch.as_tensor(disturbance).to(**opts).contiguous()
+            if tuple(disturbance.shape) != (B, T, n):
+                raise _native.NativeError(
+                    "%s: disturbance has shape %s, expected "
+                    "(%d, %d, %d)" % (what, tuple(disturbance.shape), B, T, n))
+        self._check_active(what, active)
+        return step_offset, w_std, v_std, z0, disturbance
+
+    def _trial_start(self, T, z0, v_std, seed, sample_offset, step_offset,
+                     active, out):
+        """The start of a trial: `set_nominal` from the start state - with
+        `v_std` from the first observation of the true start, or, continuing
+        with z0=None, from the observation held - and `out.Y` with its row 0.
+        Returns `x_true` (None without `v_std`), which the solver keeps."""
+        B, n = self.B, self.n
+        masked = active is not None
+        p = _native.ptr
+        x_true = None
+        if v_std is None:
+            self.set_nominal(self.z0 if z0 is None else z0, self.U)
+        elif z0 is None and self.x_true is not None:
+            # the trial goes on: the plant at x_true, the controller at the
+            # observation it holds
+            x_true = self.x_true
+            self.set_nominal(self.z0, self.U)
+        else:
+            # the true start, and the first observation under the law of every
+            # later one (a skipped trajectory keeps its start)
+            x_true = (self.z0 if z0 is None else z0).clone(
+                memory_format=torch.contiguous_format)
+            y0 = x_true.clone()
+            _native.call("pddp_mpc_observe", self.dtype, B, n, p(x_true),
+                         p(v_std), int(seed), int(sample_offset), step_offset,
+                         p(active), p(y0), self._s())
+            self.set_nominal(y0, self.U)
+        self.x_true = x_true  # (set_nominal dropped it)
+        if x_true is not None:
+            out.Y = self._out(masked, B, T + 1, n)
+            out.Y[:, 0] = self.z0 if not masked else torch.where(
+                active.bool().unsqueeze(1), self.z0, out.Y[:, 0])
+        return x_true
 
     @_on_device
     def mpc_closed_loop(self, steps, rounds_per_step, z0=None, params=None,
@@ -1427,29 +1593,9 @@ class ILQRSolver(object):
         if T < 1 or R < 1:
             raise _native.NativeError(
                 "mpc_closed_loop: %d steps of %d rounds" % (T, R))
-        if isinstance(step_offset, bool) or \
-                not isinstance(step_offset, numbers.Integral) or \
-                step_offset < 0:
-            raise _native.NativeError(
-                "mpc_closed_loop: step_offset is %r, expected an integer >= 0"
-                % (step_offset,))
-        step_offset = int(step_offset)
-        w_std = self._noise_std("process_std", process_std, "mpc_closed_loop")
-        v_std = self._noise_std("obs_std", obs_std, "mpc_closed_loop")
-        opts = dict(dtype=self.dtype, device=self.device)
-        if z0 is not None:
-            z0 = torch.as_tensor(z0).to(**opts)
-            if tuple(z0.shape) != (B, n):
-                raise _native.NativeError(
-                    "mpc_closed_loop: z0 has shape %s, expected (%d, %d)" % (
-                        tuple(z0.shape), B, n))
-        if disturbance is not None:
-            disturbance = torch.as_tensor(disturbance).to(**opts).contiguous()
-            if tuple(disturbance.shape) != (B, T, n):
-                raise _native.NativeError(
-                    "mpc_closed_loop: disturbance has shape %s, expected "
-                    "(%d, %d, %d)" % (tuple(disturbance.shape), B, T, n))
-        self._check_active("mpc_closed_loop", active)
+        step_offset, w_std, v_std, z0, disturbance = self._trial_inputs(
+            "mpc_closed_loop", T, z0, disturbance, process_std, obs_std,
+            step_offset, active)
         plant = self._plant_table("mpc_closed_loop", params, x_goal, u_goal)
         masked = active is not None
         out = types.SimpleNamespace(
@@ -1462,29 +1608,8 @@ class ILQRSolver(object):
         if events is not None:
             _native.check(record(events[0], self._s()), "pddp_event_record")
         p = _native.ptr
-        x_true = None
-        if v_std is None:
-            self.set_nominal(self.z0 if z0 is None else z0, self.U)
-        elif z0 is None and self.x_true is not None:
-            # the trial goes on: the plant at x_true, the controller at the
-            # observation it holds
-            x_true = self.x_true
-            self.set_nominal(self.z0, self.U)
-        else:
-            # the true start, and the first observation under the law of every
-            # later one (a skipped trajectory keeps its start)
-            x_true = (self.z0 if z0 is None else z0).clone(
-                memory_format=torch.contiguous_format)
-            y0 = x_true.clone()
-            _native.call("pddp_mpc_observe", self.dtype, B, n, p(x_true),
-                         p(v_std), int(seed), int(sample_offset), step_offset,
-                         p(active), p(y0), self._s())
-            self.set_nominal(y0, self.U)
-        self.x_true = x_true  # (set_nominal dropped it)
-        if x_true is not None:
-            out.Y = self._out(masked, B, T + 1, n)
-            out.Y[:, 0] = self.z0 if not masked else torch.where(
-                active.bool().unsqueeze(1), self.z0, out.Y[:, 0])
+        x_true = self._trial_start(T, z0, v_std, seed, sample_offset,
+                                   step_offset, active, out)
         if masked:  # (the skipped ones take no part in the rounds either)
             self.active.mul_(active)
             self.fresh.mul_(active)
