@@ -671,6 +671,128 @@ int pddp_mppi_trial_f64(
     double* Ulog, double* Jcl, double* Ylog, double* J0_log, double* Jw_log,
     double* ess_log, double* plan_log, void* stream);
 
+/* ---- the sampling planners under the line search's objective: pddp_shoot_*,
+ * pddp_mppi_* and pddp_mppi_trial_* above along a reference (a goal per time
+ * step, pddp_line_search_track_*) and / or under per-trajectory cost weights
+ * (pddp_line_search_weighted_*) (csrc/sampled_goals.hip; the reference has no
+ * counterpart).  Nothing changes in how candidates are drawn, clamped,
+ * selected, weighted or summed: the three laws above hold word for word.  Only
+ * the cost every rollout is summed under changes - the candidates', the
+ * winner's second pass in shoot, the weighted sequence's in mppi and the trial:
+ *
+ *   P_b = the shared problem, the parameters of row b of `table` where one is
+ *         given (with a reference the table's goal fields are NOT read), then,
+ *         where weights are given, row b of `weights` [B][PDDP_WEIGHT_ROW]
+ *         written over the diagonals of Q, Q_term, R
+ *   J += l(x_t, u_t)  under row min(ref_t0 + t, ref_len - 1) of `ref`
+ *                     [B][ref_len][PDDP_REF_ROW], trajectory b, t = 0 .. N-1
+ *   J += l_f(x_N)     under row min(ref_t0 + N, ref_len - 1), x_goal only
+ *
+ * Without a reference the goals are the table's or the shared problem's.  The
+ * cost is evaluated under the full mask: a weight may make a row live that
+ * the shared Q leaves dead.  The S candidates of a trajectory share its
+ * reference and its weights row.  With every reference row equal to the
+ * table's goals and every weights row equal to the shared diagonals the
+ * results agree with the _batch siblings' to rounding (another kernel), not to
+ * the bit.
+ *
+ * Leading arguments, then the sibling's parameter list unchanged; `table` may
+ * be NULL:
+ *   _track_            (problem, table, ref, ref_len, ref_t0, ...)
+ *   _weighted_         (problem, table, weights, ...)
+ *   _track_weighted_   (problem, table, ref, ref_len, ref_t0, weights, ...)
+ *
+ * pddp_mppi_trial_goals_* takes pddp_mppi_trial_*'s parameters with `ref,
+ * ref_len, ref_t0, weights` after `plant`; both additions are nullable, at
+ * least one of them is given.  Control step c (absolute in TT, as for the
+ * noise) plans under the window that starts at row min(ref_t0 + c,
+ * ref_len - 1).  The applied step is logged as pddp_mpc_advance_track_* logs
+ * it, on the common yardstick: Jcl[b] += l(x, u) under row ref_t0 + c and the
+ * SHARED Q, R; at c == TT-1 l_f(x') under row ref_t0 + c + 1 (both clamped)
+ * and the shared Q_term; with a reference the plant row supplies parameters
+ * only.  The weights affect planning only.  The final Z reads no goal.
+ *
+ * PDDP_E_BADARG: everything the sibling refuses; a null `weights` where the
+ * name promises weights; a null `ref`, ref_len < 1 or ref_t0 < 0 where it
+ * promises a reference; the trial: neither a reference nor weights, or (with
+ * a reference) ref_len < 1, ref_t0 < 0, ref_t0 + TT beyond an int.  All before
+ * any HIP call. */
+#define PDDP_SHOOT_REST(T)                                                     \
+  int B, int N, int S, const T* z0, const T* U, const T* u_min,                \
+      const T* u_max, const T* a_std, double smooth, uint64_t seed,            \
+      uint64_t sample_offset, const uint8_t* active, T* Jc, int32_t* best,     \
+      T* J_best, T* Z_out, T* U_out, void* stream
+#define PDDP_MPPI_REST(T)                                                      \
+  int B, int N, int S, const T* z0, const T* U, const T* u_min,                \
+      const T* u_max, const T* a_std, const T* lam, double smooth,             \
+      uint64_t seed, uint64_t sample_offset, const uint8_t* active, T* Jc,     \
+      int32_t* best, T* J_best, T* W, T* J_w, T* Z_out, T* U_out, void* stream
+int pddp_shoot_track_f32(const pddp_problem* problem, const float* table,
+                         const float* ref, int ref_len, int ref_t0,
+                         PDDP_SHOOT_REST(float));
+int pddp_shoot_track_f64(const pddp_problem* problem, const double* table,
+                         const double* ref, int ref_len, int ref_t0,
+                         PDDP_SHOOT_REST(double));
+int pddp_shoot_weighted_f32(const pddp_problem* problem, const float* table,
+                            const float* weights, PDDP_SHOOT_REST(float));
+int pddp_shoot_weighted_f64(const pddp_problem* problem, const double* table,
+                            const double* weights, PDDP_SHOOT_REST(double));
+int pddp_shoot_track_weighted_f32(const pddp_problem* problem,
+                                  const float* table, const float* ref,
+                                  int ref_len, int ref_t0,
+                                  const float* weights,
+                                  PDDP_SHOOT_REST(float));
+int pddp_shoot_track_weighted_f64(const pddp_problem* problem,
+                                  const double* table, const double* ref,
+                                  int ref_len, int ref_t0,
+                                  const double* weights,
+                                  PDDP_SHOOT_REST(double));
+int pddp_mppi_track_f32(const pddp_problem* problem, const float* table,
+                        const float* ref, int ref_len, int ref_t0,
+                        PDDP_MPPI_REST(float));
+int pddp_mppi_track_f64(const pddp_problem* problem, const double* table,
+                        const double* ref, int ref_len, int ref_t0,
+                        PDDP_MPPI_REST(double));
+int pddp_mppi_weighted_f32(const pddp_problem* problem, const float* table,
+                           const float* weights, PDDP_MPPI_REST(float));
+int pddp_mppi_weighted_f64(const pddp_problem* problem, const double* table,
+                           const double* weights, PDDP_MPPI_REST(double));
+int pddp_mppi_track_weighted_f32(const pddp_problem* problem,
+                                 const float* table, const float* ref,
+                                 int ref_len, int ref_t0, const float* weights,
+                                 PDDP_MPPI_REST(float));
+int pddp_mppi_track_weighted_f64(const pddp_problem* problem,
+                                 const double* table, const double* ref,
+                                 int ref_len, int ref_t0,
+                                 const double* weights,
+                                 PDDP_MPPI_REST(double));
+#undef PDDP_MPPI_REST
+#undef PDDP_SHOOT_REST
+int pddp_mppi_trial_goals_f32(
+    const pddp_problem* problem, const float* table, const float* plant,
+    const float* ref, int ref_len, int ref_t0, const float* weights, int B,
+    int N, int S, int K, int TT, int t0, int count, float* z0, float* U,
+    float* Z, float* U_work, const float* u_min, const float* u_max,
+    const float* a_std, const float* lam, double smooth, uint64_t seed,
+    uint64_t cand_offset, uint64_t iter_stride, const float* disturbance,
+    const float* w_std, const float* v_std, uint64_t rollout_offset,
+    int step_offset, float* x_true, const uint8_t* active, float* Jc,
+    int log_costs, float* Xlog, float* Ulog, float* Jcl, float* Ylog,
+    float* J0_log, float* Jw_log, float* ess_log, float* plan_log,
+    void* stream);
+int pddp_mppi_trial_goals_f64(
+    const pddp_problem* problem, const double* table, const double* plant,
+    const double* ref, int ref_len, int ref_t0, const double* weights, int B,
+    int N, int S, int K, int TT, int t0, int count, double* z0, double* U,
+    double* Z, double* U_work, const double* u_min, const double* u_max,
+    const double* a_std, const double* lam, double smooth, uint64_t seed,
+    uint64_t cand_offset, uint64_t iter_stride, const double* disturbance,
+    const double* w_std, const double* v_std, uint64_t rollout_offset,
+    int step_offset, double* x_true, const uint8_t* active, double* Jc,
+    int log_costs, double* Xlog, double* Ulog, double* Jcl, double* Ylog,
+    double* J0_log, double* Jw_log, double* ess_log, double* plan_log,
+    void* stream);
+
 /* ---- pddp.py:209-245 _apply_controller(mpc=True) with ilqr.py:355-362
  * forward(mpc=True) as the controller, batched and with the sample models as
  * the plant: the hand-over between two control steps of a receding-horizon

@@ -108,7 +108,19 @@ _SIGS = {
     "pddp_mppi_trial": [_P] * 3 + [c_int] * 7 + [_P] * 8 +
                        [c_double] + [c_uint64] * 3 + [_P] * 3 +
                        [c_uint64, c_int] + [_P] * 3 + [c_int] + [_P] * 9,
-    "pddp_mpc_advance": [_P, _P] + _STEP + _STEP_OUT,
+    # (the planners under the line search's objective: problem, table, then
+    # the window and / or the weights, then the sibling's list; the trial
+    # takes both, nullable each, after the plant)
+    "pddp_shoot_track": [_P, _P] + _REF + _SHOOT,
+    "pddp_shoot_weighted": [_P, _P, _P] + _SHOOT,
+    "pddp_shoot_track_weighted": [_P, _P] + _REF + [_P] + _SHOOT,
+    "pddp_mppi_track": [_P, _P] + _REF + _MPPI,
+    "pddp_mppi_weighted": [_P, _P, _P] + _MPPI,
+    "pddp_mppi_track_weighted": [_P, _P] + _REF + [_P] + _MPPI,
+    "pddp_mppi_trial_goals": [_P] * 3 + _REF + [_P] + [c_int] * 7 + [_P] * 8 +
+                             [c_double] + [c_uint64] * 3 + [_P] * 3 +
+                             [c_uint64, c_int] + [_P] * 3 + [c_int] + [_P] * 9,
+    "pddp_mpc_advance":[_P, _P] + _STEP + _STEP_OUT,
     "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
     "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
     "pddp_mpc_advance_track": [_P, _P] + _REF + _STEP + _STEP_OUT,
@@ -185,6 +197,9 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_closed_loop_track",
           "pddp_shoot", "pddp_shoot_batch", "pddp_shoot_draws",
           "pddp_mppi", "pddp_mppi_batch", "pddp_mppi_trial",
+          "pddp_shoot_track", "pddp_shoot_weighted",
+          "pddp_shoot_track_weighted", "pddp_mppi_track", "pddp_mppi_weighted",
+          "pddp_mppi_track_weighted", "pddp_mppi_trial_goals",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
           "pddp_mpc_advance_noisy", "pddp_mpc_observe",

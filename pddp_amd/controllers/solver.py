@@ -1141,7 +1141,7 @@ class ILQRSolver(object):
 
     @_on_device
     def shoot(self, samples, std, smooth=0.0, seed=0, sample_offset=0,
-              active=None, adopt=True, events=None):
+              active=None, adopt=True, events=None, objective="shared"):
         """Sampled shooting around the current action sequence
         (pddp_shoot_*, csrc/shoot.hip): S = `samples` candidates per
         trajectory, candidate 0 the sequence `U` itself, candidate s >= 1
@@ -1170,19 +1170,18 @@ class ILQRSolver(object):
         is none).  `events`: a (start, stop) pair for the dispatch.
 
         While a reference (`set_reference`) or per-trajectory cost weights
-        (`set_batch_weights`) are set the call is refused: the candidates
-        would be costed under another objective than the line search's."""
+        (`set_batch_weights`) are set the call is refused under
+        `objective="shared"` (default): the candidates would be costed under
+        another objective than the line search's.  `objective="search"`
+        costs every candidate - and the winner's second pass - under whatever
+        the line search currently uses (pddp_shoot_track_*, _weighted_*,
+        _track_weighted_*, csrc/sampled_goals.hip): step t under reference
+        row min(ref_start + t, L - 1), the terminal step under row
+        ref_start + N's `x_goal`, with row b's diagonals of Q, Q_term, R; the
+        S candidates of a trajectory share both.  With neither set it is the
+        call "shared" makes, the same launch."""
         self._need_sample_problem("shoot")
-        if self.reference is not None:
-            raise _native.NativeError(
-                "shoot costs its candidates under ONE goal per trajectory; "
-                "with a reference (set_reference) the line search's objective "
-                "is another one")
-        if self.batch_weights is not None:
-            raise _native.NativeError(
-                "shoot costs its candidates under the shared Q, Q_term, R; "
-                "with per-trajectory weights (set_batch_weights) the line "
-                "search's objective is another one")
+        goals = self._one_sampled_objective("shoot", objective)
         B, N, n, m = self.B, self.N, self.n, self.m
         S = int(samples)
         if S < 1:
@@ -1199,7 +1198,8 @@ class ILQRSolver(object):
         Zw = self._out(not adopt, B, N + 1, n)
         Uw = self._out(not adopt, B, N, m)
         p = _native.ptr
-        self._launch(events, self._problem_call, "pddp_shoot", B, N, S,
+        self._launch(events, functools.partial(self._problem_call, goals=goals),
+                     "pddp_shoot", B, N, S,
                      p(self.z0), p(self.U), p(self.u_min), p(self.u_max),
                      p(a_std), float(smooth), int(seed), int(sample_offset),
                      p(active), p(out.J), p(out.best), p(out.J_best), p(Zw),
@@ -1230,7 +1230,7 @@ class ILQRSolver(object):
     @_on_device
     def mppi(self, samples, std, temperature, smooth=0.0, seed=0,
              sample_offset=0, iterations=1, active=None, adopt=True,
-             events=None):
+             events=None, objective="shared"):
         """Sampled shooting with a softmin-weighted (MPPI) update of the
         action sequence (pddp_mppi_*, csrc/mppi.hip): `shoot`'s S = `samples`
         candidates, costed by the same law, and instead of the cheapest one
@@ -1261,10 +1261,12 @@ class ILQRSolver(object):
         carried rows.  `events`: a (start, stop) pair for the dispatch, with
         one iteration only.
 
-        Refused while a reference or per-trajectory cost weights are set, as
-        `shoot` is."""
+        `objective`: as `shoot` - "shared" refuses while a reference or
+        per-trajectory cost weights are set, "search" costs the candidates
+        and the weighted sequence under the line search's objective
+        (pddp_mppi_track_*, _weighted_*, _track_weighted_*)."""
         self._need_sample_problem("mppi")
-        self._one_sampled_objective("mppi")
+        goals = self._one_sampled_objective("mppi", objective)
         B, N, n, m = self.B, self.N, self.n, self.m
         S, K = int(samples), int(iterations)
         if S < 1:
@@ -1289,7 +1291,9 @@ class ILQRSolver(object):
                 J_w=self._out(masked, B))
             # (rows without a weighted sequence are never selected)
             Zw, Uw = self._out(False, B, N + 1, n), self._out(False, B, N, m)
-            self._launch(events, self._problem_call, "pddp_mppi", B, N, S,
+            self._launch(events,
+                         functools.partial(self._problem_call, goals=goals),
+                         "pddp_mppi", B, N, S,
                          p(self.z0), p(U), p(self.u_min), p(self.u_max),
                          p(a_std), p(lam), float(smooth), int(seed),
                          int(sample_offset) + k * B * S, p(active), p(out.J),
@@ -1311,19 +1315,33 @@ class ILQRSolver(object):
         self.reset_controller_state()
         return out
 
-    def _one_sampled_objective(self, what):
-        """`mppi`'s and `mppi_closed_loop`'s refusal while a reference or
-        per-trajectory cost weights are set."""
+    def _one_sampled_objective(self, what, objective="shared"):
+        """The `objective` of `shoot`, `mppi` and `mppi_closed_loop`.
+        "shared": the refusal while a reference or per-trajectory cost
+        weights are set.  "search": True where the candidates are costed
+        along the reference and / or under the weights (the entry points of
+        csrc/sampled_goals.hip), False where neither is set - the call is
+        then the one "shared" makes."""
+        if objective == "search":
+            return self.reference is not None or \
+                self.batch_weights is not None
+        if objective != "shared":
+            raise _native.NativeError(
+                '%s: objective is %r, expected "shared" or "search"' % (
+                    what, objective))
         if self.reference is not None:
             raise _native.NativeError(
                 "%s costs its candidates under ONE goal per trajectory; "
                 "with a reference (set_reference) the line search's objective "
-                "is another one" % what)
+                'is another one (objective="search" costs them under it)'
+                % what)
         if self.batch_weights is not None:
             raise _native.NativeError(
                 "%s costs its candidates under the shared Q, Q_term, R; "
                 "with per-trajectory weights (set_batch_weights) the line "
-                "search's objective is another one" % what)
+                'search\'s objective is another one (objective="search" '
+                "costs them under it)" % what)
+        return False
 
     def _temperature(self, what, temperature):
         """[B] device vector of a temperature given as a float or [B]."""
@@ -1343,7 +1361,7 @@ class ILQRSolver(object):
                          params=None, x_goal=None, u_goal=None,
                          disturbance=None, process_std=None, obs_std=None,
                          sample_offset=0, step_offset=0, active=None,
-                         log_costs=False, events=None):
+                         log_costs=False, events=None, objective="shared"):
         """A receding-horizon MPPI trial of every trajectory on its own plant,
         all `steps` control steps in ONE launch (pddp_mppi_trial_*,
         csrc/mppi_trial.hip): per control step `iterations` iterations of
@@ -1382,11 +1400,27 @@ class ILQRSolver(object):
         `z0=None`, `step_offset=steps` and `candidate_offset` advanced by
         steps * iterations * B * samples continues the trial.
 
-        Refused while a reference or per-trajectory cost weights are set, as
-        `mppi` is."""
+        `objective="shared"` (default): refused while a reference or
+        per-trajectory cost weights are set, as `mppi` is.
+        `objective="search"`: the trial plans under the line search's
+        objective (pddp_mppi_trial_goals_*, csrc/sampled_goals.hip).  With a
+        reference control step c plans under the window that starts at row
+        `ref_start + c`; the applied step is logged as `mpc_closed_loop` logs
+        it - the stage cost under that row, the terminal cost under the
+        next - and the plant fields supply parameters only: `x_goal` /
+        `u_goal` would not be read and are refused.  Afterwards `ref_start`
+        has advanced by `steps` and a captured round is dropped, so that a
+        continued trial continues the reference.  Per-trajectory weights
+        affect the planning only: `J` is under the shared Q, Q_term, R, the
+        common yardstick.  With neither set it is the call "shared" makes."""
         what = "mppi_closed_loop"
         self._need_sample_problem(what)
-        self._one_sampled_objective(what)
+        goals = self._one_sampled_objective(what, objective)
+        tracking = goals and self.reference is not None
+        if tracking and (x_goal is not None or u_goal is not None):
+            raise _native.NativeError(
+                "%s: with a reference the trial's cost is evaluated along "
+                "it; the plant's x_goal / u_goal would not be read" % what)
         B, N, n, m = self.B, self.N, self.n, self.m
         T, S, K = int(steps), int(samples), int(iterations)
         if S < 1:
@@ -1413,9 +1447,15 @@ class ILQRSolver(object):
         U_work = self._out(False, B, N, m)
         Jc = out.Jc if log_costs else self._out(False, B, S)
         p = _native.ptr
+        name, lead = "pddp_mppi_trial", ()
+        if goals:  # (the window and the weights, nullable each, not both)
+            name = "pddp_mppi_trial_goals"
+            lead = (self._ref_window() if tracking else (None, 0, 0)) + \
+                (p(self.batch_weights),)
         self._launch(
-            events, _native.call, "pddp_mppi_trial", self.dtype, self._pp,
-            p(self.batch_table), p(plant), B, N, S, K, T, 0, T, p(self.z0),
+            events, _native.call, name, self.dtype, self._pp,
+            p(self.batch_table), p(plant), *lead, B, N, S, K, T, 0, T,
+            p(self.z0),
             p(self.U), p(self.Z), p(U_work), p(self.u_min), p(self.u_max),
             p(a_std), p(lam), float(smooth), int(seed), int(candidate_offset),
             B * S, p(disturbance), p(w_std), p(v_std), int(sample_offset),
@@ -1426,6 +1466,9 @@ class ILQRSolver(object):
         # (the plan is a new nominal: records at the next round's start)
         self.reset_controller_state()
         self._derivs_due = True
+        if tracking:  # the next call's window, as mpc_closed_loop leaves it
+            self.ref_start += T
+            self._graph = None  # (captured under another window)
         return out
 
     def _plant_table(self, what, params, x_goal, u_goal):
