@@ -674,8 +674,8 @@ int pddp_mppi_trial_f64(
 /* ---- the sampling planners under the line search's objective: pddp_shoot_*,
  * pddp_mppi_* and pddp_mppi_trial_* above along a reference (a goal per time
  * step, pddp_line_search_track_*) and / or under per-trajectory cost weights
- * (pddp_line_search_weighted_*) (csrc/sampled_goals.hip; the reference has no
- * counterpart).  Nothing changes in how candidates are drawn, clamped,
+ * (pddp_line_search_weighted_*) (the *_goals_kernel of csrc/shoot.hip,
+ * mppi.hip, mppi_trial.hip; the reference has no counterpart).  Nothing changes in how candidates are drawn, clamped,
  * selected, weighted or summed: the three laws above hold word for word.  Only
  * the cost every rollout is summed under changes - the candidates', the
  * winner's second pass in shoot, the weighted sequence's in mppi and the trial:

@@ -1175,7 +1175,7 @@ class ILQRSolver(object):
         another objective than the line search's.  `objective="search"`
         costs every candidate - and the winner's second pass - under whatever
         the line search currently uses (pddp_shoot_track_*, _weighted_*,
-        _track_weighted_*, csrc/sampled_goals.hip): step t under reference
+        _track_weighted_*, csrc/shoot.hip, mppi.hip): step t under reference
         row min(ref_start + t, L - 1), the terminal step under row
         ref_start + N's `x_goal`, with row b's diagonals of Q, Q_term, R; the
         S candidates of a trajectory share both.  With neither set it is the
@@ -1320,7 +1320,7 @@ class ILQRSolver(object):
         "shared": the refusal while a reference or per-trajectory cost
         weights are set.  "search": True where the candidates are costed
         along the reference and / or under the weights (the entry points of
-        csrc/sampled_goals.hip), False where neither is set - the call is
+        csrc/shoot.hip, mppi.hip), False where neither is set - the call is
         then the one "shared" makes."""
         if objective == "search":
             return self.reference is not None or \
@@ -1403,7 +1403,7 @@ class ILQRSolver(object):
         `objective="shared"` (default): refused while a reference or
         per-trajectory cost weights are set, as `mppi` is.
         `objective="search"`: the trial plans under the line search's
-        objective (pddp_mppi_trial_goals_*, csrc/sampled_goals.hip).  With a
+        objective (pddp_mppi_trial_goals_*, csrc/mppi_trial.hip).  With a
         reference control step c plans under the window that starts at row
         `ref_start + c`; the applied step is logged as `mpc_closed_loop` logs
         it - the stage cost under that row, the terminal cost under the

@@ -1,0 +1,261 @@
+// sampled_common.hpp - what the sampling planners share (shoot.hip, mppi.hip,
+// mppi_trial.hip): the draws' stream, the order of an argmin,
+// the softmin weight, the sum over a lane group, the hand-over inside a launch,
+// the hooks through which a family's ONE kernel text (*_kernel_body.inc)
+// reaches the problem of trajectory b - the plain kernel's table row, or the
+// goals kernel's reference and weights - and the host path's common pieces.
+#pragma once
+
+#include <climits>
+#include <cmath>
+#include <limits>
+#include "models.hpp"
+#include "problem_args.hpp"
+#include "model_params.hpp"
+#include "ref_args.hpp"
+#include "closed_loop_args.hpp"
+#include "closed_loop_draws.hpp"
+
+namespace pddp {
+
+constexpr int kSampledStream = 2;  // (0 process, 1 measurement: closed_loop.hip)
+
+// (J, s) ordered lexicographically; (+inf, -1) is "no finite cost" and loses
+// against every candidate, whose J is finite.
+template <typename T>
+PDDP_DEV void take_lower(T& J, int& s, T oJ, int os) {
+  const bool take = oJ < J || (oJ == J && os < s);
+  J = take ? oJ : J;
+  s = take ? os : s;
+}
+
+PDDP_DEV float exp_of(float x) { return expf(x); }
+PDDP_DEV double exp_of(double x) { return exp(x); }
+
+// w_s: 1 for the best candidate (the exponent is -0), 0 for a cost that is
+// not finite.  The difference and the quotient are rounded one by one.
+template <typename T>
+PDDP_DEV T softmin_weight(T J, T J_best, T lam) {
+  const T arg = -((J - J_best) / lam);
+  return is_finite(J) ? exp_of(arg) : T(0);
+}
+
+// The sums of v[0..K) over a trajectory's lane group, on every lane of the
+// group: the butterfly, then (one trajectory over several wavefronts) the
+// wavefronts in their order through `part` [K][waves], read by every lane
+// after ONE barrier.  The caller alternates between two `part` blocks from one
+// sum to the next, so a wavefront that runs ahead writes the block nobody
+// still reads.
+template <typename T, int K>
+PDDP_DEV void group_sum(T (&v)[K], int span, bool multi,
+                        T (&part)[K][kClosedLoopThreads / kWave]) {
+  for (int off = 1; off < span; off <<= 1) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) v[j] += __shfl_xor(v[j], off);
+  }
+  if (multi) {
+    const int tid = threadIdx.x;
+    if (tid % kWave == 0) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) part[j][tid / kWave] = v[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      v[j] = part[j][0];
+      for (int w = 1; w < (int)blockDim.x / kWave; ++w) v[j] += part[j][w];
+    }
+  }
+}
+
+// Between the head's stores to z0[b] / U[b] and the group's loads of them: the
+// storing wavefront waits for its stores, then the workgroup meets at the
+// barrier, whose fence keeps the compiler from moving the loads ahead of it.
+// A workgroup's wavefronts share their CU's L1: workgroup scope is enough.
+PDDP_DEV void hand_over() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+// ---- the hooks of the kernel texts --------------------------------------------
+// A kernel defines, ahead of its #include of the family's text,
+//   PDDP_PROBLEM_OF_B     first statement: P, the problem of trajectory b
+//   PDDP_ROW_OF_B         inside the `if (live)` that loads the bounds: the
+//                         plain kernel's table row; empty in the goals kernel,
+//                         whose PDDP_PROBLEM_OF_B has written it.  (The two
+//                         places are what the two kernels were compiled from:
+//                         a hook for the statement's place alone.)
+//   PDDP_GOALS(point)     sampled_rollout_body.inc's; empty in a plain kernel
+// and #undefs them behind it.
+//
+// The plain kernels (`a.table` nullable: the _batch entry points' table).  The
+// row as statements, as shoot.hip wrote it, not write_params_and_goals: the
+// same statements inlined from a function reach the optimiser in another order
+// (ref_args.hpp's note), and shoot's and mppi's kernels were compiled from
+// these; the trial's from the function, mppi_trial.hip.
+#define PDDP_PLAIN_PROBLEM_OF_B ProblemT<T> P = shared;
+#define PDDP_PLAIN_ROW_OF_B                                                    \
+  if (a.table != nullptr) {                                                    \
+    const T* row = a.table + (size_t)b * PDDP_BATCH_ROW;                       \
+    P.dt = row[PDDP_BATCH_PARAMS];                                             \
+    PDDP_COPY(kModelParamCount<MODEL> - 1, P.p, row + PDDP_BATCH_PARAMS + 1)   \
+    PDDP_COPY(D::na, P.goal, row + PDDP_BATCH_X_GOAL)                          \
+    PDDP_COPY(D::m, P.ugoal, row + PDDP_BATCH_U_GOAL)                          \
+  }
+// The goals kernels.  `goals` (RefArgs: table, ref, ref_len, ref_t0; ref NULL
+// without a reference) and `weights` (NULL without) are the launch's.  P: the
+// shared problem, row b of the table (its goals only where no reference
+// supplies them), row b of the weights.  `tracked` is uniform over the
+// launch.  (PDDP_GOALS_P_OF_B apart: the trial forms `tracked` from its
+// `window` ahead of `goals`, mppi_trial.hip - statement order alone.)
+#define PDDP_GOALS_PROBLEM_OF_B                                               \
+  const bool tracked = goals.ref != nullptr;                                   \
+  PDDP_GOALS_P_OF_B
+#define PDDP_GOALS_P_OF_B                                                      \
+  ProblemT<T> P = shared;                                                      \
+  if (live) {                                                                  \
+    if (goals.table != nullptr) {                                              \
+      const T* trow = goals.table + (size_t)b * PDDP_BATCH_ROW;                \
+      if (tracked)                                                             \
+        write_params<T, MODEL>(P, trow);                                       \
+      else                                                                     \
+        write_params_and_goals<T, MODEL>(P, trow);                             \
+    }                                                                          \
+    if (weights != nullptr)                                                    \
+      write_weights<T, MODEL>(P, weights + (size_t)b * PDDP_WEIGHT_ROW);       \
+  }
+// track_goal_hooks.inc's line-search hooks with a nullable reference: without
+// one the "next row" is the goals P holds.  #define PDDP_GOALS(point)
+// PDDP_GOALS_##point.
+#define PDDP_GOALS_TAKE_FIRST                                                  \
+  if (tracked) {                                                               \
+    const T* row0 = ref_row(goals, b, 0);                                      \
+    PDDP_COPY(D::na, P.goal, row0 + PDDP_REF_X_GOAL)                           \
+    PDDP_COPY(m, P.ugoal, row0 + PDDP_REF_U_GOAL)                              \
+  }
+#define PDDP_GOALS_REQUEST_NEXT                                                \
+  T xg2[D::na], ug2[m];                                                        \
+  PDDP_COPY(D::na, xg2, P.goal)                                                \
+  PDDP_COPY(m, ug2, P.ugoal)                                                   \
+  if (tracked) {                                                               \
+    const T* row = ref_row(goals, b, t + 1);                                   \
+    PDDP_COPY(D::na, xg2, row + PDDP_REF_X_GOAL)                               \
+    PDDP_COPY(m, ug2, row + PDDP_REF_U_GOAL)                                   \
+  }
+#define PDDP_GOALS_TAKE_NEXT                                                   \
+  PDDP_COPY(m, P.ugoal, ug2)                                                   \
+  PDDP_COPY(D::na, P.goal, xg2)
+
+// ---- host path -----------------------------------------------------------------
+
+// What an entry point's suffix brings: `batch` promises the table, `track`
+// the reference, `weighted` the weights; what a suffix does not name is
+// absent.  `goals`: the family's goals kernel (every suffix but _batch).
+template <typename T>
+struct SampledForm {
+  bool batch, goals, track, weighted;
+  const T* table;
+  const T* ref;
+  int ref_len, ref_t0;
+  const T* weights;
+};
+
+// the reference and the weights of a launch
+template <typename T>
+struct SampledGoals {
+  RefArgs<T> goals;
+  const T* weights;  // [B][PDDP_WEIGHT_ROW] or NULL
+};
+
+// What the form promises is there: the table, the reference with ref_t0
+// clamped (ref_args), the weights.
+template <typename T>
+static bool sampled_goals(const SampledForm<T>& f, SampledGoals<T>* out) {
+  *out = SampledGoals<T>{RefArgs<T>{f.table, nullptr, 0, 0}, nullptr};
+  if (f.batch && f.table == nullptr) return false;
+  if (f.track &&
+      !ref_args(f.table, f.ref, f.ref_len, f.ref_t0, &out->goals))
+    return false;
+  if (f.weighted && f.weights == nullptr) return false;
+  if (f.weighted) out->weights = f.weights;
+  return true;
+}
+
+// The mapping is closed_loop's: its geometry.  Sets a.G.
+template <typename Args>
+static dim3 sampled_geometry(Args& a, int* threads) {
+  ClosedLoopArgs<float> g{};
+  g.B = a.B;
+  g.S = a.S;
+  dim3 blocks;
+  *threads = closed_loop_geometry(g, blocks);
+  a.G = g.G;
+  return blocks;
+}
+
+// One launcher for the six kernels: `extra` are the goals kernel's trailing
+// arguments, none for a plain kernel.
+template <typename T, typename Args, typename... Extra>
+static int launch_sampled(void (*kernel)(ProblemT<T>, Args, Extra...),
+                          const pddp_problem& p, Args a, hipStream_t st,
+                          Extra... extra) {
+  const ProblemT<T> P = convert_problem<T>(p);
+  int threads;
+  const dim3 blocks = sampled_geometry(a, &threads);
+  PDDP_LAUNCH(kernel, blocks, dim3(threads), 0, st, P, a, extra...);
+  return launch_status();
+}
+
+}  // namespace pddp
+
+// The parameters the entry points of shoot and of mppi share, and their names.
+#define PDDP_SHOOT_PARAMS(T)                                                   \
+  int B, int N, int S, const T* z0, const T* U, const T* u_min,                \
+      const T* u_max, const T* a_std, double smooth, uint64_t seed,            \
+      uint64_t sample_offset, const uint8_t* active, T* Jc, int32_t* best,     \
+      T* J_best, T* Z_out, T* U_out, void* stream
+#define PDDP_SHOOT_ARGS                                                        \
+  B, N, S, z0, U, u_min, u_max, a_std, smooth, seed, sample_offset, active,    \
+      Jc, best, J_best, Z_out, U_out, stream
+#define PDDP_MPPI_PARAMS(T)                                                    \
+  int B, int N, int S, const T* z0, const T* U, const T* u_min,                \
+      const T* u_max, const T* a_std, const T* lam, double smooth,             \
+      uint64_t seed, uint64_t sample_offset, const uint8_t* active, T* Jc,     \
+      int32_t* best, T* J_best, T* W, T* J_w, T* Z_out, T* U_out, void* stream
+#define PDDP_MPPI_ARGS                                                         \
+  B, N, S, z0, U, u_min, u_max, a_std, lam, smooth, seed, sample_offset,       \
+      active, Jc, best, J_best, W, J_w, Z_out, U_out, stream
+
+// The five entry points of one family (NAME: shoot, mppi) over its one impl.
+#define PDDP_SAMPLED_ENTRY_POINTS(NAME, SUF, T, PARAMS, ARGS)                  \
+  int pddp_##NAME##_##SUF(const pddp_problem* p, PARAMS(T)) {                  \
+    return pddp::NAME##_impl<T>(                                               \
+        p, {false, false, false, false, nullptr, nullptr, 0, 0, nullptr},      \
+        ARGS);                                                                 \
+  }                                                                            \
+  /* the same with a problem per trajectory: row b of `table` */               \
+  int pddp_##NAME##_batch_##SUF(const pddp_problem* p, const T* table,         \
+                                PARAMS(T)) {                                   \
+    return pddp::NAME##_impl<T>(                                               \
+        p, {true, false, false, false, table, nullptr, 0, 0, nullptr}, ARGS);  \
+  }                                                                            \
+  /* under the line search's objective: thin fronts over the goals kernel */   \
+  int pddp_##NAME##_track_##SUF(const pddp_problem* p, const T* table,         \
+                                const T* ref, int ref_len, int ref_t0,         \
+                                PARAMS(T)) {                                   \
+    return pddp::NAME##_impl<T>(                                               \
+        p, {false, true, true, false, table, ref, ref_len, ref_t0, nullptr},   \
+        ARGS);                                                                 \
+  }                                                                            \
+  int pddp_##NAME##_weighted_##SUF(const pddp_problem* p, const T* table,      \
+                                   const T* weights, PARAMS(T)) {              \
+    return pddp::NAME##_impl<T>(                                               \
+        p, {false, true, false, true, table, nullptr, 0, 0, weights}, ARGS);   \
+  }                                                                            \
+  int pddp_##NAME##_track_weighted_##SUF(                                      \
+      const pddp_problem* p, const T* table, const T* ref, int ref_len,        \
+      int ref_t0, const T* weights, PARAMS(T)) {                               \
+    return pddp::NAME##_impl<T>(                                               \
+        p, {false, true, true, true, table, ref, ref_len, ref_t0, weights},    \
+        ARGS);                                                                 \
+  }

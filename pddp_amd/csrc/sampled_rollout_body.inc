@@ -1,14 +1,15 @@
 // sampled_rollout_body.inc - one candidate (b, s) of the sampling planners
-// rolled out by its lane under the line search's objective: the text of the
-// three kernels of sampled_goals.hip (shoot_goals_kernel, mppi_goals_kernel,
-// mppi_trial_goals_kernel).  It is shoot.hip's candidate rollout - the
+// rolled out by its lane: the text of all six kernels (shoot.hip, mppi.hip,
+// mppi_trial.hip: the plain kernel and the goals kernel of each) - the
 // action's perturbation, the clamp, cost, dynamics and the AR(1) update of e,
-// operation for operation - with the goals of `P` taken step by step.
+// with the goals of `P` taken step by step where the kernel has goal hooks.
 //
 // The including kernel has `a` (seed, beta, gamma), `P` (its
 // PDDP_PROBLEM_OF_B), `z0`, `Ub`, `roll`, `base`, `astd`, `umin`, `umax`,
 // `bounded`, `N`, `b` and defines
-//   PDDP_SAMPLED_STREAM     the draws' stream
+//   PDDP_SAMPLED_AFTER_E0   behind the first draws: empty, or declarations
+//                           the kernel was compiled with at this place (a
+//                           hook for statement order alone: shoot.hip)
 //   PDDP_SAMPLED_KEEP_ROW   after the clamp: empty, or the stores of row t
 //   PDDP_GOALS(point)       TAKE_FIRST ahead of the time loop, REQUEST_NEXT
 //                           behind the step's draws (row t + 1, ahead of the
@@ -21,7 +22,8 @@
       for (int j = 0; j < n; ++j) z[j] = z0[j];
 #pragma unroll
       for (int j = 0; j < m; ++j) ur[j] = Ub[j];
-      draw_units<T, m>(a.seed, roll, 0, PDDP_SAMPLED_STREAM, e);  // e_0 = xi_0
+      draw_units<T, m>(a.seed, roll, 0, kSampledStream, e);  // e_0 = xi_0
+      PDDP_SAMPLED_AFTER_E0
       PDDP_GOALS(TAKE_FIRST)
       T J = T(0);
       for (int t = 0; t < N; ++t) {
@@ -30,7 +32,7 @@
         const int tn = (t + 1 < N) ? t + 1 : t;
 #pragma unroll
         for (int j = 0; j < m; ++j) ur2[j] = Ub[tn * m + j];
-        draw_units<T, m>(a.seed, roll, t + 1, PDDP_SAMPLED_STREAM, xi);
+        draw_units<T, m>(a.seed, roll, t + 1, kSampledStream, xi);
         PDDP_GOALS(REQUEST_NEXT)
 #pragma unroll
         for (int r = 0; r < m; ++r) {

@@ -1,7 +1,8 @@
 """What the tests of the sampling planners under the line search's objective
 share (tests/test_sampled_goals.py; pddp_shoot_* / pddp_mppi_* with the
 suffixes _track, _weighted, _track_weighted, pddp_mppi_trial_goals_*,
-csrc/sampled_goals.hip, ILQRSolver.shoot / mppi / mppi_closed_loop with
+the *_goals_kernel of csrc/shoot.hip, mppi.hip and mppi_trial.hip;
+ILQRSolver.shoot / mppi / mppi_closed_loop with
 objective="search"): the per-trajectory weights, the oracle's rollouts with
 every step under its reference row, the entry points called directly - the
 form chosen by what the solver has set - and the numpy / oracle model of a

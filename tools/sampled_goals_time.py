@@ -1,9 +1,8 @@
 """What the line search's objective costs the sampling planners: each new form
 (ILQRSolver.shoot / mppi / mppi_closed_loop with objective="search" along a
-reference, under per-trajectory weights, under both - the kernels of
-csrc/sampled_goals.hip) next to its sibling without either (csrc/shoot.hip,
-csrc/mppi.hip, csrc/mppi_trial.hip, units this one leaves byte for byte as
-they were) ON THE SAME COMMIT: cartpole f32, 4096 trajectories, horizon 100,
+reference, under per-trajectory weights, under both - the *_goals_kernel of
+csrc/shoot.hip, csrc/mppi.hip, csrc/mppi_trial.hip) next to its sibling
+without either (the plain kernel of the same unit) ON THE SAME COMMIT: cartpole f32, 4096 trajectories, horizon 100,
 bounded, base actions 0.1 randn, std 3, smooth 0.7, temperature 100,
 S = 16, 64 and 256.  The reference has N + 1 + steps rows around the shared
 goal, the weights are the shared diagonals x U(1, 2).
