@@ -853,7 +853,7 @@ int pddp_mpc_advance_f64(const pddp_problem* problem, const double* table,
                          int32_t* iter, uint8_t* active, uint8_t* fresh,
                          int32_t* n_live, void* stream);
 
-/* ---- reference tracking: a goal PER TIME STEP (csrc/tracking.hip) ---------
+/* ---- reference tracking: a goal PER TIME STEP (csrc/goal_kernels.hpp) -----
  * `ref` [B][ref_len][PDDP_REF_ROW], device memory of the run's dtype: row k of
  * trajectory b holds the goals of step k of its reference,
  *   [PDDP_REF_X_GOAL .. +7]  x_goal  (augmented coordinates, PDDP_MAX_AUG)
@@ -1008,7 +1008,7 @@ int pddp_mpc_observe_f64(int B, int n, const double* x, const double* v_std,
                          uint64_t seed, uint64_t rollout_offset, int step,
                          const uint8_t* mask, double* y, void* stream);
 
-/* ---- per-trajectory cost weights (csrc/weights.hip) -------------------------
+/* ---- per-trajectory cost weights (csrc/goal_kernels.hpp) --------------------
  * `weights` [B][PDDP_WEIGHT_ROW], device memory of the run's dtype: row b holds
  *   [PDDP_WEIGHT_Q      .. +7]  the diagonal of Q      of trajectory b
  *                               (augmented coordinates, PDDP_MAX_AUG)
@@ -1066,7 +1066,7 @@ int pddp_line_search_weighted_f64(const pddp_problem* problem,
                                   double* Uc, double* Jc, void* stream);
 
 /* ---- a reference tracked under per-trajectory cost weights
- * (csrc/track_weights.hip): pddp_derivs_track_* / pddp_line_search_track_*
+ * (csrc/goal_kernels.hpp): pddp_derivs_track_* / pddp_line_search_track_*
  * with the diagonals of Q, Q_term and R of trajectory b REPLACED by row b of
  * `weights`.  `ref`, ref_len, ref_t0 in the reference's layout and law above
  * (row min(ref_t0 + i, ref_len - 1), the last row held), `weights`

@@ -74,6 +74,11 @@ _STEP, _STEP_OUT = [c_int] * 4 + [_P] * 7, [_P] * 14
 _SHOOT = [c_int] * 3 + [_P] * 5 + [c_double, c_uint64, c_uint64] + [_P] * 7
 # (its weighted update: lam after a_std; W and J_w after J_best)
 _MPPI = [c_int] * 3 + [_P] * 6 + [c_double, c_uint64, c_uint64] + [_P] * 9
+# (the records and the line search, what every form takes behind its leading
+# arguments: B N, Z .. state, stream; B N A, Z .. Jc, stream.  The forms lead
+# with the problem; _batch adds the table; _track the table and the window;
+# _weighted the table and the weights; _track_weighted all three)
+_DERIVS, _SEARCH = [c_int] * 2 + [_P] * 10, [c_int] * 3 + [_P] * 12
 _SIGS = {
     "pddp_hip_abi_version": [],
     "pddp_hip_device_count": [],
@@ -88,11 +93,11 @@ _SIGS = {
     "pddp_pack_records": [c_int] * 4 + [_P] * 10,
     "pddp_sum_stage_costs": [c_int, c_int, _P, _P, _P],
     "pddp_nominal_rollout": [_P, c_int, c_int] + [_P] * 7,
-    "pddp_derivs": [_P, c_int, c_int] + [_P] * 10,
-    "pddp_line_search": [_P, c_int, c_int, c_int] + [_P] * 12,
+    "pddp_derivs": [_P] + _DERIVS,
+    "pddp_line_search": [_P] + _SEARCH,
     "pddp_nominal_rollout_batch": [_P, _P, c_int, c_int] + [_P] * 7,
-    "pddp_derivs_batch": [_P, _P, c_int, c_int] + [_P] * 10,
-    "pddp_line_search_batch": [_P, _P, c_int, c_int, c_int] + [_P] * 12,
+    "pddp_derivs_batch": [_P, _P] + _DERIVS,
+    "pddp_line_search_batch": [_P, _P] + _SEARCH,
     "pddp_closed_loop": [_P] + _LOOP + _LOOP_OUT,
     "pddp_closed_loop_noisy": [_P] + _LOOP + _NOISE + _LOOP_OUT,
     "pddp_closed_loop_draws": [c_int] * 5 + [c_uint64, c_uint64, _P, _P],
@@ -121,19 +126,17 @@ _SIGS = {
                              [c_double] + [c_uint64] * 3 + [_P] * 3 +
                              [c_uint64, c_int] + [_P] * 3 + [c_int] + [_P] * 9,
     "pddp_mpc_advance":[_P, _P] + _STEP + _STEP_OUT,
-    "pddp_derivs_track": [_P, _P, _P] + [c_int] * 4 + [_P] * 10,
-    "pddp_line_search_track": [_P, _P, _P] + [c_int] * 5 + [_P] * 12,
+    "pddp_derivs_track": [_P, _P] + _REF + _DERIVS,
+    "pddp_line_search_track": [_P, _P] + _REF + _SEARCH,
     "pddp_mpc_advance_track": [_P, _P] + _REF + _STEP + _STEP_OUT,
     "pddp_mpc_advance_noisy": [_P, _P] + _REF + _STEP + _NOISE +
                               [c_int, _P, _P] + _STEP_OUT,
     "pddp_mpc_observe": [c_int, c_int, _P, _P, c_uint64, c_uint64, c_int, _P,
                          _P, _P],
-    "pddp_derivs_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] * 10,
-    "pddp_line_search_weighted": [_P, _P, _P] + [c_int] * 3 + [_P] * 12,
-    "pddp_derivs_track_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] +
-                                  [c_int] * 2 + [_P] * 10,
-    "pddp_line_search_track_weighted": [_P, _P, _P] + [c_int] * 2 + [_P] +
-                                       [c_int] * 3 + [_P] * 12,
+    "pddp_derivs_weighted": [_P, _P, _P] + _DERIVS,
+    "pddp_line_search_weighted": [_P, _P, _P] + _SEARCH,
+    "pddp_derivs_track_weighted": [_P, _P] + _REF + [_P] + _DERIVS,
+    "pddp_line_search_track_weighted": [_P, _P] + _REF + [_P] + _SEARCH,
     "pddp_search_accept": [_P, c_int, c_int, c_int] + [_P] * 11 +
                           [c_double, c_double, c_int] +
                           [_P] * 11,

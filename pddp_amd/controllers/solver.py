@@ -58,7 +58,7 @@ records+separate.
 Weights and a reference are held at once where the second setter is told to
 keep the first (`set_reference(keep_weights=True)`,
 `set_batch_weights(keep_reference=True)`): derivs and line search are then the
-pddp_*_track_weighted_* entry points (csrc/track_weights.hip), with the table's
+pddp_*_track_weighted_* entry points (csrc/goal_kernels.hpp), with the table's
 address or NULL, the reference window and the weights; every round is
 records+separate.  Without the keyword the second setter refuses.
 """
@@ -611,20 +611,17 @@ class ILQRSolver(object):
         window, the weights.  The addresses are looked up at the call: a
         tensor may be replaced between two calls."""
         p = _native.ptr
-        if goals and self.batch_weights is not None and \
-                self.reference is not None:
-            suffix, lead = "_track_weighted", (p(self.batch_table),) + \
-                self._ref_window() + (p(self.batch_weights),)
-        elif goals and self.batch_weights is not None:
-            suffix, lead = "_weighted", (p(self.batch_table),
-                                         p(self.batch_weights))
-        elif goals and self.reference is not None:
-            suffix, lead = "_track", (p(self.batch_table),) + \
-                self._ref_window()
-        elif self.batch_table is not None:
-            suffix, lead = "_batch", (p(self.batch_table),)
-        else:
-            suffix, lead = "", ()
+        track = goals and self.reference is not None
+        weighted = goals and self.batch_weights is not None
+        suffix = ("_track" if track else "") + \
+            ("_weighted" if weighted else "")
+        if not suffix and self.batch_table is not None:
+            suffix = "_batch"
+        lead = ()
+        if suffix:  # the table, then the window, then the weights
+            lead = (p(self.batch_table),) + \
+                (self._ref_window() if track else ()) + \
+                ((p(self.batch_weights),) if weighted else ())
         return _native.call(name + suffix, self.dtype, self._pp, *lead, *args)
 
     def _ref_window(self):

@@ -18,7 +18,7 @@
 //   rollout, step, stream, component): Philox4x32-10 on a counter, Box-Muller
 //   on its words (closed_loop_draws.hpp).  No noise tensor exists.
 //
-//   `ref` [B][ref_len][PDDP_REF_ROW], tracking.hip's: rollout (b, s) takes the
+//   `ref` [B][ref_len][PDDP_REF_ROW], the records': rollout (b, s) takes the
 //   stage cost of step t under row min(ref_t0 + t, ref_len - 1) of trajectory
 //   b and the terminal cost under row min(ref_t0 + N, ref_len - 1), x_goal
 //   only.  The S rollouts of a trajectory share its reference; the plant row

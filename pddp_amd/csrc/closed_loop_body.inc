@@ -14,7 +14,7 @@
 //                          noise
 // and, for the goals of `P` (empty where a rollout has ONE goal: the plant
 // row's or the shared problem's; closed_loop_track_kernel takes them from a
-// reference row, as tracking.hip does at line_search_body.inc's hooks)
+// reference row, as track_goal_hooks.inc at line_search_body.inc's hooks)
 //   PDDP_GOALS_TAKE_FIRST    ahead of the time loop: row 0's over P's
 //   PDDP_GOALS_REQUEST_NEXT  behind the step's draws: row t + 1, ahead of the
 //                            dependent chain

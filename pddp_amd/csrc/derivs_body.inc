@@ -1,11 +1,11 @@
 // derivs_body.inc - the derivative records of one trajectory by its workgroup:
 // the text of derivs_kernel and batch_derivs_kernel (problem_kernels.hip) and
-// of track_derivs_kernel (tracking.hip).
+// of the track_, weighted_ and track_weighted_derivs_kernel (goal_kernels.hpp).
 // PDDP_PROBLEM_OF_B as in rollout_body.inc; PDDP_SPLIT_TERMINAL: record_of is
 // called under `if (terminal)` with the flag a constant in each call (see
 // batch_derivs_kernel).  PDDP_GOALS(point): empty, or with a goal per time
-// step what tracking.hip does at TAKE_X and TAKE_U (write step t's goals over
-// P's, the latter where the step has an action).
+// step what track_goal_hooks.inc does at TAKE_X and TAKE_U (write step t's
+// goals over P's, the latter where the step has an action).
   using D = ModelDims<MODEL>;
   constexpr int n = D::n, m = D::m;
   constexpr RecLayout lay(n, m);

@@ -1,10 +1,11 @@
 // line_search_body.inc - one (trajectory, step size) candidate by its lane: the
 // text of line_search_kernel and batch_line_search_kernel (problem_kernels.hip)
-// and of track_line_search_kernel (tracking.hip).
+// and of the track_, weighted_ and track_weighted_line_search_kernel
+// (goal_kernels.hpp).
 // PDDP_PROBLEM_OF_B as in rollout_body.inc.  PDDP_GOALS(point): empty, or with
-// a goal per time step what tracking.hip does at TAKE_FIRST (write row 0's over
-// P's), NEXT_ROW (name row t + 1, ahead of the nominal prefetch), PREFETCH_NEXT
-// (request it, behind the nominal prefetch) and TAKE_NEXT (write it over P's at
+// a goal per time step what track_goal_hooks.inc does at TAKE_FIRST (write row
+// 0's over P's), NEXT_ROW (name row t + 1, ahead of the nominal prefetch),
+// PREFETCH_NEXT (request it, behind the nominal prefetch) and TAKE_NEXT (write it over P's at
 // the end of the step; up to row N, the terminal cost's).
   using D = ModelDims<MODEL>;
   constexpr int n = D::n, m = D::m;

@@ -2,8 +2,8 @@
 // included (include/pddp_problem.h; ILQRSolver._PARAM_COUNT holds the same
 // numbers on the Python side, tests/test_mpc_closed_loop.py compares the two),
 // and the writers of a per-trajectory row over the shared problem.  The one
-// copy of each: problem_kernels.hip, closed_loop.hip, mpc_advance.hip,
-// tracking.hip, weights.hip, track_weights.hip include it.
+// copy of each: problem_kernels.hip (with goal_kernels.hpp), closed_loop.hip
+// and mpc_advance.hip include it.
 #pragma once
 
 #include "models.hpp"
@@ -40,7 +40,7 @@ PDDP_DEV void write_params_and_goals(ProblemT<T>& P, const T* row) {
 // `row` [PDDP_WEIGHT_ROW] (include/pddp_hip.h: the diagonals of Q, Q_term, R)
 // written over the diagonals of P's cost matrices; the off-diagonal entries
 // stay P's, entries of the row beyond the model's sizes are not read
-// (weights.hip).
+// (goal_kernels.hpp).
 template <typename T, int MODEL>
 PDDP_DEV void write_weights(ProblemT<T>& P, const T* row) {
   using D = ModelDims<MODEL>;

@@ -125,16 +125,16 @@ static int launch_mppi(const pddp_problem& p, MppiArgs<T> a, hipStream_t st) {
 
 template <typename T, int MODEL>
 static int launch_mppi_goals(const pddp_problem& p,
-                             With<MppiGoalsArgs<T>, SampledGoals<T>> w,
+                             With<MppiGoalsArgs<T>, FormGoals<T>> w,
                              hipStream_t st) {
   return launch_sampled<T>(mppi_goals_kernel<T, MODEL>, p, w.a, st, w.x.goals,
                            w.x.weights);
 }
 
 // One impl and one argument test for the five entry-point families: what a
-// form does not bring is null (sampled_common.hpp).
+// form does not bring is null (goal_form.hpp).
 template <typename T>
-static int mppi_impl(const pddp_problem* p, const SampledForm<T>& f,
+static int mppi_impl(const pddp_problem* p, const GoalForm<T>& f,
                      PDDP_MPPI_PARAMS(T)) {
   if (B <= 0 || N <= 0 || S <= 0 || (long long)B * S > 0x7fffffffLL || !z0 ||
       !U || !a_std || !lam || !Jc || !best || !J_w ||
@@ -144,8 +144,8 @@ static int mppi_impl(const pddp_problem* p, const SampledForm<T>& f,
       (U_out == nullptr && S > kClosedLoopThreads) ||
       !(smooth >= 0.0 && smooth < 1.0))  // (NaN fails both)
     return PDDP_E_BADARG;
-  With<MppiGoalsArgs<T>, SampledGoals<T>> w{};
-  if (!sampled_goals(f, &w.x)) return PDDP_E_BADARG;
+  With<MppiGoalsArgs<T>, FormGoals<T>> w{};
+  if (!form_goals(f, &w.x)) return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
   const T beta = (T)smooth, gamma = (T)std::sqrt(1.0 - smooth * smooth);
   if (f.goals) {
@@ -166,7 +166,7 @@ static int mppi_impl(const pddp_problem* p, const SampledForm<T>& f,
 
 extern "C" {
 
-PDDP_SAMPLED_ENTRY_POINTS(mppi, f32, float, PDDP_MPPI_PARAMS, PDDP_MPPI_ARGS)
-PDDP_SAMPLED_ENTRY_POINTS(mppi, f64, double, PDDP_MPPI_PARAMS, PDDP_MPPI_ARGS)
+PDDP_FORM_ENTRY_POINTS(mppi, f32, float, PDDP_MPPI_PARAMS, PDDP_MPPI_ARGS)
+PDDP_FORM_ENTRY_POINTS(mppi, f64, double, PDDP_MPPI_PARAMS, PDDP_MPPI_ARGS)
 
 }  // extern "C"

@@ -183,7 +183,7 @@ static int launch_mppi_trial(const pddp_problem& p, MppiTrialArgs<T> a,
 
 template <typename T, int MODEL>
 static int launch_mppi_trial(
-    const pddp_problem& p, With<MppiTrialGoalsArgs<T>, SampledGoals<T>> w,
+    const pddp_problem& p, With<MppiTrialGoalsArgs<T>, FormGoals<T>> w,
     hipStream_t st) {
   return launch_sampled<T>(mppi_trial_goals_kernel<T, MODEL>, p, w.a, st,
                            w.x.goals, w.x.weights);
@@ -194,7 +194,7 @@ template <typename T>
 static MppiTrialArgs<T>& block_of(MppiTrialArgs<T>& a) { return a; }
 template <typename T>
 static MppiTrialGoalsArgs<T>& block_of(
-    With<MppiTrialGoalsArgs<T>, SampledGoals<T>>& w) {
+    With<MppiTrialGoalsArgs<T>, FormGoals<T>>& w) {
   return w.a;
 }
 
@@ -205,7 +205,7 @@ static MppiTrialGoalsArgs<T>& block_of(
 // the sum).
 template <typename T, typename Launch>
 static int mppi_trial_impl(const pddp_problem* p, Launch l, bool with_goals,
-                           const SampledGoals<T>& x, double smooth,
+                           const FormGoals<T>& x, double smooth,
                            void* stream) {
   auto& a = block_of(l);
   if (a.B <= 0 || a.N <= 0 || a.S <= 0 ||
@@ -266,13 +266,13 @@ extern "C" {
   int pddp_mppi_trial_goals_##SUF(                                             \
       const pddp_problem* p, const T* table, const T* plant, const T* ref,     \
       int ref_len, int ref_t0, const T* weights, PDDP_MPPI_TRIAL_PARAMS(T)) {  \
-    const pddp::SampledGoals<T> x{                                             \
+    const pddp::FormGoals<T> x{                                                \
         ref != nullptr ? pddp::RefArgs<T>{table, ref, ref_len, ref_t0}         \
                        : pddp::RefArgs<T>{table, nullptr, 0, 0},               \
         weights};                                                              \
     return pddp::mppi_trial_impl<T>(                                           \
         p,                                                                     \
-        pddp::With<pddp::MppiTrialGoalsArgs<T>, pddp::SampledGoals<T>>{        \
+        pddp::With<pddp::MppiTrialGoalsArgs<T>, pddp::FormGoals<T>>{           \
             {PDDP_MPPI_TRIAL_HEAD, PDDP_MPPI_TRIAL_REST(T)}, x},               \
         true, x, smooth, stream);                                              \
   }

@@ -1,6 +1,6 @@
 // problem_args.hpp - kernel argument blocks of the problem kernels (shared by
-// problem_kernels.hip: IGNORE_UNCERTAINTY, and default_kernels.hip: the DEFAULT
-// / upper-triangular Cholesky encoding).
+// problem_kernels.hip with goal_kernels.hpp: IGNORE_UNCERTAINTY, and
+// default_kernels.hip: the DEFAULT / upper-triangular Cholesky encoding).
 #pragma once
 
 #include "pddp_common.hpp"
@@ -68,10 +68,9 @@ struct LineSearchArgs {
 };
 
 // Host side of every entry point that takes one of the blocks above
-// (problem_kernels.hip, tracking.hip, weights.hip, track_weights.hip): the
-// argument test, the grid of the per-candidate line search, and the carrier
-// of a block together with a form's per-trajectory data through
-// PDDP_DISPATCH_MODEL.
+// (problem_kernels.hip, all five forms): the argument test, the grid of the
+// per-candidate line search, and the carrier of a block together with a
+// form's per-trajectory data through PDDP_DISPATCH_MODEL.
 template <typename T>
 inline bool args_ok(const DerivArgs<T>& a) {
   return !(a.B <= 0 || a.N <= 0 || !a.Z || !a.U || !a.rec || !a.L || !a.J);

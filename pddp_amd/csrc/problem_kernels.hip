@@ -9,6 +9,8 @@
 #include "models.hpp"
 #include "problem_args.hpp"
 #include "model_params.hpp"
+#include "goal_form.hpp"
+#include "goal_kernels.hpp"  // (_track, _weighted, _track_weighted)
 #include "accept.hpp"
 #include "riccati_n4.hpp"  // DPP helpers of the 16-lane groups
 #include "line_search_lds.hpp"
@@ -23,9 +25,9 @@ namespace pddp {
 // [B][PDDP_BATCH_ROW] written over it (include/pddp_hip.h: params, x_goal,
 // u_goal).  The __global__ functions are that and nothing else; launchers,
 // argument checks and the dispatch on the model are shared too.  The records'
-// and the search's texts are tracking.hip's as well (a goal PER TIME STEP): at
-// their PDDP_GOALS(point) that unit writes a reference row's goals over P's;
-// here the hook is empty.
+// and the search's texts are goal_kernels.hpp's as well (a goal PER TIME STEP,
+// per-trajectory cost weights, both): at their PDDP_GOALS(point) the tracked
+// kernels write a reference row's goals over P's; here the hook is empty.
 //
 // An included text and not a device function: as a forceinline function
 // <T, MODEL> (arguments by value or by reference, the problem handed in or
@@ -172,28 +174,55 @@ static int launch_rollout(const pddp_problem& p,
                 P, w.a);
   return launch_status();
 }
+// The records and the line search in their five forms: the kernel by what the
+// form brought (FormGoals, goal_form.hpp) - a reference, weights, both, the
+// table alone, nothing.
 template <typename T, int MODEL>
 static int launch_derivs(const pddp_problem& p,
-                         With<DerivArgs<T>, const T*> w, hipStream_t st) {
+                         With<DerivArgs<T>, FormGoals<T>> w, hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
-  if (w.x != nullptr)
-    PDDP_LAUNCH((batch_derivs_kernel<T, MODEL>), dim3(w.a.B),
-                dim3(kDerivThreads), 0, st, P, w.a, w.x);
+  const RefArgs<T>& g = w.x.goals;
+  const T* weights = w.x.weights;
+  const dim3 grid(w.a.B), block(kDerivThreads);
+  if (g.ref != nullptr && weights != nullptr)
+    PDDP_LAUNCH((track_weighted_derivs_kernel<T, MODEL>), grid, block, 0, st,
+                P, w.a, g, weights);
+  else if (g.ref != nullptr)
+    PDDP_LAUNCH((track_derivs_kernel<T, MODEL>), grid, block, 0, st, P, w.a,
+                g);
+  else if (weights != nullptr)
+    PDDP_LAUNCH((weighted_derivs_kernel<T, MODEL>), grid, block, 0, st, P,
+                w.a, (WeightArgs<T>{g.table, weights}));
+  else if (g.table != nullptr)
+    PDDP_LAUNCH((batch_derivs_kernel<T, MODEL>), grid, block, 0, st, P, w.a,
+                g.table);
   else
-    PDDP_LAUNCH((derivs_kernel<T, MODEL>), dim3(w.a.B), dim3(kDerivThreads), 0,
-                st, P, w.a);
+    PDDP_LAUNCH((derivs_kernel<T, MODEL>), grid, block, 0, st, P, w.a);
   return launch_status();
 }
 template <typename T, int MODEL>
 static int launch_line_search(const pddp_problem& p,
-                              With<LineSearchArgs<T>, const T*> w,
+                              With<LineSearchArgs<T>, FormGoals<T>> w,
                               hipStream_t st) {
   const ProblemT<T> P = convert_problem<T>(p);
   const LineSearchArgs<T>& a = w.a;
+  const RefArgs<T>& g = w.x.goals;
+  const T* weights = w.x.weights;
   const dim3 lanes = search_lanes(a);
-  if (w.x != nullptr) {  // (the LDS kernels take one problem)
-    PDDP_LAUNCH((batch_line_search_kernel<T, MODEL>), lanes, dim3(kWave), 0,
-                st, P, a, w.x);
+  if (g.ref != nullptr || weights != nullptr || g.table != nullptr) {
+    // (the LDS kernels take one problem)
+    if (g.ref != nullptr && weights != nullptr)
+      PDDP_LAUNCH((track_weighted_line_search_kernel<T, MODEL>), lanes,
+                  dim3(kWave), 0, st, P, a, g, weights);
+    else if (g.ref != nullptr)
+      PDDP_LAUNCH((track_line_search_kernel<T, MODEL>), lanes, dim3(kWave), 0,
+                  st, P, a, g);
+    else if (weights != nullptr)
+      PDDP_LAUNCH((weighted_line_search_kernel<T, MODEL>), lanes, dim3(kWave),
+                  0, st, P, a, (WeightArgs<T>{g.table, weights}));
+    else
+      PDDP_LAUNCH((batch_line_search_kernel<T, MODEL>), lanes, dim3(kWave), 0,
+                  st, P, a, g.table);
     return launch_status();
   }
   using D = ModelDims<MODEL>;
@@ -309,10 +338,10 @@ static bool is_default_encoding(const pddp_problem* p) {
 
 // (check_problem, PDDP_DISPATCH_MODEL: problem_args.hpp)
 
-// The three entry points in both forms.  `batch`: a pddp_*_batch_* entry
-// point - it needs its table and takes check_problem()'s domain only, the four
-// sample models under IGNORE_UNCERTAINTY; the uniform ones (table == nullptr)
-// route the Gaussian encodings to default_kernels.hip.
+// The nominal rollout in its two forms.  `batch`: pddp_nominal_rollout_batch_*
+// - it needs its table and takes check_problem()'s domain only, the four
+// sample models under IGNORE_UNCERTAINTY; the uniform one (table == nullptr)
+// routes the Gaussian encodings to default_kernels.hip.
 template <typename T>
 static int nominal_rollout_impl(const pddp_problem* p, bool batch,
                                 const T* table, int B, int N, const T* z0,
@@ -328,32 +357,50 @@ static int nominal_rollout_impl(const pddp_problem* p, bool batch,
   PDDP_DISPATCH_MODEL(launch_rollout, T, p, w, (hipStream_t)stream)
 }
 
+// What every form of an operation takes behind its leading arguments.
+#define PDDP_DERIVS_PARAMS(T)                                                  \
+  int B, int N, const T* Z, const T* U, const T* u_min, const T* u_max,        \
+      const uint8_t* mask, T* rec, T* L, T* J, int32_t* state, void* stream
+#define PDDP_DERIVS_ARGS \
+  B, N, Z, U, u_min, u_max, mask, rec, L, J, state, stream
+#define PDDP_SEARCH_PARAMS(T)                                                  \
+  int B, int N, int A, const T* Z, const T* U, const T* gains,                 \
+      const T* alphas, const T* u_min, const T* u_max, const uint8_t* active,  \
+      const int32_t* bwd_status, T* Zc, T* Uc, T* Jc, void* stream
+#define PDDP_SEARCH_ARGS                                                       \
+  B, N, A, Z, U, gains, alphas, u_min, u_max, active, bwd_status, Zc, Uc, Jc,  \
+      stream
+
+// The records and the line search: one impl and one argument test for the five
+// forms (goal_form.hpp).  The plain form alone (no suffix) routes the Gaussian
+// encodings to default_kernels.hip, and alone does not hold B * A to an int.
 template <typename T>
-static int derivs_impl(const pddp_problem* p, bool batch, const T* table,
-                       int B, int N, const T* Z, const T* U, const T* u_min,
-                       const T* u_max, const uint8_t* mask, T* rec, T* L, T* J,
-                       int32_t* state, void* stream) {
-  With<DerivArgs<T>, const T*> w{
-      {B, N, Z, U, u_min, u_max, mask, rec, L, J, state}, table};
-  if (!args_ok(w.a) || (batch && !table)) return PDDP_E_BADARG;
-  if (!batch && is_default_encoding(p))
+static bool is_plain(const GoalForm<T>& f) {
+  return !f.batch && !f.goals;
+}
+
+template <typename T>
+static int derivs_impl(const pddp_problem* p, const GoalForm<T>& f,
+                       PDDP_DERIVS_PARAMS(T)) {
+  With<DerivArgs<T>, FormGoals<T>> w{
+      {B, N, Z, U, u_min, u_max, mask, rec, L, J, state}, {}};
+  if (!args_ok(w.a) || !form_goals(f, &w.x)) return PDDP_E_BADARG;
+  if (is_plain(f) && is_default_encoding(p))
     return default_derivs<T>(*p, w.a, (hipStream_t)stream);
   if (int rc = check_problem(p)) return rc;
   PDDP_DISPATCH_MODEL(launch_derivs, T, p, w, (hipStream_t)stream)
 }
 
 template <typename T>
-static int line_search_impl(const pddp_problem* p, bool batch, const T* table,
-                            int B, int N, int A, const T* Z, const T* U,
-                            const T* gains, const T* alphas, const T* u_min,
-                            const T* u_max, const uint8_t* active,
-                            const int32_t* bwd_status, T* Zc, T* Uc, T* Jc,
-                            void* stream) {
-  With<LineSearchArgs<T>, const T*> w{{B, N, A, Z, U, gains, alphas, u_min,
-                                       u_max, active, bwd_status, Zc, Uc, Jc},
-                                      table};
-  if (!args_ok(w.a, batch) || (batch && !table)) return PDDP_E_BADARG;
-  if (!batch && is_default_encoding(p))
+static int line_search_impl(const pddp_problem* p, const GoalForm<T>& f,
+                            PDDP_SEARCH_PARAMS(T)) {
+  With<LineSearchArgs<T>, FormGoals<T>> w{
+      {B, N, A, Z, U, gains, alphas, u_min, u_max, active, bwd_status, Zc, Uc,
+       Jc},
+      {}};
+  if (!args_ok(w.a, !is_plain(f)) || !form_goals(f, &w.x))
+    return PDDP_E_BADARG;
+  if (is_plain(f) && is_default_encoding(p))
     return default_line_search<T>(*p, w.a, (hipStream_t)stream);
   if (int rc = check_problem(p)) return rc;
   PDDP_DISPATCH_MODEL(launch_line_search, T, p, w, (hipStream_t)stream)
@@ -445,22 +492,6 @@ int pddp_search_candidates(int mode) {
     return pddp::nominal_rollout_impl<T>(p, false, nullptr, B, N, z0, U,       \
                                          u_min, u_max, mask, Z, stream);       \
   }                                                                            \
-  int pddp_derivs_##SUF(const pddp_problem* p, int B, int N, const T* Z,       \
-                        const T* U, const T* u_min, const T* u_max,            \
-                        const uint8_t* mask, T* rec, T* L, T* J,               \
-                        int32_t* state, void* stream) {                        \
-    return pddp::derivs_impl<T>(p, false, nullptr, B, N, Z, U, u_min, u_max,   \
-                                mask, rec, L, J, state, stream);               \
-  }                                                                            \
-  int pddp_line_search_##SUF(                                                  \
-      const pddp_problem* p, int B, int N, int A, const T* Z, const T* U,      \
-      const T* gains, const T* alphas, const T* u_min, const T* u_max,         \
-      const uint8_t* active, const int32_t* bwd_status, T* Zc, T* Uc, T* Jc,   \
-      void* stream) {                                                          \
-    return pddp::line_search_impl<T>(p, false, nullptr, B, N, A, Z, U, gains,  \
-                                     alphas, u_min, u_max, active, bwd_status, \
-                                     Zc, Uc, Jc, stream);                      \
-  }                                                                            \
   /* the same with a problem per trajectory: row b of `table` */               \
   int pddp_nominal_rollout_batch_##SUF(                                        \
       const pddp_problem* p, const T* table, int B, int N, const T* z0,        \
@@ -469,22 +500,11 @@ int pddp_search_candidates(int mode) {
     return pddp::nominal_rollout_impl<T>(p, true, table, B, N, z0, U, u_min,   \
                                          u_max, mask, Z, stream);              \
   }                                                                            \
-  int pddp_derivs_batch_##SUF(                                                 \
-      const pddp_problem* p, const T* table, int B, int N, const T* Z,         \
-      const T* U, const T* u_min, const T* u_max, const uint8_t* mask, T* rec, \
-      T* L, T* J, int32_t* state, void* stream) {                              \
-    return pddp::derivs_impl<T>(p, true, table, B, N, Z, U, u_min, u_max,      \
-                                mask, rec, L, J, state, stream);               \
-  }                                                                            \
-  int pddp_line_search_batch_##SUF(                                            \
-      const pddp_problem* p, const T* table, int B, int N, int A, const T* Z,  \
-      const T* U, const T* gains, const T* alphas, const T* u_min,             \
-      const T* u_max, const uint8_t* active, const int32_t* bwd_status, T* Zc, \
-      T* Uc, T* Jc, void* stream) {                                            \
-    return pddp::line_search_impl<T>(p, true, table, B, N, A, Z, U, gains,     \
-                                     alphas, u_min, u_max, active, bwd_status, \
-                                     Zc, Uc, Jc, stream);                      \
-  }
+  /* the records and the line search: five forms each (goal_form.hpp) */       \
+  PDDP_FORM_ENTRY_POINTS(derivs, SUF, T, PDDP_DERIVS_PARAMS,                   \
+                         PDDP_DERIVS_ARGS)                                     \
+  PDDP_FORM_ENTRY_POINTS(line_search, SUF, T, PDDP_SEARCH_PARAMS,              \
+                         PDDP_SEARCH_ARGS)
 
 PDDP_PROBLEM_ENTRY_POINTS(f32, float)
 PDDP_PROBLEM_ENTRY_POINTS(f64, double)

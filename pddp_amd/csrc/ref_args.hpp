@@ -1,6 +1,6 @@
 // ref_args.hpp - where the kernels with a goal PER TIME STEP take their goals
-// from: what tracking.hip, track_weights.hip, closed_loop.hip, mpc_advance.hip
-// and mpc_advance_noise.hip share.  The layout of `ref` is include/pddp_hip.h's
+// from: what goal_kernels.hpp, closed_loop.hip, mpc_advance.hip and
+// mpc_advance_noise.hip share.  The layout of `ref` is include/pddp_hip.h's
 // (PDDP_REF_*); DESIGN.md 3.4e.
 #pragma once
 

@@ -13,6 +13,7 @@
 #include "problem_args.hpp"
 #include "model_params.hpp"
 #include "ref_args.hpp"
+#include "goal_form.hpp"
 #include "closed_loop_args.hpp"
 #include "closed_loop_draws.hpp"
 
@@ -148,38 +149,7 @@ PDDP_DEV void hand_over() {
 
 // ---- host path -----------------------------------------------------------------
 
-// What an entry point's suffix brings: `batch` promises the table, `track`
-// the reference, `weighted` the weights; what a suffix does not name is
-// absent.  `goals`: the family's goals kernel (every suffix but _batch).
-template <typename T>
-struct SampledForm {
-  bool batch, goals, track, weighted;
-  const T* table;
-  const T* ref;
-  int ref_len, ref_t0;
-  const T* weights;
-};
-
-// the reference and the weights of a launch
-template <typename T>
-struct SampledGoals {
-  RefArgs<T> goals;
-  const T* weights;  // [B][PDDP_WEIGHT_ROW] or NULL
-};
-
-// What the form promises is there: the table, the reference with ref_t0
-// clamped (ref_args), the weights.
-template <typename T>
-static bool sampled_goals(const SampledForm<T>& f, SampledGoals<T>* out) {
-  *out = SampledGoals<T>{RefArgs<T>{f.table, nullptr, 0, 0}, nullptr};
-  if (f.batch && f.table == nullptr) return false;
-  if (f.track &&
-      !ref_args(f.table, f.ref, f.ref_len, f.ref_t0, &out->goals))
-    return false;
-  if (f.weighted && f.weights == nullptr) return false;
-  if (f.weighted) out->weights = f.weights;
-  return true;
-}
+// (GoalForm, FormGoals, form_goals: goal_form.hpp)
 
 // The mapping is closed_loop's: its geometry.  Sets a.G.
 template <typename Args>
@@ -225,37 +195,4 @@ static int launch_sampled(void (*kernel)(ProblemT<T>, Args, Extra...),
 #define PDDP_MPPI_ARGS                                                         \
   B, N, S, z0, U, u_min, u_max, a_std, lam, smooth, seed, sample_offset,       \
       active, Jc, best, J_best, W, J_w, Z_out, U_out, stream
-
-// The five entry points of one family (NAME: shoot, mppi) over its one impl.
-#define PDDP_SAMPLED_ENTRY_POINTS(NAME, SUF, T, PARAMS, ARGS)                  \
-  int pddp_##NAME##_##SUF(const pddp_problem* p, PARAMS(T)) {                  \
-    return pddp::NAME##_impl<T>(                                               \
-        p, {false, false, false, false, nullptr, nullptr, 0, 0, nullptr},      \
-        ARGS);                                                                 \
-  }                                                                            \
-  /* the same with a problem per trajectory: row b of `table` */               \
-  int pddp_##NAME##_batch_##SUF(const pddp_problem* p, const T* table,         \
-                                PARAMS(T)) {                                   \
-    return pddp::NAME##_impl<T>(                                               \
-        p, {true, false, false, false, table, nullptr, 0, 0, nullptr}, ARGS);  \
-  }                                                                            \
-  /* under the line search's objective: thin fronts over the goals kernel */   \
-  int pddp_##NAME##_track_##SUF(const pddp_problem* p, const T* table,         \
-                                const T* ref, int ref_len, int ref_t0,         \
-                                PARAMS(T)) {                                   \
-    return pddp::NAME##_impl<T>(                                               \
-        p, {false, true, true, false, table, ref, ref_len, ref_t0, nullptr},   \
-        ARGS);                                                                 \
-  }                                                                            \
-  int pddp_##NAME##_weighted_##SUF(const pddp_problem* p, const T* table,      \
-                                   const T* weights, PARAMS(T)) {              \
-    return pddp::NAME##_impl<T>(                                               \
-        p, {false, true, false, true, table, nullptr, 0, 0, weights}, ARGS);   \
-  }                                                                            \
-  int pddp_##NAME##_track_weighted_##SUF(                                      \
-      const pddp_problem* p, const T* table, const T* ref, int ref_len,        \
-      int ref_t0, const T* weights, PARAMS(T)) {                               \
-    return pddp::NAME##_impl<T>(                                               \
-        p, {false, true, true, true, table, ref, ref_len, ref_t0, weights},    \
-        ARGS);                                                                 \
-  }
+// (the five entry points of one family: PDDP_FORM_ENTRY_POINTS, goal_form.hpp)

@@ -156,16 +156,16 @@ static int launch_shoot(const pddp_problem& p, ShootArgs<T> a, hipStream_t st) {
 
 template <typename T, int MODEL>
 static int launch_shoot_goals(const pddp_problem& p,
-                              With<ShootGoalsArgs<T>, SampledGoals<T>> w,
+                              With<ShootGoalsArgs<T>, FormGoals<T>> w,
                               hipStream_t st) {
   return launch_sampled<T>(shoot_goals_kernel<T, MODEL>, p, w.a, st, w.x.goals,
                            w.x.weights);
 }
 
 // One impl and one argument test for the five entry-point families: what a
-// form does not bring is null (sampled_common.hpp).
+// form does not bring is null (goal_form.hpp).
 template <typename T>
-static int shoot_impl(const pddp_problem* p, const SampledForm<T>& f,
+static int shoot_impl(const pddp_problem* p, const GoalForm<T>& f,
                       PDDP_SHOOT_PARAMS(T)) {
   if (B <= 0 || N <= 0 || S <= 0 || (long long)B * S > 0x7fffffffLL || !z0 ||
       !U || !a_std || !Jc || !best ||
@@ -173,8 +173,8 @@ static int shoot_impl(const pddp_problem* p, const SampledForm<T>& f,
       (U_out != nullptr && (U_out == U || Z_out == z0)) ||
       !(smooth >= 0.0 && smooth < 1.0))  // (NaN fails both)
     return PDDP_E_BADARG;
-  With<ShootGoalsArgs<T>, SampledGoals<T>> w{};
-  if (!sampled_goals(f, &w.x)) return PDDP_E_BADARG;
+  With<ShootGoalsArgs<T>, FormGoals<T>> w{};
+  if (!form_goals(f, &w.x)) return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
   const T beta = (T)smooth, gamma = (T)std::sqrt(1.0 - smooth * smooth);
   if (f.goals) {
@@ -210,7 +210,7 @@ static int shoot_draws_impl(int B, int N, int S, int m, uint64_t seed,
 extern "C" {
 
 #define PDDP_SHOOT_ENTRY_POINTS(SUF, T)                                        \
-  PDDP_SAMPLED_ENTRY_POINTS(shoot, SUF, T, PDDP_SHOOT_PARAMS, PDDP_SHOOT_ARGS) \
+  PDDP_FORM_ENTRY_POINTS(shoot, SUF, T, PDDP_SHOOT_PARAMS, PDDP_SHOOT_ARGS) \
   int pddp_shoot_draws_##SUF(int B, int N, int S, int m, uint64_t seed,        \
                              uint64_t sample_offset, T* E, void* stream) {     \
     return pddp::shoot_draws_impl<T>(B, N, S, m, seed, sample_offset, E,       \

@@ -1,8 +1,8 @@
 // track_goal_hooks.inc - the goal hooks of derivs_body.inc (TAKE_X, TAKE_U) and
 // line_search_body.inc (TAKE_FIRST, NEXT_ROW, PREFETCH_NEXT, TAKE_NEXT) with a
-// goal PER TIME STEP: the text the kernels of tracking.hip and
-// track_weights.hip define ahead of their bodies; the including unit undefines
-// them behind its last kernel.  The including kernel has `goals` (RefArgs,
+// goal PER TIME STEP: the text the track_* and track_weighted_* kernels of
+// goal_kernels.hpp define ahead of their bodies; the including header undefines
+// them behind each pair of kernels.  The including kernel has `goals` (RefArgs,
 // ref_args.hpp), `P` (its PDDP_PROBLEM_OF_B) and the body's `b`, `t`, `m`, `D`.
 #define PDDP_GOALS(point) PDDP_GOALS_##point
 

@@ -1,6 +1,6 @@
 """Per-trajectory cost weights (ILQRSolver.set_batch_weights, the
-pddp_*_weighted_* entry points of csrc/weights.hip): every trajectory of the
-batch with its own diagonals of Q, Q_term and R, against the CPU oracle run
+pddp_*_weighted_* entry points of csrc/goal_kernels.hpp): every trajectory of
+the batch with its own diagonals of Q, Q_term and R, against the CPU oracle run
 once per trajectory on that trajectory's own problem.
 
 The weights (q = shared diagonal x U(1, 2) + U(0, 0.5), q_term and r = shared

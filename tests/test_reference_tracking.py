@@ -1,6 +1,6 @@
 """Reference tracking (ILQRSolver.set_reference, the pddp_*_track_* entry
-points of csrc/tracking.hip and csrc/mpc_advance.hip): a goal per time step in
-the derivative records, the line search and the MPC hand-over.
+points of csrc/goal_kernels.hpp and csrc/mpc_advance.hip): a goal per time step
+in the derivative records, the line search and the MPC hand-over.
 
 The oracle takes one goal per pddp_problem, but Oracle.cost / Oracle.dynamics
 are per step: every expected value here is composed from them with a problem

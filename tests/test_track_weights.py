@@ -1,6 +1,6 @@
 """A reference tracked under per-trajectory cost weights (ILQRSolver with
 set_reference AND set_batch_weights, the pddp_*_track_weighted_* entry points
-of csrc/track_weights.hip): a goal per time step and every trajectory's own
+of csrc/goal_kernels.hpp): a goal per time step and every trajectory's own
 diagonals of Q, Q_term and R in the derivative records, the line search, the
 rounds of an MPC trial and a captured round.
 

@@ -1,5 +1,5 @@
 """What per-trajectory cost weights cost (ILQRSolver.set_batch_weights, the
-weighted_* kernels of csrc/weights.hip): cartpole f32, 4096 trajectories,
+weighted_* kernels of csrc/goal_kernels.hpp): cartpole f32, 4096 trajectories,
 horizon 100, bounded, the fit's ten step sizes; every row of the weights (and
 of the table) is the shared problem's, so all legs do the same work.
 

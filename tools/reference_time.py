@@ -1,5 +1,5 @@
 """What a goal per time step costs (ILQRSolver.set_reference, the track_*
-kernels of csrc/tracking.hip and csrc/mpc_advance.hip): cartpole f32, 4096
+kernels of csrc/goal_kernels.hpp and csrc/mpc_advance.hip): cartpole f32, 4096
 trajectories, horizon 100, bounded, the fit's ten step sizes.  Every row of
 the table is the shared problem and every row of the reference its goals, so
 both legs of a pair do

@@ -1,6 +1,6 @@
 """What per-trajectory cost weights cost next to a reference (ILQRSolver with
 set_reference and set_batch_weights, the track_weighted_* kernels of
-csrc/track_weights.hip): cartpole f32, 4096 trajectories, horizon 100, bounded,
+csrc/goal_kernels.hpp): cartpole f32, 4096 trajectories, horizon 100, bounded,
 the fit's ten step sizes; every row of the weights holds the shared diagonals
 and every row of the reference the problem's own goals, so all legs do the same
 work.  The method of tools/batch_weights_time.py.
