@@ -510,6 +510,8 @@ def test_no_test_module_is_imported_for_its_helpers():
             {"F32_RATIO", "_check_gains", "_f32_ok"},
         ("tests/test_cartpole_branches.py", "test_gpu_parity"):
             {"STATS", "_check_gains"},
+        ("tests/test_matrix_sweeps.py", "test_gpu_parity"):
+            {"F32_RATIO", "_check_gains", "_f32_ok"},
     }
     plain = re.compile(r"^\s*import\s+(.+)$")
     bad = []
