@@ -576,6 +576,110 @@ int pddp_mppi_batch_f64(const pddp_problem* problem, const double* table,
                         double* J_w, double* Z_out, double* U_out,
                         void* stream);
 
+/* ---- sampled shooting with a cross-entropy (CEM) refit: the candidates of
+ * pddp_shoot_* above drawn with a width per time step and action component
+ * around the mean U, the K cheapest ("elites") ranked out inside the launch,
+ * and the mean AND the width refitted to them; the new mean rolled out and
+ * costed inside the launch (csrc/cem.hip; the reference has no counterpart).
+ * Trajectory b, candidate s, r = sample_offset + b S + s:
+ *
+ *   e_{s,t}          pddp_shoot_*'s draws and AR(1), word for word (stream 2,
+ *                    explicit fmas)
+ *   u_{s,t}[j]     = clamp(fma(sigma[b][t][j], e_{s,t}[j], U[b][t][j]))    s >= 1
+ *   u_{0,t}        = clamp(U[b][t])                  the mean is a candidate
+ *   Jc[b][s]         the open-loop cost, as pddp_shoot_*
+ *   rank[b][s]     = #{ s' : Jc[b][s'] finite and (Jc[b][s'], s') <
+ *                    (Jc[b][s], s) lexicographically } where Jc[b][s] is
+ *                    finite, else -1
+ *   Ke[b]          = min(K, number of finite costs)
+ *   elite(s)      <=> 0 <= rank[b][s] < K
+ *   best[b]        = the s of rank 0 (-1 without a finite cost);
+ *   J_best[b]      = the bits of Jc[b][best[b]]
+ *   s1_t[j]        = sum over elites s >= 1 of e_{s,t}[j]
+ *   s2_t[j]        = sum over elites s >= 1 of fma(e, e, 0)   (each term rounded
+ *                    before it meets a sum; candidate 0 counts in Ke and adds
+ *                    nothing)
+ *   ebar           = s1 / Ke
+ *   V              = Ke > 1 ? max(fma(-ebar, ebar, s2 / Ke), 0) : 0
+ *   g              = step * sigma[b][t][j]          (rounded)
+ *   Um[b][t][j]    = clamp(fma(g, ebar, U[b][t][j]))
+ *   sd             = sigma[b][t][j] * sqrt(V)       (rounded)
+ *   Sm[b][t][j]    = max(fma(step, sd - sigma[b][t][j], sigma[b][t][j]),
+ *                        std_min[j])
+ *   Zm[b], J_m[b]    the open-loop rollout of Um[b] from z0[b] under f_b, and
+ *                    its cost (stage costs in t order, then the terminal one)
+ *
+ * The refit is in the raw AR(1) values e, as pddp_mppi_*'s mean is: they are
+ * of unit scale whatever the width has become, so the variance does not cancel
+ * badly when the distribution narrows.  step = 1 - mix, formed on the host in
+ * double and then cast to the run's type: mix = 0 replaces the distribution by
+ * the elites' fit, mix towards 1 keeps more of the old one.
+ *
+ * Arguments beside pddp_shoot_*'s: K, 1 <= K <= S, after S; sigma [B][N][m] in
+ * a_std's place, entries >= 0 the caller's business; std_min [m] behind it,
+ * nullable: zeros; mix in [0, 1) next to smooth.  Jc [B][S] out.  rank [B][S]
+ * int32 out, nullable.  best [B] out.  J_best [B] out, nullable.  n_elite [B]
+ * int32 out: Ke.  J_m [B] out.  Z_out [B][N+1][n], U_out [B][N][m], S_out
+ * [B][N][m] out, all three or none, receive Zm, Um, Sm (shoot's aliasing
+ * rules, S_out against sigma as U_out against U); with S > 256 the running
+ * sums over a lane's turns are kept in U_out (s1) and S_out (s2), so the three
+ * are required then.  Without a finite cost: best[b] = -1, J_best[b] = J_m[b]
+ * = +inf, n_elite[b] = 0, the ranks are -1 and row b of Z_out / U_out / S_out
+ * is not written (Jc[b] is).  active [B] nullable: nothing of a skipped
+ * trajectory is read or written.  pddp_cem_batch_* takes `table`
+ * [B][PDDP_BATCH_ROW] as pddp_mppi_batch_*.
+ *
+ * The order of every sum and of the ranking depends on S alone, never on b or
+ * B.  The ranking is exact integer work on (Jc, s).  s1 and s2, per step and
+ * component, with G and the turns as pddp_mppi_*'s: the group's sum of turn 0,
+ * then that of turn 1 added to it, and so on; a sum over the group is the
+ * butterfly with partner distances 1, 2, 4, ... (lanes without an elite add
+ * +0), then the wavefronts in their order.  No atomics: a trajectory's outputs
+ * are the same bits wherever it sits in the batch, and with sample_offset +
+ * b0 S they are the same bits when trajectories b0.. run alone.
+ *
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY.
+ * PDDP_E_BADARG: pddp_shoot_*'s list, with sigma in a_std's place; a null
+ * n_elite or J_m; K < 1 or K > S; mix outside [0, 1) or NaN; some but not all
+ * of Z_out / U_out / S_out; U_out == U, S_out == sigma or Z_out == z0; S > 256
+ * without the rows.  PDDP_E_UNSUPPORTED: any other encoding.  All before any
+ * HIP call. */
+int pddp_cem_f32(const pddp_problem* problem, int B, int N, int S, int K,
+                 const float* z0, const float* U, const float* u_min,
+                 const float* u_max, const float* sigma, const float* std_min,
+                 double smooth, double mix, uint64_t seed,
+                 uint64_t sample_offset, const uint8_t* active, float* Jc,
+                 int32_t* rank, int32_t* best, float* J_best, int32_t* n_elite,
+                 float* J_m, float* Z_out, float* U_out, float* S_out,
+                 void* stream);
+int pddp_cem_f64(const pddp_problem* problem, int B, int N, int S, int K,
+                 const double* z0, const double* U, const double* u_min,
+                 const double* u_max, const double* sigma,
+                 const double* std_min, double smooth, double mix,
+                 uint64_t seed, uint64_t sample_offset, const uint8_t* active,
+                 double* Jc, int32_t* rank, int32_t* best, double* J_best,
+                 int32_t* n_elite, double* J_m, double* Z_out, double* U_out,
+                 double* S_out, void* stream);
+int pddp_cem_batch_f32(const pddp_problem* problem, const float* table, int B,
+                       int N, int S, int K, const float* z0, const float* U,
+                       const float* u_min, const float* u_max,
+                       const float* sigma, const float* std_min, double smooth,
+                       double mix, uint64_t seed, uint64_t sample_offset,
+                       const uint8_t* active, float* Jc, int32_t* rank,
+                       int32_t* best, float* J_best, int32_t* n_elite,
+                       float* J_m, float* Z_out, float* U_out, float* S_out,
+                       void* stream);
+int pddp_cem_batch_f64(const pddp_problem* problem, const double* table, int B,
+                       int N, int S, int K, const double* z0, const double* U,
+                       const double* u_min, const double* u_max,
+                       const double* sigma, const double* std_min,
+                       double smooth, double mix, uint64_t seed,
+                       uint64_t sample_offset, const uint8_t* active,
+                       double* Jc, int32_t* rank, int32_t* best,
+                       double* J_best, int32_t* n_elite, double* J_m,
+                       double* Z_out, double* U_out, double* S_out,
+                       void* stream);
+
 /* ---- a receding-horizon MPPI trial, every control step inside ONE launch:
  * plan by K iterations of pddp_mppi_*'s law around the plan U, apply the first
  * action to the plant, observe, shift the plan (csrc/mppi_trial.hip; the

@@ -74,6 +74,10 @@ _STEP, _STEP_OUT = [c_int] * 4 + [_P] * 7, [_P] * 14
 _SHOOT = [c_int] * 3 + [_P] * 5 + [c_double, c_uint64, c_uint64] + [_P] * 7
 # (its weighted update: lam after a_std; W and J_w after J_best)
 _MPPI = [c_int] * 3 + [_P] * 6 + [c_double, c_uint64, c_uint64] + [_P] * 9
+# (its cross-entropy refit: K after S; sigma, std_min; smooth, mix; the mask,
+# Jc, rank, best, J_best, n_elite, J_m, the three row outputs, the stream)
+_CEM = [c_int] * 4 + [_P] * 6 + [c_double, c_double, c_uint64, c_uint64] + \
+    [_P] * 11
 # (the records and the line search, what every form takes behind its leading
 # arguments: B N, Z .. state, stream; B N A, Z .. Jc, stream.  The forms lead
 # with the problem; _batch adds the table; _track the table and the window;
@@ -107,6 +111,8 @@ _SIGS = {
     "pddp_shoot_draws": [c_int] * 4 + [c_uint64, c_uint64, _P, _P],
     "pddp_mppi": [_P] + _MPPI,
     "pddp_mppi_batch": [_P, _P] + _MPPI,
+    "pddp_cem": [_P] + _CEM,
+    "pddp_cem_batch": [_P, _P] + _CEM,
     # (a whole MPPI trial: problem, table, plant; B N S K TT t0 count; z0 ..
     # lam; smooth, seed, cand_offset, iter_stride; disturbance, w_std, v_std;
     # rollout_offset, step_offset; x_true, active, Jc; log_costs; the logs)
@@ -200,6 +206,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_closed_loop_track",
           "pddp_shoot", "pddp_shoot_batch", "pddp_shoot_draws",
           "pddp_mppi", "pddp_mppi_batch", "pddp_mppi_trial",
+          "pddp_cem", "pddp_cem_batch",
           "pddp_shoot_track", "pddp_shoot_weighted",
           "pddp_shoot_track_weighted", "pddp_mppi_track", "pddp_mppi_weighted",
           "pddp_mppi_track_weighted", "pddp_mppi_trial_goals",

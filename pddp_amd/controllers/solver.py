@@ -1312,6 +1312,122 @@ class ILQRSolver(object):
         self.reset_controller_state()
         return out
 
+    def _width(self, what, std):
+        """[B][N][m] device tensor, a private copy, of a width given as a
+        float, an [m] vector or a [B][N][m] tensor (the `std` a `cem` call
+        returned)."""
+        shape = (self.B, self.N, self.m)
+        std = torch.as_tensor(std, dtype=self.dtype, device=self.device)
+        if std.dim() == 0 or tuple(std.shape) == (self.m,):
+            return std.expand(shape).contiguous()
+        if tuple(std.shape) != shape:
+            raise _native.NativeError(
+                "%s: std has shape %s, expected a scalar, (%d,) or %s" % (
+                    what, tuple(std.shape), self.m, shape))
+        return std.clone().contiguous()
+
+    @_on_device
+    def cem(self, samples, std, elites, iterations=1, std_min=0.0, mix=0.0,
+            smooth=0.0, seed=0, sample_offset=0, active=None, adopt=True,
+            events=None):
+        """Sampled shooting with a cross-entropy (CEM) refit of the
+        distribution the candidates are drawn from (pddp_cem_*, csrc/cem.hip):
+        `shoot`'s S = `samples` candidates around the mean - the current `U` -
+        with a width per time step and action component, costed by the same
+        law; the K = `elites` cheapest finite ones are ranked out inside the
+        launch and the mean and the width are refitted to them, the new mean
+        is rolled out and costed in the same launch.  `std`: a float, an [m]
+        vector or a [B][N][m] tensor, such as the `std` an earlier call
+        returned.  `std_min`: a float or [m], the floor of the refitted width.
+        `mix` in [0, 1): the share of the old distribution kept in the new one
+        (0: the elites' fit alone).  `smooth`, `seed`, `sample_offset`,
+        `active`: as `shoot`.
+
+        `iterations` launches follow each other on private copies: iteration k
+        draws with `sample_offset` + k B S around the distribution iteration
+        k - 1 left, which moves for every trajectory with an elite (a
+        device-side select, no host synchronisation).  Next to the
+        distribution the call carries an incumbent: the start, replaced by an
+        iteration's mean where isfinite(J_m) & (J_m <= the carried cost) - so
+        the call is never worse than its start, as `shoot` and `mppi`.
+
+        Returns an object with `J` [B][S], `rank` [B][S] int32 (-1: not
+        finite), `best` [B] int32, `J_best` [B], `n_elite` [B] int32, `J_m`
+        [B] (the cost of the refitted mean; +inf without a finite candidate) -
+        those of the LAST iteration; of a masked trajectory NaN / -1 / 0 -,
+        `mean` [B][N][m] and `std` [B][N][m], the final distribution, and
+        `J_trace` [iterations + 1][B]: the start's cost, then the incumbent's
+        after each iteration.
+
+        `adopt=True`: `U` and `Z` take the incumbent's rows in place and the
+        controller state is re-armed, as `shoot` does.  `adopt=False`: nothing
+        of the solver is touched; the object also has `Z` and `U`, the
+        incumbent's rows.  `events`: a (start, stop) pair for the dispatch,
+        with one iteration only.
+
+        Refused while a reference or per-trajectory cost weights are set: the
+        candidates would be costed under another objective than the line
+        search's."""
+        self._need_sample_problem("cem")
+        self._one_sampled_objective("cem")
+        B, N, n, m = self.B, self.N, self.n, self.m
+        S, K, iters = int(samples), int(elites), int(iterations)
+        if S < 1:
+            raise _native.NativeError("cem: %d samples" % S)
+        if not 1 <= K <= S:
+            raise _native.NativeError(
+                "cem: %d elites of %d samples" % (K, S))
+        if iters < 1:
+            raise _native.NativeError("cem: %d iterations" % iters)
+        if events is not None and iters > 1:
+            raise _native.NativeError(
+                "cem: events time ONE dispatch, %d iterations are %d" % (
+                    iters, iters))
+        sigma = self._width("cem", std)
+        floor = self._action_std(std_min, "cem")
+        self._check_active("cem", active)
+        masked = active is not None
+        p = _native.ptr
+        mean = self.U.clone()
+        U, Z = self.U.clone(), self.Z.clone()  # the incumbent
+        J_trace = torch.empty(iters + 1, B, dtype=self.dtype,
+                              device=self.device)
+        for k in range(iters):
+            out = types.SimpleNamespace(
+                J=self._out(masked, B, S),
+                rank=self._out(masked, B, S, dtype=torch.int32, fill=-1),
+                best=self._out(masked, B, dtype=torch.int32, fill=-1),
+                J_best=self._out(masked, B),
+                n_elite=self._out(masked, B, dtype=torch.int32, fill=0),
+                J_m=self._out(masked, B))
+            # (rows without a refit are never selected)
+            Zm, Um = self._out(False, B, N + 1, n), self._out(False, B, N, m)
+            Sm = self._out(False, B, N, m)
+            self._launch(events, self._problem_call, "pddp_cem", B, N, S, K,
+                         p(self.z0), p(mean), p(self.u_min), p(self.u_max),
+                         p(sigma), p(floor), float(smooth), float(mix),
+                         int(seed), int(sample_offset) + k * B * S, p(active),
+                         p(out.J), p(out.rank), p(out.best), p(out.J_best),
+                         p(out.n_elite), p(out.J_m), p(Zm), p(Um), p(Sm),
+                         self._s())
+            if k == 0:
+                J_trace[0] = out.J[:, 0]
+            better = torch.isfinite(out.J_m) & (out.J_m <= J_trace[k])
+            take = better.reshape(B, 1, 1)
+            U, Z = torch.where(take, Um, U), torch.where(take, Zm, Z)
+            J_trace[k + 1] = torch.where(better, out.J_m, J_trace[k])
+            moved = (out.n_elite > 0).reshape(B, 1, 1)
+            mean = torch.where(moved, Um, mean)
+            sigma = torch.where(moved, Sm, sigma)
+        out.mean, out.std, out.J_trace = mean, sigma, J_trace
+        if not adopt:
+            out.Z, out.U = Z, U
+            return out
+        self.U.copy_(U)
+        self.Z.copy_(Z)
+        self.reset_controller_state()
+        return out
+
     def _one_sampled_objective(self, what, objective="shared"):
         """The `objective` of `shoot`, `mppi` and `mppi_closed_loop`.
         "shared": the refusal while a reference or per-trajectory cost

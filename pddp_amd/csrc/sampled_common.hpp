@@ -1,6 +1,7 @@
 // sampled_common.hpp - what the sampling planners share (shoot.hip, mppi.hip,
-// mppi_trial.hip): the draws' stream, the order of an argmin,
-// the softmin weight, the sum over a lane group, the hand-over inside a launch,
+// mppi_trial.hip, cem.hip): the draws' stream, the order
+// of an argmin and of a ranking, the softmin weight, the sum over a lane
+// group, the hand-over inside a launch,
 // the hooks through which a family's ONE kernel text (*_kernel_body.inc)
 // reaches the problem of trajectory b - the plain kernel's table row, or the
 // goals kernel's reference and weights - and the host path's common pieces.
@@ -32,6 +33,8 @@ PDDP_DEV void take_lower(T& J, int& s, T oJ, int os) {
 
 PDDP_DEV float exp_of(float x) { return expf(x); }
 PDDP_DEV double exp_of(double x) { return exp(x); }
+PDDP_DEV float sqrt_of(float x) { return sqrtf(x); }
+PDDP_DEV double sqrt_of(double x) { return sqrt(x); }
 
 // w_s: 1 for the best candidate (the exponent is -0), 0 for a cost that is
 // not finite.  The difference and the quotient are rounded one by one.
@@ -195,4 +198,16 @@ static int launch_sampled(void (*kernel)(ProblemT<T>, Args, Extra...),
 #define PDDP_MPPI_ARGS                                                         \
   B, N, S, z0, U, u_min, u_max, a_std, lam, smooth, seed, sample_offset,       \
       active, Jc, best, J_best, W, J_w, Z_out, U_out, stream
+// (cem: K after S; sigma [B][N][m] in a_std's place, std_min [m] behind it;
+// mix next to smooth; rank, n_elite, J_m and the third row output S_out)
+#define PDDP_CEM_PARAMS(T)                                                     \
+  int B, int N, int S, int K, const T* z0, const T* U, const T* u_min,         \
+      const T* u_max, const T* sigma, const T* std_min, double smooth,         \
+      double mix, uint64_t seed, uint64_t sample_offset,                       \
+      const uint8_t* active, T* Jc, int32_t* rank, int32_t* best, T* J_best,   \
+      int32_t* n_elite, T* J_m, T* Z_out, T* U_out, T* S_out, void* stream
+#define PDDP_CEM_ARGS                                                          \
+  B, N, S, K, z0, U, u_min, u_max, sigma, std_min, smooth, mix, seed,          \
+      sample_offset, active, Jc, rank, best, J_best, n_elite, J_m, Z_out,      \
+      U_out, S_out, stream
 // (the five entry points of one family: PDDP_FORM_ENTRY_POINTS, goal_form.hpp)

@@ -11,12 +11,23 @@
 //                           the kernel was compiled with at this place (a
 //                           hook for statement order alone: shoot.hip)
 //   PDDP_SAMPLED_KEEP_ROW   after the clamp: empty, or the stores of row t
+//   PDDP_SAMPLED_WIDTH(r)   optional, with PDDP_SAMPLED_WIDTH_REQUEST: the
+//                           width of component r at step t, and what asks for
+//                           row t + 1 of a width per step next to `ur2`
+//                           (cem.hip's sigma[b]).  A kernel that defines
+//                           neither draws with `astd[r]` and asks for nothing:
+//                           the text of the six kernels as it was.
 //   PDDP_GOALS(point)       TAKE_FIRST ahead of the time loop, REQUEST_NEXT
 //                           behind the step's draws (row t + 1, ahead of the
 //                           dependent chain), TAKE_NEXT at the end of the step
 //                           (up to row N, the terminal cost's)
 // It leaves `z` (x_N) and `J` in the including scope.  An included text, not
 // a device function: csrc/Makefile's note on contraction (DESIGN.md 3.4f).
+#ifndef PDDP_SAMPLED_WIDTH
+#define PDDP_SAMPLED_WIDTH(r) astd[r]
+#define PDDP_SAMPLED_WIDTH_REQUEST
+#define PDDP_SAMPLED_WIDTH_IS_ASTD
+#endif
       T z[n], zn[n], un[m], ur[m], e[m];
 #pragma unroll
       for (int j = 0; j < n; ++j) z[j] = z0[j];
@@ -32,11 +43,13 @@
         const int tn = (t + 1 < N) ? t + 1 : t;
 #pragma unroll
         for (int j = 0; j < m; ++j) ur2[j] = Ub[tn * m + j];
+        PDDP_SAMPLED_WIDTH_REQUEST
         draw_units<T, m>(a.seed, roll, t + 1, kSampledStream, xi);
         PDDP_GOALS(REQUEST_NEXT)
 #pragma unroll
         for (int r = 0; r < m; ++r) {
-          const T v = base ? ur[r] : fma_of(astd[r], e[r], ur[r]);
+          const T v =
+              base ? ur[r] : fma_of(PDDP_SAMPLED_WIDTH(r), e[r], ur[r]);
           un[r] = bounded ? clamp_nan(v, umin[r], umax[r]) : v;
         }
         PDDP_SAMPLED_KEEP_ROW
@@ -53,3 +66,8 @@
         PDDP_GOALS(TAKE_NEXT)
       }
       J += cost_value<T, MODEL>(P, z, nullptr, trig_of<T, MODEL>(z), true);
+#ifdef PDDP_SAMPLED_WIDTH_IS_ASTD
+#undef PDDP_SAMPLED_WIDTH_IS_ASTD
+#undef PDDP_SAMPLED_WIDTH_REQUEST
+#undef PDDP_SAMPLED_WIDTH
+#endif
