@@ -274,6 +274,23 @@ def ptr(t):
     return t.data_ptr()
 
 
+def set_pointers(st, **tensors):
+    """Pointer fields of a structure from tensors (None -> NULL).  The
+    structure holds no reference: the caller keeps the tensors alive."""
+    for name, t in tensors.items():
+        setattr(st, name, ptr(t))
+
+
+def set_angles(st, ang, non):
+    """n_ang, n_non, ang[], non[] of a structure: the angular and the other
+    indices of the state, in the order of the augmented features."""
+    st.n_ang, st.n_non = len(ang), len(non)
+    for i, v in enumerate(ang):
+        st.ang[i] = int(v)
+    for i, v in enumerate(non):
+        st.non[i] = int(v)
+
+
 def stream_handle(device=None):
     return torch.cuda.current_stream(device).cuda_stream
 

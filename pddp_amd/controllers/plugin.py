@@ -16,31 +16,113 @@ the way the reference does, batched over B trajectories:
 
 Nothing here runs on the CPU; tensors must be CUDA tensors.
 """
+import ctypes
+import os
+
 import torch
 
 from .. import _native
+from ..costs.base import AggregateCost
+from ..costs.quadratic import QRCost
+from ..examples._common import AugmentedQRCost
+from ..utils.angular import (augment_moments, augment_moments_var,
+                             augment_state)
 from ..utils.constraint import clamp
+from ..utils.encoding import (StateEncoding, decode_covar, decode_covar_sqrt,
+                              decode_mean, decode_var)
 
 
-def _augmented_forward():
-    from ..examples._common import AugmentedQRCost
-    return AugmentedQRCost.forward
+def _vec(t, k, opts):
+    """A scalar or vector of a module as k contiguous numbers for a kernel."""
+    return torch.as_tensor(t).detach().to(**opts).expand(k).contiguous()
+
+
+def _mat(t, opts):
+    return t.detach().to(**opts).contiguous()
+
+
+def _live_rows(alive, rows):
+    """The live trajectories packed to the front of the network's rows:
+    rank [B] (int32; a live trajectory's slot is rank - 1) and the number of
+    rows the network runs on, `rows` per live trajectory, as an int32 device
+    scalar the kernel reads (sync-free: capturable)."""
+    rank = torch.cumsum(alive.to(torch.int32), 0, dtype=torch.int32)
+    return rank, (rank[-1:] * rows).to(torch.int32)
 
 
 class TorchProblem(object):
     """Adapter with the three problem-dependent operations of ILQRSolver."""
+
+    # switches of the native paths (tests and tools turn them off per instance)
+    use_native_bnn = True      # moment-step rollouts around the fused network
+    use_native_bnn_jvp = True  # forward-mode F_z, F_u (pddp_bnn_jvp_*)
+    use_native_gp = True       # pddp_gp_step_* records and line search
+    use_native_cost = True     # pddp_qr_cost_derivs_*
+    use_gp_rollout = True      # pddp_gp_rollout_* (False: the per-step form)
 
     def __init__(self, model, cost, encoding, model_opts=None, cost_opts=None):
         self.model, self.cost, self.encoding = model, cost, encoding
         self.model_opts = dict(model_opts or {})
         self.cost_opts = dict(cost_opts or {})
 
+    # -- which code runs: each question is answered here and nowhere else ----
+    # (the predicates are looked up and asked at every call: tests replace
+    # them on an instance and flip the switches between calls)
+    def _rollout_path(self, s):
+        """"bnn" (moment-step launches around the network kernel) or "torch"
+        (the model module per time step)."""
+        return "bnn" if self._bnn_native_ok(s) else "torch"
+
+    def _dynamics_path(self, s):
+        """F_z, F_u of `derivs`: "bnn" (forward mode), "gp" (the step kernel
+        with its Jacobian) or "autograd"."""
+        with torch.no_grad():  # (the network's kernel refuses when autograd
+            # could be asked to differentiate through it)
+            if self._bnn_native_ok(s, need_cost=False) and \
+                    self._bnn_jvp_ok(s):
+                return "bnn"
+            if self._gp_native_ok(s):
+                return "gp"
+        return "autograd"
+
+    def _cost_path(self, s):
+        """The cost blocks of `derivs`: "hip" (pddp_qr_cost_derivs_*, an
+        expression tree over it included) or "autograd"."""
+        return "hip" if self._qr_cost_native_ok(s) else "autograd"
+
+    def _line_search_path(self, s):
+        """"bnn", "gp_rollout" (pddp_gp_rollout_*), "gp_step" (torch ops
+        around pddp_gp_step_*) or "generic" (model and cost modules)."""
+        if self._bnn_native_ok(s):
+            return "bnn"
+        if not self._gp_line_search_ok(s):
+            return "generic"
+        mo = self.model
+        if os.environ.get("PDDP_NO_GP_ROLLOUT") or not (
+                self.use_gp_rollout and mo.state_size <= 6 and
+                len(mo.non_angular_indices) + 2 * len(mo.angular_indices) <= 8
+                and s.m <= 4):
+            return "gp_step"
+        return "gp_rollout"
+
+    @torch.no_grad()
+    def capture_ok(self, s):
+        """True when a whole round is HIP launches and sync-free torch ops
+        (native BNN rollout, forward-mode Jacobians, hyper-dual cost
+        derivatives): the round can then be captured into hipGraphs
+        (ILQRSolver.capture_round)."""
+        if self._bnn_native_ok(s) and self._bnn_jvp_ok(s) and \
+                self._qr_cost_native_ok(s):
+            return True
+        # GP plugin: records and line search on pddp_gp_step_*, batched costs
+        return self._gp_line_search_ok(s) and self._qr_cost_native_ok(s)
+
     # -- ilqr.py:457-468 ------------------------------------------------------
     @torch.no_grad()
     def rollout(self, s):
         self.model.eval()
         Z, U = s.Z, s.U
-        if self._bnn_native_ok(s):
+        if self._rollout_path(s) == "bnn":
             # the nominal is the alpha = 0 "candidate" of zero gains
             opts = dict(dtype=s.dtype, device=s.device)
             Z.zero_()
@@ -102,18 +184,6 @@ class TorchProblem(object):
         J = J.reshape(B, n, n + m)
         return J[:, :, :n], J[:, :, n:]
 
-    @torch.no_grad()
-    def capture_ok(self, s):
-        """True when a whole round is HIP launches and sync-free torch ops
-        (native BNN rollout, forward-mode Jacobians, hyper-dual cost
-        derivatives): the round can then be captured into hipGraphs
-        (ILQRSolver.capture_round)."""
-        if self._bnn_native_ok(s) and self._bnn_jvp_ok(s) and \
-                self._qr_cost_native_ok(s):
-            return True
-        # GP plugin: records and line search on pddp_gp_step_*, batched costs
-        return self._gp_line_search_ok(s) and self._qr_cost_native_ok(s)
-
     def derivs(self, s, mask=None, set_state=True, in_graph=False):
         """Fills s.rec, s.L, s.J_opt (and resets s.state) for masked rows.
         `in_graph`: no host synchronisation at all (stream capture): the
@@ -129,37 +199,26 @@ class TorchProblem(object):
         opts = dict(dtype=s.dtype, device=s.device)
         F_z = torch.zeros(B, N, n, n, **opts)
         F_u = torch.zeros(B, N, n, m, **opts)
-        L = torch.zeros(B, N + 1, **opts)
-        L_z = torch.zeros(B, N + 1, n, **opts)
-        L_u = torch.zeros(B, N, m, **opts)
-        L_zz = torch.zeros(B, N + 1, n, n, **opts)
-        L_uz = torch.zeros(B, N, m, n, **opts)
-        L_uu = torch.zeros(B, N, m, m, **opts)
-        with torch.no_grad():  # (the network's kernel refuses when autograd
-            # could be asked to differentiate through it)
-            native_dyn = self._bnn_native_ok(s, need_cost=False) and \
-                self._bnn_jvp_ok(s)
-            gp_dyn = not native_dyn and self._gp_native_ok(s)
-        native_cost = self._qr_cost_native_ok(s)
-        # which code produced the records (tests assert on it)
-        if native_dyn:
+        L, L_z, L_u, L_zz, L_uz, L_uu = self._zero_cost_blocks(s)
+        dyn, cost = self._dynamics_path(s), self._cost_path(s)
+        if dyn == "bnn":
             # (rows of the trajectories whose nominal stands are skipped)
             self._dyn_derivs_bnn(s, F_z, F_u, mask)
-        elif gp_dyn:
+        elif dyn == "gp":
             # GP plugin: every (trajectory, step) row of the nominal in ONE
             # launch of the moment-matched step with its Jacobian
             # (rows of the trajectories whose nominal stands are skipped:
             # their records are kept below)
             self._dyn_derivs_gp(s, F_z, F_u, mask)
-            native_dyn = True
+        native_dyn, native_cost = dyn != "autograd", cost == "hip"
+        # which code produced the records (tests assert on it)
         self.last_derivs_path = {"dynamics": "hip" if native_dyn else "autograd",
-                                 "cost": "hip" if native_cost else "autograd"}
+                                 "cost": cost}
         if native_cost:
             self._cost_derivs_qr(s, L, L_z, L_u, L_zz, L_uz, L_uu)
         with torch.enable_grad():
-            for t in range(N):
-                if native_dyn and native_cost:
-                    break
+            # (nothing is left for autograd when both came from kernels)
+            for t in range(0 if native_dyn and native_cost else N):
                 z = s.Z[:, t].detach()
                 u = s.U[:, t].detach()
                 if s.u_min is not None:  # derivatives AT the clamped action
@@ -201,7 +260,7 @@ class TorchProblem(object):
         mo = self.model
         if not (hasattr(mo, "native_step") and hasattr(mo, "native_form")):
             return False
-        if not getattr(self, "use_native_gp", True) or self.model_opts:
+        if not self.use_native_gp or self.model_opts:
             return False
         # (either form of the kernel: resident or chunked)
         return mo.native_form(s.Z[:, 0], self.encoding,
@@ -228,7 +287,6 @@ class TorchProblem(object):
         """The line search as N launches of the GP step plus ONE batched
         evaluation of the stage costs: needs the sample problems' QR cost on
         the model's own angle-augmented state."""
-        from ..examples._common import AugmentedQRCost
         co, mo = self.cost, self.model
         if not self._gp_native_ok(s) or self.cost_opts:
             return False
@@ -248,11 +306,6 @@ class TorchProblem(object):
         the moments themselves: the reference's encode -> decode round trip of
         the augmented covariance (a Cholesky factorisation per time step) is
         the identity up to its 1e-12 jitter."""
-        from ..utils.angular import (augment_moments, augment_moments_var,
-                                     augment_state)
-        from ..utils.encoding import (StateEncoding, decode_covar,
-                                      decode_covar_sqrt, decode_mean,
-                                      decode_var)
         co, enc = self.cost, self.encoding
         mc = co.model_class
         ai, ni, D = list(mc.angular_indices), list(mc.non_angular_indices), \
@@ -305,8 +358,6 @@ class TorchProblem(object):
         J += ((du @ co.R) * du).sum(-1).sum(1)
         return J
 
-    use_gp_rollout = True  # pddp_gp_rollout_* (False: the per-step torch form)
-
     def cost_generation(self):
         """Identity and version of the cost's tensors whose converted copies
         captured launches read (`_line_search_gp`): a captured round is stale
@@ -324,22 +375,14 @@ class TorchProblem(object):
         """ilqr.py:677-723 + :764-791 for every (trajectory, step size) as a
         device rollout: control law, clamp, moment-matched GP step and stage
         cost in the step's own kernel, N + 1 launches with nothing between
-        them (`pddp_gp_rollout_*`, csrc/gp_step.hip)."""
+        them (`pddp_gp_rollout_*`, csrc/gp_step.hip).  Whether it covers the
+        model: `_line_search_path`."""
         mo, co = self.model, self.cost
-        import os
-        if os.environ.get("PDDP_NO_GP_ROLLOUT"):
-            return self._line_search_gp_torch(s)
-        if not (self.use_gp_rollout and mo.state_size + 0 <= 6 and
-                len(mo.non_angular_indices) + 2 * len(mo.angular_indices) <= 8
-                and s.m <= 4):
-            return self._line_search_gp_torch(s)
-        import ctypes
         g = mo._native_model(s.dtype, s.device, self.encoding)
-        key = (s.dtype, str(s.device)) + tuple(
-            (t.data_ptr(), t._version)
-            for t in (co.Q, co.Q_term, co.R, co.x_goal, co.u_goal))
-        cc = getattr(self, "_gp_cost_cache", None)
         src = (co.Q, co.Q_term, co.R, co.x_goal, co.u_goal)
+        key = (s.dtype, str(s.device)) + tuple(
+            (t.data_ptr(), t._version) for t in src)
+        cc = getattr(self, "_gp_cost_cache", None)
         if cc is not None and cc[0] != key and cc[0][:2] == key[:2] and all(
                 d.shape == t.shape for d, t in zip(cc[1], src)):
             # new values INTO the converted copies: launches baked into a
@@ -354,17 +397,13 @@ class TorchProblem(object):
                                            copy=True).contiguous()
             cc = self._gp_cost_cache = (key, tuple(conv(t) for t in src))
         Q, Qt, R, xg, ug = cc[1]
-        p = _native.ptr
         r = _native.GpRollout()
         r.B, r.N, r.A = s.B, s.N, s.A
-        for name, t in (("Z", s.Z), ("U", s.U), ("gains", s.gains),
-                        ("alphas", s.alphas), ("u_min", s.u_min),
-                        ("u_max", s.u_max), ("active", active),
-                        ("bwd_status", s.bwd_status if use_status else None),
-                        ("Zc", s.Zc), ("Uc", s.Uc), ("Jc", s.Jc), ("Q", Q),
-                        ("Q_term", Qt), ("R", R), ("x_goal", xg),
-                        ("u_goal", ug)):
-            setattr(r, name, p(t))
+        _native.set_pointers(
+            r, Z=s.Z, U=s.U, gains=s.gains, alphas=s.alphas, u_min=s.u_min,
+            u_max=s.u_max, active=active,
+            bwd_status=s.bwd_status if use_status else None, Zc=s.Zc,
+            Uc=s.Uc, Jc=s.Jc, Q=Q, Q_term=Qt, R=R, x_goal=xg, u_goal=ug)
         with torch.cuda.device(s.device):
             _native.call("pddp_gp_rollout", s.dtype, ctypes.byref(g),
                          ctypes.byref(r), _native.stream_handle(s.device))
@@ -402,14 +441,10 @@ class TorchProblem(object):
         last with a constant exponent): its derivatives follow from the
         leaves' by the product / quotient / power rules
         (`_cost_derivs_tree`), no autograd pass per time step."""
-        from ..costs.base import AggregateCost
-        from ..costs.quadratic import QRCost
-        from ..utils.encoding import StateEncoding
-        top = co is None
         co = self.cost if co is None else co
+        if not self.use_native_cost or self.cost_opts:
+            return False
         if isinstance(co, AggregateCost):
-            if not getattr(self, "use_native_cost", True) or self.cost_opts:
-                return False
             if co.op not in (torch.add, torch.sub, torch.mul, torch.div,
                              torch.pow):
                 return False
@@ -424,12 +459,9 @@ class TorchProblem(object):
                    for c in consts):
                 return False
             return all(self._qr_cost_native_ok(s, c) for c in kids)
-        del top
         mc = getattr(co, "model_class", None)
-        if not getattr(self, "use_native_cost", True) or self.cost_opts:
-            return False
         if s.dtype not in (torch.float32, torch.float64) or \
-                type(co).forward is not _augmented_forward() or mc is None:
+                type(co).forward is not AugmentedQRCost.forward or mc is None:
             return False
         if int(self.encoding) != int(StateEncoding.UPPER_TRIANGULAR_CHOLESKY):
             return False
@@ -437,6 +469,17 @@ class TorchProblem(object):
         return (D in (2, 4, 6) and s.m <= 2 and len(mc.angular_indices) <= 2
                 and s.n == D + D * (D + 1) // 2
                 and isinstance(co, QRCost))
+
+    def _zero_cost_blocks(self, s):
+        """L [B, N+1], L_z, L_u [B, N, m], L_zz, L_uz, L_uu, all zero."""
+        B, N, n, m = s.B, s.N, s.n, s.m
+        opts = dict(dtype=s.dtype, device=s.device)
+        return (torch.zeros(B, N + 1, **opts),
+                torch.zeros(B, N + 1, n, **opts),
+                torch.zeros(B, N, m, **opts),
+                torch.zeros(B, N + 1, n, n, **opts),
+                torch.zeros(B, N, m, n, **opts),
+                torch.zeros(B, N, m, m, **opts))
 
     @torch.no_grad()
     def _cost_derivs_tree(self, s, co):
@@ -449,23 +492,13 @@ class TorchProblem(object):
                    r'' = -b'' / b^2 + 2 b' b'^T / b^3
             ** e:  c' = e a^(e-1) a',  c'' = e a^(e-1) a'' + e (e-1) a^(e-2) a' a'^T
         (blocks zz, uz, uu; the terminal step has the z blocks only)."""
-        from ..costs.base import AggregateCost
-        B, N, n, m = s.B, s.N, s.n, s.m
-        opts = dict(dtype=s.dtype, device=s.device)
-
-        def zeros():
-            return (torch.zeros(B, N + 1, **opts),
-                    torch.zeros(B, N + 1, n, **opts),
-                    torch.zeros(B, N, m, **opts),
-                    torch.zeros(B, N + 1, n, n, **opts),
-                    torch.zeros(B, N, m, n, **opts),
-                    torch.zeros(B, N, m, m, **opts))
+        B, N = s.B, s.N
         if not isinstance(co, torch.nn.Module):  # a constant
-            out = zeros()
+            out = self._zero_cost_blocks(s)
             out[0].fill_(float(co))
             return out
         if not isinstance(co, AggregateCost):
-            out = zeros()
+            out = self._zero_cost_blocks(s)
             self._cost_derivs_qr(s, *out, co=co)
             return out
         a = self._cost_derivs_tree(s, co.first)
@@ -518,8 +551,6 @@ class TorchProblem(object):
 
     @torch.no_grad()
     def _cost_derivs_qr(self, s, L, L_z, L_u, L_zz, L_uz, L_uu, co=None):
-        import ctypes
-        from ..costs.base import AggregateCost
         co = self.cost if co is None else co
         if isinstance(co, AggregateCost):
             for dst, src in zip((L, L_z, L_u, L_zz, L_uz, L_uu),
@@ -527,30 +558,19 @@ class TorchProblem(object):
                 dst.copy_(src)
             return
         mc = co.model_class
-        ang = [int(i) for i in mc.angular_indices]
-        non = [int(i) for i in mc.non_angular_indices]
+        ang, non = mc.angular_indices, mc.non_angular_indices
         na, m = len(non) + 2 * len(ang), s.m
         opts = dict(dtype=s.dtype, device=s.device)
-        vec = lambda t, k: torch.as_tensor(t).detach().to(**opts).expand(
-            k).contiguous()
-        mat = lambda t: t.detach().to(**opts).contiguous()
-        keep = [mat(co.Q), mat(co.Q_term), mat(co.R), vec(co.x_goal, na),
-                vec(co.u_goal, m), s.Z.contiguous(), s.U.contiguous()]
+        # (held until the launch is queued: the structure has raw pointers)
+        keep = dict(Q=_mat(co.Q, opts), Q_term=_mat(co.Q_term, opts),
+                    R=_mat(co.R, opts), x_goal=_vec(co.x_goal, na, opts),
+                    u_goal=_vec(co.u_goal, m, opts), Z=s.Z.contiguous(),
+                    U=s.U.contiguous())
         st = _native.QrCost()
         st.B, st.N, st.D, st.m = s.B, s.N, mc.state_size, m
-        st.n_ang, st.n_non = len(ang), len(non)
-        for i, v in enumerate(ang):
-            st.ang[i] = v
-        for i, v in enumerate(non):
-            st.non[i] = v
-        p = _native.ptr
-        for name, t in (("Q", keep[0]), ("Q_term", keep[1]), ("R", keep[2]),
-                        ("x_goal", keep[3]), ("u_goal", keep[4]),
-                        ("Z", keep[5]), ("U", keep[6]), ("u_min", s.u_min),
-                        ("u_max", s.u_max), ("L", L), ("L_z", L_z),
-                        ("L_u", L_u), ("L_zz", L_zz), ("L_uz", L_uz),
-                        ("L_uu", L_uu)):
-            setattr(st, name, p(t))
+        _native.set_angles(st, ang, non)
+        _native.set_pointers(st, u_min=s.u_min, u_max=s.u_max, L=L, L_z=L_z,
+                             L_u=L_u, L_zz=L_zz, L_uz=L_uz, L_uu=L_uu, **keep)
         _native.call("pddp_qr_cost_derivs", s.dtype, ctypes.byref(st),
                      _native.stream_handle(s.device))
 
@@ -559,7 +579,7 @@ class TorchProblem(object):
         tangent rows and up to 31 directions of (z | u) (include/pddp_hip.h
         pddp_bnn_jvp_group)."""
         mo = self.model
-        return (getattr(self, "use_native_bnn_jvp", True) and
+        return (self.use_native_bnn_jvp and
                 _native.lib().pddp_bnn_jvp_group(mo.state_size, s.m) != 0)
 
     @torch.no_grad()
@@ -568,61 +588,35 @@ class TorchProblem(object):
         feature launch, the fused network in JVP mode on B P 8 rows, one
         moment launch (csrc/bnn_jvp.hip, csrc/bnn_mlp.hip) - instead of
         autograd over n replicated inputs (utils/evaluation.py:203-235)."""
-        import ctypes
-        from ..utils.encoding import decode_covar_sqrt, decode_mean
         mo = self.model
-        B, N, n, m = s.B, s.N, s.n, s.m
-        D, P = mo.state_size, mo.n_particles
-        ang, non = mo.angular_indices_, mo.non_angular_indices_
-        in_dim = len(non) + 2 * len(ang) + m
+        B, N, D, P = s.B, s.N, mo.state_size, mo.n_particles
         opts = dict(dtype=s.dtype, device=s.device)
-        vec = lambda t, k: torch.as_tensor(t).detach().to(**opts).expand(
-            k).contiguous()
-        z0 = s.Z[:, 0]
-        if 0 not in mo.eps_in:
-            e = torch.randn(P, D, **opts)
-            mo.eps_in[0] = (e - e.mean(0)) / e.std(0)
-        Xp = (decode_mean(z0, self.encoding).unsqueeze(-2) +
-              mo.eps_in[0] @ decode_covar_sqrt(z0, self.encoding)).contiguous()
+        Xp = self._first_particles(s.Z[:, 0], opts).contiguous()
         Xn = torch.empty_like(Xp)
         eps = torch.empty_like(Xp)
-        G = 8  # network rows per (state, particle): input + D + m tangents
-        F = torch.empty(B * P * G, in_dim, **opts)
-        keep = [vec(mo.X_mean, in_dim), vec(mo.X_std_inv, in_dim),
-                vec(mo.dX_mean, D), vec(mo.dX_std, D), s.Z.contiguous(),
-                s.U.contiguous()]
         st = _native.BnnJvp()
-        st.B, st.P, st.D, st.m, st.N = B, P, D, m, N
-        st.n_ang, st.n_non = len(ang), len(non)
-        for i, v in enumerate(ang):
-            st.ang[i] = v
-        for i, v in enumerate(non):
-            st.non[i] = v
-        ups = self._predicted_std()
-        out_rows = 2 * D if ups else D
-        st.in_dim, st.out_dim = in_dim, out_rows
+        norm = self._bnn_header(st, s, opts)  # (sets st.in_dim, st.out_dim)
+        keep = dict(norm, Z=s.Z.contiguous(), U=s.U.contiguous())
+        G = 8  # network rows per (state, particle): input + D + m tangents
+        F = torch.empty(B * P * G, st.in_dim, **opts)
+        ups, out_rows = self._predicted_std(), st.out_dim
         st.independent_noise = int(bool(
             self.model_opts.get("independent_noise", False)))
         eps_keep = [self._eps_out(i, P, D, opts) for i in range(N)] if ups \
             else None
         p = _native.ptr
-        for name, t in (("X_mean", keep[0]), ("X_std_inv", keep[1]),
-                        ("dX_mean", keep[2]), ("dX_std", keep[3]),
-                        ("Z", keep[4]), ("U", keep[5]), ("u_min", s.u_min),
-                        ("u_max", s.u_max), ("eps", eps), ("F", F),
-                        ("F_z", F_z), ("F_u", F_u)):
-            setattr(st, name, p(t))
+        _native.set_pointers(st, u_min=s.u_min, u_max=s.u_max, eps=eps, F=F,
+                             F_z=F_z, F_u=F_u, **keep)
         # with a mask: only its trajectories, their network rows packed to the
         # front and the network on that many rows (a device count; sync-free)
         live_rows = slot = None
         if mask is not None:
             run = mask != 0
-            rank = torch.cumsum(run.to(torch.int32), 0, dtype=torch.int32)
+            rank, live_rows = _live_rows(run, P * G)
             slot = torch.where(run, rank - 1,
                                torch.full_like(rank, -1)).contiguous()
-            live_rows = (rank[-1:] * (P * G)).to(torch.int32)
             st.slot = p(slot)
-        lib, stream = _native.lib(), _native.stream_handle(s.device)
+        stream = _native.stream_handle(s.device)
         for t in range(N):
             st.t = t
             st.Xp, st.Xp_next = p(Xp), p(Xn)
@@ -642,10 +636,8 @@ class TorchProblem(object):
         with the fused network kernel in between (include/pddp_hip.h:
         pddp_bnn_moment_step_f32, pddp_bnn_mlp_f32) instead of ~150 torch
         launches per time step."""
-        from ..costs.quadratic import QRCost
-        from ..utils.encoding import StateEncoding
         mo, co = self.model, self.cost
-        if not getattr(self, "use_native_bnn", True):
+        if not self.use_native_bnn:
             return False
         if s.dtype not in (torch.float32, torch.float64) or self.cost_opts:
             return False
@@ -681,6 +673,34 @@ class TorchProblem(object):
     def _predicted_std(self):
         return bool(self.model_opts.get("use_predicted_std", False))
 
+    def _first_particles(self, z0, opts):
+        """Particles of step 0, [B, P, D]: mean + eps L on cached standardised
+        normals (modules.py:312-330; the same draw the model itself would
+        make, and the first draw of a call that makes any)."""
+        mo = self.model
+        if 0 not in mo.eps_in:
+            e = torch.randn(mo.n_particles, mo.state_size, **opts)
+            mo.eps_in[0] = (e - e.mean(0)) / e.std(0)
+        return decode_mean(z0, self.encoding).unsqueeze(-2) + \
+            mo.eps_in[0] @ decode_covar_sqrt(z0, self.encoding)
+
+    def _bnn_header(self, st, s, opts):
+        """What pddp_bnn_step and pddp_bnn_jvp share: the sizes, the layout of
+        the features, and the model's normalisation as the kernels read it
+        (returned: the caller keeps it alive and sets its pointers)."""
+        mo = self.model
+        ang, non = mo.angular_indices_, mo.non_angular_indices_
+        D = mo.state_size
+        st.B, st.P, st.D, st.m, st.N = s.B, mo.n_particles, D, s.m, s.N
+        _native.set_angles(st, ang, non)
+        st.in_dim = len(non) + 2 * len(ang) + s.m
+        # (without the predicted std the log-std rows of fc_out are unused)
+        st.out_dim = 2 * D if self._predicted_std() else D
+        return dict(X_mean=_vec(mo.X_mean, st.in_dim, opts),
+                    X_std_inv=_vec(mo.X_std_inv, st.in_dim, opts),
+                    dX_mean=_vec(mo.dX_mean, D, opts),
+                    dX_std=_vec(mo.dX_std, D, opts))
+
     def _eps_out(self, i, P, D, opts):
         """Standardised normals of time index i for the predicted std, drawn
         and cached exactly as the model's own forward does
@@ -692,70 +712,32 @@ class TorchProblem(object):
         return mo.eps_out[i].contiguous()
 
     @torch.no_grad()
-    def _line_search_bnn(self, s, active, use_status):
-        # (costs straight into s.Jc: rows of skipped trajectories stay as they
-        # are, like their candidates)
-        self._bnn_rollouts(s, s.A, s.alphas, s.gains, s.Zc, s.Uc, active,
-                           s.bwd_status if use_status else None,
-                           Jc_out=s.Jc.view(-1))
-
-    @torch.no_grad()
     def _bnn_rollouts(self, s, A, alphas, gains, Zc, Uc, active, status,
                       Jc_out=None):
         """A moment-matched rollouts per trajectory under the control law
         u = clamp(U + alpha k + K (z - Z)): N + 1 moment-step launches with the
         fused network kernel in between.  Returns the costs [B A]."""
-        import ctypes
-        from ..utils.encoding import decode_covar_sqrt, decode_mean
         mo, co = self.model, self.cost
-        B, N, n, m = s.B, s.N, s.n, s.m
-        D, P = mo.state_size, mo.n_particles
-        ang, non = mo.angular_indices_, mo.non_angular_indices_
-        na = len(non) + 2 * len(ang)
-        ups = self._predicted_std()
-        # (without the predicted std the log-std rows of fc_out are unused)
-        in_dim, out_dim = na + m, (2 * D if ups else D)
+        B, N, m, D, P = s.B, s.N, s.m, mo.state_size, mo.n_particles
         opts = dict(dtype=s.dtype, device=s.device)
-        vec = lambda t, k: torch.as_tensor(t).detach().to(**opts).expand(
-            k).contiguous()
-        mat = lambda t: t.detach().to(**opts).contiguous()
-        # particles of step 0: mean + eps L, cached standardised normals
-        # (modules.py:312-330; the same draw the model itself would make)
-        z0 = s.Z[:, 0]
-        mean0 = decode_mean(z0, self.encoding)
-        if 0 not in mo.eps_in:
-            e = torch.randn(P, D, **opts)
-            mo.eps_in[0] = (e - e.mean(0)) / e.std(0)
-        X0 = mean0.unsqueeze(-2) + mo.eps_in[0] @ decode_covar_sqrt(
-            z0, self.encoding)
+        X0 = self._first_particles(s.Z[:, 0], opts)
         Xp = X0.unsqueeze(1).expand(B, A, P, D).contiguous()
-        F = torch.zeros(B * A, P, in_dim, **opts)
+        st = _native.BnnStep()
+        st.A = A
+        norm = self._bnn_header(st, s, opts)  # (sets st.in_dim, st.out_dim)
+        na = st.in_dim - m  # the augmented state: the features without u
+        keep = dict(norm, Q=_mat(co.Q, opts), Q_term=_mat(co.Q_term, opts),
+                    R=_mat(co.R, opts), x_goal=_vec(co.x_goal, na, opts),
+                    u_goal=_vec(co.u_goal, m, opts))
+        ups, out_dim = self._predicted_std(), st.out_dim
+        F = torch.zeros(B * A, P, st.in_dim, **opts)
         J = torch.zeros(B * A, **opts)
         Jc = torch.zeros(B * A, **opts) if Jc_out is None else Jc_out
-        keep = [vec(mo.X_mean, in_dim), vec(mo.X_std_inv, in_dim),
-                vec(mo.dX_mean, D), vec(mo.dX_std, D), mat(co.Q),
-                mat(co.Q_term), mat(co.R), vec(co.x_goal, na),
-                vec(co.u_goal, m)]
-        st = _native.BnnStep()
-        st.B, st.A, st.P, st.D, st.m, st.N = B, A, P, D, m, N
-        st.n_ang, st.n_non = len(ang), len(non)
-        for i, v in enumerate(ang):
-            st.ang[i] = v
-        for i, v in enumerate(non):
-            st.non[i] = v
-        st.in_dim, st.out_dim = in_dim, out_dim
         p = _native.ptr
-        for name, t in (("Z", s.Z), ("U", s.U), ("gains", gains),
-                        ("alphas", alphas), ("u_min", s.u_min),
-                        ("u_max", s.u_max), ("active", active),
-                        ("bwd_status", status),
-                        ("X_mean", keep[0]), ("X_std_inv", keep[1]),
-                        ("dX_mean", keep[2]), ("dX_std", keep[3]),
-                        ("Q", keep[4]), ("Q_term", keep[5]), ("R", keep[6]),
-                        ("x_goal", keep[7]), ("u_goal", keep[8]), ("Xp", Xp),
-                        ("F", F), ("Zc", Zc), ("Uc", Uc), ("J", J),
-                        ("Jc", Jc)):
-            setattr(st, name, p(t))
+        _native.set_pointers(st, Z=s.Z, U=s.U, gains=gains, alphas=alphas,
+                             u_min=s.u_min, u_max=s.u_max, active=active,
+                             bwd_status=status, Xp=Xp, F=F, Zc=Zc, Uc=Uc, J=J,
+                             Jc=Jc, **keep)
         # The live trajectories' candidates are packed to the front of the
         # network's rows (slot = rank among the live ones) and the network runs
         # on those rows only - a count it reads on the device: a round of
@@ -768,11 +750,10 @@ class TorchProblem(object):
                 alive &= active != 0
             if status is not None:
                 alive &= status == 0
-            rank = torch.cumsum(alive.to(torch.int32), 0, dtype=torch.int32)
+            rank, live_rows = _live_rows(alive, A * P)
             slot = (rank - 1).contiguous()
-            live_rows = (rank[-1:] * (A * P)).to(torch.int32)
             st.slot = p(slot)
-        lib, stream = _native.lib(), _native.stream_handle(s.device)
+        stream = _native.stream_handle(s.device)
         out = None
         eps_keep = [self._eps_out(i, P, D, opts) for i in range(N)] if ups \
             else None
@@ -792,10 +773,18 @@ class TorchProblem(object):
     def line_search(self, s, active=None, use_status=True):
         self.model.eval()
         self.cost.eval()
-        if self._bnn_native_ok(s):
-            return self._line_search_bnn(s, active, use_status)
-        if self._gp_line_search_ok(s):
+        path = self._line_search_path(s)
+        if path == "bnn":
+            # (costs straight into s.Jc: rows of skipped trajectories stay as
+            # they are, like their candidates)
+            self._bnn_rollouts(s, s.A, s.alphas, s.gains, s.Zc, s.Uc, active,
+                               s.bwd_status if use_status else None,
+                               Jc_out=s.Jc.view(-1))
+            return
+        if path == "gp_rollout":
             return self._line_search_gp(s, active, use_status)
+        if path == "gp_step":
+            return self._line_search_gp_torch(s)
         B, N, n, m, A = s.B, s.N, s.n, s.m, s.A
         k, K = s.gain_views()
         alpha = s.alphas.view(1, A, 1)

@@ -23,6 +23,7 @@ import torch
 from torch.nn import Parameter
 
 from .base import DynamicsModel
+from .. import _native
 from ..utils.angular import augment_state, infer_augmented_state_size
 from ..utils.classproperty import classproperty
 from ..utils.encoding import (StateEncoding, decode_covar_sqrt, decode_mean,
@@ -53,7 +54,6 @@ def set_network_precision(mode):
     (pddp_bnn_mlp_precision, include/pddp_hip.h): 0 exact f32 (default), 3 the
     bf16-split twin (f32 to rounding, ~1.5x faster at [200, 200]).  Process-wide;
     returns the previous mode."""
-    from .. import _native
     return int(_native.lib().pddp_bnn_mlp_precision(int(mode)))
 
 
@@ -64,7 +64,6 @@ def set_network_deal(deal):
     deal for both - 2 in forward mode is 5 % faster and sums in another order
     (a ReLU linearised within rounding of zero may take the other sign).
     Process-wide; returns the previous value."""
-    from .. import _native
     return int(_native.lib().pddp_bnn_mlp_deal(int(deal)))
 
 
@@ -233,29 +232,33 @@ class BayesianMLP(torch.nn.Module):
             cache[k] = (key, m.to(like.dtype).contiguous())
         return cache[k][1]
 
+    def _operands(self, P, out_rows, like):
+        """W1, b1, mask 1, W2, b2, mask 2, the first `out_rows` rows of fc_out
+        and of its bias: what both network kernels take between the input and
+        the output (the masks are drawn here on first use, layer 0 first)."""
+        c = lambda t: t.detach().contiguous()
+        m1, m2 = self._mask_t(0, P, like), self._mask_t(1, P, like)
+        h0, h1 = self.hidden
+        return [c(h0.weight), c(h0.bias), m1, c(h1.weight), c(h1.bias), m2,
+                c(self.out.weight[:out_rows]), c(self.out.bias[:out_rows])]
+
     def _forward_native(self, x, out_rows=None, live_rows=None):
         """`out_rows`: only the first rows of fc_out (the mean increments when
         the predicted std is not used, modules.py:262).  `live_rows`: an int32
         device scalar - only that many leading rows are computed (the kernel
         reads it: no host synchronisation), the others are left alone."""
-        from .. import _native
         P, in_dim = x.shape[-2], x.shape[-1]
         H = self.hidden[0].out_features
         out_dim = self.out.out_features if out_rows is None else int(out_rows)
         xc = x.detach().contiguous()
         R = xc.numel() // in_dim
         y = torch.empty(*x.shape[:-1], out_dim, dtype=x.dtype, device=x.device)
-        m1, m2 = self._mask_t(0, P, xc), self._mask_t(1, P, xc)
-        c = lambda t: t.detach().contiguous()
+        keep = self._operands(P, out_dim, xc)
         p = _native.ptr
         fn = getattr(_native.lib(),
                      "pddp_bnn_mlp_rows_" + _native.suffix(x.dtype))
-        rc = fn(
-            R, P, in_dim, H, out_dim, p(xc), p(c(self.hidden[0].weight)),
-            p(c(self.hidden[0].bias)), p(m1), p(c(self.hidden[1].weight)),
-            p(c(self.hidden[1].bias)), p(m2), p(c(self.out.weight[:out_dim])),
-            p(c(self.out.bias[:out_dim])), p(y), p(live_rows),
-            _native.stream_handle(x.device))
+        rc = fn(R, P, in_dim, H, out_dim, p(xc), *[p(t) for t in keep], p(y),
+                p(live_rows), _native.stream_handle(x.device))
         _native.check(rc, "pddp_bnn_mlp_rows_" + _native.suffix(x.dtype))
         return y
 
@@ -265,25 +268,18 @@ class BayesianMLP(torch.nn.Module):
         first `out_rows` outputs per row (include/pddp_hip.h
         pddp_bnn_mlp_jvp_live_f32).  `live`: rows of a group in use (default:
         all) - the rest is neither read nor written."""
-        from .. import _native
         in_dim = F.shape[-1]
         H = self.hidden[0].out_features
         R = F.shape[0]
         Y = torch.empty(R, out_rows, dtype=F.dtype, device=F.device)
-        m1, m2 = self._mask_t(0, P, F), self._mask_t(1, P, F)
-        c = lambda t: t.detach().contiguous()
+        keep = self._operands(P, out_rows, F)
         p = _native.ptr
         # (`live_rows`: an int32 device scalar - only that many leading rows)
         fn = getattr(_native.lib(),
                      "pddp_bnn_mlp_jvp_rows_" + _native.suffix(F.dtype))
-        rc = fn(
-            R, P, int(group), int(group if live is None else live), in_dim, H,
-            out_rows, p(F),
-            p(c(self.hidden[0].weight)),
-            p(c(self.hidden[0].bias)), p(m1), p(c(self.hidden[1].weight)),
-            p(c(self.hidden[1].bias)), p(m2), p(c(self.out.weight[:out_rows])),
-            p(c(self.out.bias[:out_rows])), p(Y), p(live_rows),
-            _native.stream_handle(F.device))
+        rc = fn(R, P, int(group), int(group if live is None else live), in_dim,
+                H, out_rows, p(F), *[p(t) for t in keep], p(Y), p(live_rows),
+                _native.stream_handle(F.device))
         _native.check(rc, "pddp_bnn_mlp_jvp_rows_" + _native.suffix(F.dtype))
         return Y
 

@@ -41,11 +41,14 @@ controllers' plugin path takes F_z, F_u of a whole nominal from one launch
 (controllers/plugin.py `_dyn_derivs_gp`) and runs the line search on it
 (`_line_search_gp`).
 """
+import ctypes
 import math
 
 import torch
 
 from .base import DynamicsModel
+from .bnn import bump_generation
+from .. import _native
 from ..utils.angular import augment_moments, augment_state
 from ..utils.classproperty import classproperty
 from ..utils.encoding import StateEncoding, decode_covar, decode_mean, encode
@@ -201,7 +204,6 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
             it replays) dies with the tensors it was made from - eagerly, not
             at the next eager native_step, which a graph-only controller never
             makes."""
-            from .bnn import bump_generation
             self._native_cache = {}
             bump_generation(self)
 
@@ -325,7 +327,6 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
             inputs = self._native_inputs(z, encoding)
             if inputs is None:
                 return False
-            from .. import _native
             fn = _native.lib().pddp_gp_step_lds_bytes
             need = fn(state_size, d_in, int(self.Xt.shape[0]), inputs,
                       int(bool(jacobian)), z.element_size())
@@ -339,7 +340,6 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
             inputs = self._native_inputs(z, encoding)
             if inputs is None:
                 return None
-            from .. import _native
             form = _native.lib().pddp_gp_step_form(
                 state_size, d_in, int(self.Xt.shape[0]), inputs,
                 int(bool(jacobian)), z.element_size())
@@ -348,7 +348,6 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
         def _native_model(self, dtype, device, encoding):
             """The kernel's view of the conditioned GPs (cached per dtype; the
             cache is dropped by `condition`)."""
-            from .. import _native
             # (keyed by what the view was made from: a loaded state or a
             # parameter changed in place makes a new one)
             src = (self.Xt, self.beta, self.Kinv, self.log_ell, self.log_sf,
@@ -360,7 +359,6 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
                 self._native_cache.clear()
                 # (hipGraphs captured around the old view hold its pointers:
                 # ILQRSolver._graphs_fresh drops them on a new generation)
-                from .bnn import bump_generation
                 bump_generation(self)
                 conv = lambda t: t.detach().to(dtype=dtype, device=device) \
                     .contiguous()
@@ -386,13 +384,8 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
                 g = _native.GpModel()
                 g.state_size, g.action_size = state_size, action_size
                 g.M = int(self.Xt.shape[0])
-                g.n_ang, g.n_non = len(ai), len(ni)
-                for k_, v in enumerate(ai):
-                    g.ang[k_] = int(v)
-                for k_, v in enumerate(ni):
-                    g.non[k_] = int(v)
-                for name, t in keep.items():
-                    setattr(g, name, _native.ptr(t))
+                _native.set_angles(g, ai, ni)
+                _native.set_pointers(g, **keep)
                 hit = self._native_cache[key] = (g, keep)
             hit[0].encoding = int(encoding)
             return hit[0]
@@ -407,8 +400,6 @@ def gp_dynamics_model_factory(state_size, action_size, angular_indices=(),
             elements).  `row_mask` (uint8, one entry per `rows_per_mask`
             consecutive rows): rows of a zero entry are skipped, their outputs
             left as they are."""
-            import ctypes
-            from .. import _native
             z = z.detach().contiguous()
             u = u.detach().reshape(z.shape[0], -1).to(z.dtype).contiguous()
             R, n = z.shape
