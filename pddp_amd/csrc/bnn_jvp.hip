@@ -33,6 +33,9 @@
 // 15, 21 of the double cartpole's 28).  jvp_moments still has one lane per
 // direction of z (G = 16 or 32 lanes per trajectory), each reading its base
 // direction's row and scaling.
+// (exp_, log_: pddp_common.hpp.  The jittered Cholesky of jvp_moments stays
+// written out here: through a shared attempt ladder the runtime-D instances
+// took one or two more registers)
 #include "pddp_common.hpp"
 #include "models.hpp"  // sincos_
 
@@ -47,10 +50,6 @@ constexpr int kNetRows = 8;  // network rows per (state, particle)
 // EXACT: D == kJvpMaxD, known at compile time - every small matrix below is
 // then indexed statically and lives in registers (under a runtime D they sat in
 // scratch memory: 160 .. 1024 bytes per lane, and the kernels waited for it).
-PDDP_DEV float jvp_exp(float x) { return expf(x); }
-PDDP_DEV double jvp_exp(double x) { return exp(x); }
-PDDP_DEV float jvp_log(float x) { return logf(x); }
-PDDP_DEV double jvp_log(double x) { return log(x); }
 
 // pddp_bnn_jvp / pddp_bnn_jvp_f64 (include/pddp_hip.h) with the scalar type as
 // a parameter: the two structs differ in the pointee type only
@@ -193,13 +192,13 @@ __global__ __launch_bounds__(64) void bnn_jvp_moments_kernel(BnnJvpV<T> s) {
   // use_predicted_std (modules.py:242-260): + exp(log_std + log dX_std) eps
   const bool ups = s.eps_out != nullptr;
   T lsd[kJvpMaxD];
-  for (int d = 0; d < D; ++d) lsd[d] = ups ? jvp_log(sd[d]) : 0.f;
+  for (int d = 0; d < D; ++d) lsd[d] = ups ? log_(sd[d]) : 0.f;
   auto primal_out = [&](int p, int d, T& stdeps) {
     const T* y = Y + (size_t)p * kNetRows * OUT;
     T dx = y[d] * sd[d] + mu[d];
     stdeps = 0.f;
     if (ups) {
-      stdeps = jvp_exp(y[D + d] + lsd[d]) * s.eps_out[p * D + d];
+      stdeps = exp_(y[D + d] + lsd[d]) * s.eps_out[p * D + d];
       dx = dx + stdeps;
     }
     return Xin[p * D + d] + dx;

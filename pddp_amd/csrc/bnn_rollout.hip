@@ -37,10 +37,6 @@ constexpr int kBnnGroup = 16;                  // lanes per candidate
 constexpr int kBnnPerWave = 64 / kBnnGroup;    // candidates per wavefront
 constexpr int kBnnMaxPPL = 128 / kBnnGroup;    // particles per lane (P <= 128)
 
-PDDP_DEV float bnn_exp(float x) { return expf(x); }
-PDDP_DEV double bnn_exp(double x) { return exp(x); }
-PDDP_DEV float bnn_log(float x) { return logf(x); }
-PDDP_DEV double bnn_log(double x) { return log(x); }
 PDDP_DEV void bnn_sincos_core(float x, float& s, float& c) { sincos_core(x, s, c); }
 PDDP_DEV void bnn_sincos_core(double x, double& s, double& c) { sincos(x, &s, &c); }
 
@@ -211,7 +207,7 @@ __global__ __launch_bounds__(64) void bnn_moment_step_kernel(BnnStepV<T> s) {
       if (t > 0) {  // X + dx, dx = out[:D] * dX_std + dX_mean   (modules.py:262)
         T dx = net[d] * s.dX_std[d] + s.dX_mean[d];
         if (s.eps_out != nullptr)  // + exp(log_std + log dX_std) eps (:242-260)
-          dx = dx + bnn_exp(nls[d] + bnn_log(s.dX_std[d])) *
+          dx = dx + exp_(nls[d] + log_(s.dX_std[d])) *
                         s.eps_out[(has[q] ? p : 0) * D + d];
         v = v + dx;
       }
@@ -342,7 +338,7 @@ __global__ __launch_bounds__(64) void bnn_moment_step_kernel(BnnStepV<T> s) {
     for (int a1 = 0; a1 < nang; ++a1) {
       const int i1 = s.ang[a1];
       const T m1 = Ms[i1], v1 = Cs[i1 * kBnnMaxNa + i1];
-      const T damp = bnn_exp(-0.5f * v1);
+      const T damp = exp_(-0.5f * v1);
       T sin1, cos1;
       sincos_(m1, sin1, cos1);
       const T Es = damp * sin1, Ec = damp * cos1;
@@ -352,8 +348,8 @@ __global__ __launch_bounds__(64) void bnn_moment_step_kernel(BnnStepV<T> s) {
         const int i2 = s.ang[a2];
         const T m2 = Ms[i2], v2 = Cs[i2 * kBnnMaxNa + i2];
         const T cij = Cs[i1 * kBnnMaxNa + i2];
-        const T lq = -0.5f * (v1 + v2), q = bnn_exp(lq);
-        const T ep = bnn_exp(lq + cij) - q, em = bnn_exp(lq - cij) - q;
+        const T lq = -0.5f * (v1 + v2), q = exp_(lq);
+        const T ep = exp_(lq + cij) - q, em = exp_(lq - cij) - q;
         T sd, cd, ss, cs;
         sincos_(m1 - m2, sd, cd);
         sincos_(m1 + m2, ss, cs);

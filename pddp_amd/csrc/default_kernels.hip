@@ -29,8 +29,11 @@
 //                    utils/evaluation.py:134-288)
 //   line search      one lane per (trajectory, step size): ilqr.py:677-723
 //                    _control_law + :764-791 _trajectory_cost
-// float and double; the cost is written once over a number type (plain T for
-// values, HDual<T> for derivatives).
+// float and double; the cost is one text over a number type (plain T for
+// values, HDual<T> for derivatives), gauss_cost_body.inc, shared with
+// qr_cost_derivs.hip; the number types and the cost's jittered Cholesky are
+// gauss_numbers.hpp's.  rechol_upper keeps its own attempt ladder: it leaves
+// the factor, in triangle storage, over T or FDual<T>.
 //
 // FULL_COVARIANCE_MATRIX (z = mean | C row-major, n = D + D^2; round 3: the
 // double cartpole too, n = 42): C is taken as given - no symmetrisation, so that the partial
@@ -41,46 +44,11 @@
 // covariance is diag(var), the dynamics carry var unchanged (std: sqrt(std^2)),
 // the augmented state keeps variances only (angular.py:87-158), so the
 // cost's trace term is sum_i Q_ii Var_a[i] (no Cholesky, no jitter).
+#include "gauss_numbers.hpp"
 #include "models.hpp"
 #include "problem_args.hpp"
 
 namespace pddp {
-
-PDDP_DEV float exp_(float x) { return expf(x); }
-PDDP_DEV double exp_(double x) { return exp(x); }
-
-template <typename T>
-struct HDual {  // hyper-dual number: value, d/dx_i, d/dx_j, d2/dx_i dx_j
-  T v, a, b, ab;
-};
-template <typename T> PDDP_DEV HDual<T> operator+(HDual<T> x, HDual<T> y) { return {x.v + y.v, x.a + y.a, x.b + y.b, x.ab + y.ab}; }
-template <typename T> PDDP_DEV HDual<T> operator-(HDual<T> x, HDual<T> y) { return {x.v - y.v, x.a - y.a, x.b - y.b, x.ab - y.ab}; }
-template <typename T> PDDP_DEV HDual<T> operator-(HDual<T> x) { return {-x.v, -x.a, -x.b, -x.ab}; }
-template <typename T> PDDP_DEV HDual<T> operator*(HDual<T> x, HDual<T> y) {
-  return {x.v * y.v, x.a * y.v + x.v * y.a, x.b * y.v + x.v * y.b,
-          x.ab * y.v + x.a * y.b + x.b * y.a + x.v * y.ab};
-}
-template <typename T> PDDP_DEV HDual<T> operator*(T s, HDual<T> x) { return {s * x.v, s * x.a, s * x.b, s * x.ab}; }
-template <typename T> PDDP_DEV HDual<T> operator-(HDual<T> x, T s) { return {x.v - s, x.a, x.b, x.ab}; }
-template <typename T> PDDP_DEV HDual<T> exp_(HDual<T> x) {
-  const T e = exp_(x.v);
-  return {e, e * x.a, e * x.b, e * (x.ab + x.a * x.b)};
-}
-PDDP_DEV void sincos_lib(float x, float& s, float& c) { sincosf(x, &s, &c); }
-PDDP_DEV void sincos_lib(double x, double& s, double& c) { sincos(x, &s, &c); }
-template <typename T> PDDP_DEV void sincos_x(T x, T& s, T& c) { sincos_lib(x, s, c); }
-template <typename T> PDDP_DEV void sincos_x(HDual<T> x, HDual<T>& s, HDual<T>& c) {
-  T sv, cv;
-  sincos_lib(x.v, sv, cv);
-  s = {sv, cv * x.a, cv * x.b, cv * x.ab - sv * x.a * x.b};
-  c = {cv, -sv * x.a, -sv * x.b, -sv * x.ab - cv * x.a * x.b};
-}
-template <typename T> PDDP_DEV T val(T x) { return x; }
-template <typename T> PDDP_DEV T val(HDual<T> x) { return x.v; }
-template <typename X, typename T> PDDP_DEV X lift(T v) {
-  if constexpr (sizeof(X) == sizeof(T)) return v;
-  else return X{v, T(0), T(0), T(0)};
-}
 
 // shape of a sample problem under a Gaussian encoding ENC (PDDP_ENC_*)
 constexpr int kChol = PDDP_ENC_UPPER_TRIANGULAR_CHOLESKY;
@@ -95,8 +63,10 @@ struct DefDims {
   static constexpr int NO =
       ENC == kChol ? D * (D + 1) / 2 : (ENC == kFull ? D * D : D);
   static constexpr int n = D + NO;               // encoded size
-  static constexpr int non(int r) { return M::col[r]; }
-  static constexpr int ang(int a) { return M::col[nn + 2 * a]; }
+  // state dimension at position a of (non-angular ... | angles ...)
+  static constexpr int perm(int a) {
+    return a < nn ? M::col[a] : M::col[nn + 2 * (a - nn)];
+  }
   // position of U[k][i] (k <= i) among the row-major upper-triangle entries
   static constexpr int tri(int k, int i) {
     return k * D - k * (k - 1) / 2 + (i - k);
@@ -138,37 +108,6 @@ PDDP_DEV void covar_of(const X (&oth)[DefDims<MODEL, ENC>::NO],
     }
 }
 
-// the jittered upper Cholesky only decides which trace the cost sees
-// (encoding.py:536-564: jitter 1e-12, 1e-11, ... <= 10, else the diagonal)
-template <typename T, int NA>
-PDDP_DEV T chol_jitter_of(const T (&C)[NA][NA]) {
-  double jit = 1e-12;
-  while (jit <= 10.0) {
-    T U[NA][NA];
-    bool ok = true;
-    // (no early exit: a failed pivot ends the reference's attempt, what is
-    // computed after it is discarded - the loops unroll, U stays in registers)
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-#pragma unroll
-      for (int j = i; j < NA; ++j) {
-        T s = C[i][j] + (i == j ? (T)jit : T(0));
-#pragma unroll
-        for (int q = 0; q < i; ++q) s -= U[q][i] * U[q][j];
-        if (i == j) {
-          if (!(s > T(0))) ok = false;
-          U[i][i] = sqrt_(s);
-        } else {
-          U[i][j] = s / U[i][i];
-        }
-      }
-    }
-    if (ok) return (T)jit;
-    jit *= 10.0;
-  }
-  return T(-1);
-}
-
 // Rendezvous (8 states, 4 actions, no angles) carries the input's FULL
 // covariance through its dynamics (pddp/examples/rendezvous/model.py:94,110:
 // encode(mean', C = decode_covar(z))), where the other sample models keep the
@@ -179,24 +118,6 @@ PDDP_DEV T chol_jitter_of(const T (&C)[NA][NA]) {
 //   full       C' = C, every entry      variance / std   as the other models
 template <int MODEL>
 constexpr bool kCarriesCovar = (MODEL == PDDP_MODEL_RENDEZVOUS);
-
-template <typename T>
-struct FDual {  // forward dual number: value, one tangent
-  T v, d;
-};
-template <typename T> PDDP_DEV FDual<T> operator+(FDual<T> x, FDual<T> y) { return {x.v + y.v, x.d + y.d}; }
-template <typename T> PDDP_DEV FDual<T> operator-(FDual<T> x, FDual<T> y) { return {x.v - y.v, x.d - y.d}; }
-template <typename T> PDDP_DEV FDual<T> operator*(FDual<T> x, FDual<T> y) { return {x.v * y.v, x.d * y.v + x.v * y.d}; }
-template <typename T> PDDP_DEV FDual<T> operator/(FDual<T> x, FDual<T> y) {
-  const T q = x.v / y.v;
-  return {q, (x.d - q * y.d) / y.v};
-}
-template <typename T> PDDP_DEV FDual<T> sqrt_x(FDual<T> x) {
-  const T r = sqrt_(x.v);
-  return {r, x.d / (r + r)};
-}
-template <typename T> PDDP_DEV T sqrt_x(T x) { return sqrt_(x); }
-template <typename T> PDDP_DEV T val(FDual<T> x) { return x.v; }
 
 // R = upper Cholesky factor of U^T U + jitter I, both as the row-major upper
 // triangles the encoding stores (utils/encoding.py _cholesky_upper: jitter
@@ -251,96 +172,33 @@ PDDP_DEV X qr_cost_default(const ProblemT<T>& P,
                            const X (&u)[DefDims<MODEL, ENC>::m],
                            bool terminal) {
   using G = DefDims<MODEL, ENC>;
-  constexpr int D = G::D, m = G::m, na = G::na, nn = G::nn, nang = G::nang;
+  constexpr int D = G::D, m = G::m, NA = G::na, NN = G::nn, NANG = G::nang;
   constexpr int LQ = PDDP_MAX_AUG, LR = PDDP_MAX_ACTION;
   const T* Q = terminal ? P.Qt : P.Q;
   X C[D][D];
   covar_of<X, MODEL, ENC>(oth, C);
-  T Cav[na][na];
-#pragma unroll
-  for (int r = 0; r < na; ++r)
-#pragma unroll
-    for (int c = 0; c < na; ++c) Cav[r][c] = T(0);
-  X Ma[na];
-  X tr = lift<X>(T(0)), trd = lift<X>(T(0));  // sum Ca_ij Q_ji; sum Ca_ii Q_ii
-  auto put = [&](int r, int c, X v) {  // every entry is written once
-    Cav[r][c] = val(v);
-    tr = tr + Q[c * LQ + r] * v;
-    if (r == c) trd = trd + Q[r * LQ + r] * v;
-  };
-#pragma unroll
-  for (int r = 0; r < nn; ++r) {
-    Ma[r] = mu[G::non(r)];
-#pragma unroll
-    for (int c = 0; c < nn; ++c) put(r, c, C[G::non(r)][G::non(c)]);
+  T jit;
+#define PDDP_COST_ZERO lift<X>(T(0))
+#define PDDP_COST_MU(a) mu[G::perm(a)]
+#define PDDP_COST_COV(a, c) C[G::perm(a)][G::perm(c)]
+#define PDDP_COST_Q(r, c) Q[(r) * LQ + (c)]
+#define PDDP_COST_GOAL(r) P.goal[r]
+  /* variance-only encodings: the augmented state keeps diag(Ca) only (full
+     covariance: encode() flattens the augmented matrix as it is) */
+#define PDDP_COST_JITTER                                  \
+  jit = ENC == kChol ? chol_jitter_of<T, NA>(Cav)         \
+                     : (ENC == kFull ? T(0) : T(-1));
+#define PDDP_COST_JITTER_TERM(v) lift<X>(v)
+#define PDDP_COST_ACTION                                            \
+  if (!terminal) {                                                  \
+    _Pragma("unroll") for (int c = 0; c < m; ++c) {                 \
+      X row = lift<X>(T(0));                                        \
+      _Pragma("unroll") for (int r = 0; r < m; ++r)                 \
+        row = row + P.R[r * LR + c] * (u[r] - P.ugoal[r]);          \
+      cost = cost + row * (u[c] - P.ugoal[c]);                      \
+    }                                                               \
   }
-#pragma unroll
-  for (int a1 = 0; a1 < nang; ++a1) {
-    const int i1 = G::ang(a1);
-    const X m1 = mu[i1], v1 = C[i1][i1];
-    const X damp = exp_(T(-0.5) * v1);
-    X s1, c1;
-    sincos_x(m1, s1, c1);
-    const X Es = damp * s1, Ec = damp * c1;
-    const int r = nn + 2 * a1;
-    Ma[r] = Es;
-    Ma[r + 1] = Ec;
-#pragma unroll
-    for (int a2 = 0; a2 < nang; ++a2) {
-      const int i2 = G::ang(a2);
-      const X m2 = mu[i2], v2 = C[i2][i2], cij = C[i1][i2];
-      const X lq = T(-0.5) * (v1 + v2), qq = exp_(lq);
-      const X ep = exp_(lq + cij) - qq, em = exp_(lq - cij) - qq;
-      X sd, cd, ss, cs;
-      sincos_x(m1 - m2, sd, cd);
-      sincos_x(m1 + m2, ss, cs);
-      const int cc = nn + 2 * a2;
-      put(r, cc, T(0.5) * (ep * cd - em * cs));          // sin, sin
-      put(r + 1, cc + 1, T(0.5) * (ep * cd + em * cs));  // cos, cos
-      const X sc = T(0.5) * (ep * sd + em * ss);         // sin_1, cos_2
-      put(r, cc + 1, sc);
-      put(cc + 1, r, sc);
-    }
-#pragma unroll
-    for (int c = 0; c < nn; ++c) {
-      // row = the angle (utils/angular.py:243-245 sums over the row index)
-      const X col = C[i1][G::non(c)];
-      put(c, r, col * Ec);         // Cov(x, sin)
-      put(c, r + 1, -(col * Es));  // Cov(x, cos)
-      put(r, c, col * Ec);
-      put(r + 1, c, -(col * Es));
-    }
-  }
-  // variance-only encodings: the augmented state keeps diag(Ca) only
-  // (full covariance: encode() flattens the augmented matrix as it is)
-  const T jit = ENC == kChol ? chol_jitter_of<T, na>(Cav)
-                             : (ENC == kFull ? T(0) : T(-1));
-  X cost = lift<X>(T(0));
-#pragma unroll
-  for (int c = 0; c < na; ++c) {
-    X row = lift<X>(T(0));
-#pragma unroll
-    for (int r = 0; r < na; ++r) row = row + Q[r * LQ + c] * (Ma[r] - P.goal[r]);
-    cost = cost + row * (Ma[c] - P.goal[c]);
-  }
-  if (!terminal) {
-#pragma unroll
-    for (int c = 0; c < m; ++c) {
-      X row = lift<X>(T(0));
-#pragma unroll
-      for (int r = 0; r < m; ++r)
-        row = row + P.R[r * LR + c] * (u[r] - P.ugoal[r]);
-      cost = cost + row * (u[c] - P.ugoal[c]);
-    }
-  }
-  if (jit >= T(0)) {
-    T trq = T(0);
-#pragma unroll
-    for (int r = 0; r < na; ++r) trq += Q[r * LQ + r];
-    cost = cost + tr + lift<X>(jit * trq);  // tr(Q (Ca + jitter I))
-  } else {
-    cost = cost + trd;  // encode()'s diagonal fall-back
-  }
+#include "gauss_cost_body.inc"
   return cost;
 }
 

@@ -139,10 +139,8 @@ using pddp::sin_;
 PDDP_DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 PDDP_DEV double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
 using pddp::sqrt_;
-PDDP_DEV float exp_(float x) { return expf(x); }
-PDDP_DEV double exp_(double x) { return exp(x); }
-PDDP_DEV float log_(float x) { return logf(x); }
-PDDP_DEV double log_(double x) { return log(x); }
+using pddp::exp_;
+using pddp::log_;
 template <typename T> PDDP_DEV Dual<T> exp_(Dual<T> a) { const T e = exp_(a.p); return {e, e * a.t}; }
 template <typename T> PDDP_DEV Dual<T> sin_(Dual<T> a) {
   T sv, cv;

@@ -71,6 +71,14 @@ PDDP_DEV float cos_(float x) { return cosf(x); }
 PDDP_DEV double cos_(double x) { return cos(x); }
 PDDP_DEV float abs_(float x) { return fabsf(x); }
 PDDP_DEV double abs_(double x) { return fabs(x); }
+PDDP_DEV float exp_(float x) { return expf(x); }
+PDDP_DEV double exp_(double x) { return exp(x); }
+PDDP_DEV float log_(float x) { return logf(x); }
+PDDP_DEV double log_(double x) { return log(x); }
+// the library's sine and cosine of one argument (models.hpp's sincos_ is the
+// branch-free polynomial: another sine, chosen where it is used)
+PDDP_DEV void sincos_lib(float x, float& s, float& c) { sincosf(x, &s, &c); }
+PDDP_DEV void sincos_lib(double x, double& s, double& c) { sincos(x, &s, &c); }
 
 // Optional HIP events attached to the NEXT sweep dispatch itself
 // (hipExtLaunchKernelGGL): they time the kernel from its own start to its own

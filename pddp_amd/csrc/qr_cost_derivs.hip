@@ -14,14 +14,12 @@
 // hyper-dual numbers (v, d/dx_i, d/dx_j, d2/dx_i dx_j): one lane per pair
 // (i <= j) of the n + m inputs, 120 pairs for cartpole, every (trajectory, time
 // step) in one launch.  The terminal state (no action, Q_term) is step N.
-#include "pddp_common.hpp"
+// The hyper-dual numbers and chol_jitter_of are gauss_numbers.hpp's, the cost
+// itself is gauss_cost_body.inc - the text default_kernels.hip evaluates under
+// the same encoding (tests/test_qr_cost_kernel.py holds both to one model).
+#include "gauss_numbers.hpp"
 
 namespace pddp {
-
-PDDP_DEV float qr_exp(float x) { return expf(x); }
-PDDP_DEV double qr_exp(double x) { return exp(x); }
-PDDP_DEV void qr_sincos(float x, float& s, float& c) { sincosf(x, &s, &c); }
-PDDP_DEV void qr_sincos(double x, double& s, double& c) { sincos(x, &s, &c); }
 
 // pddp_qr_cost / pddp_qr_cost_f64 with the scalar type as a parameter
 template <typename T>
@@ -47,65 +45,7 @@ struct QrCostV {
 static_assert(sizeof(QrCostV<float>) == sizeof(pddp_qr_cost) &&
               sizeof(QrCostV<double>) == sizeof(pddp_qr_cost_f64), "");
 
-template <typename T>
-struct HDT {  // hyper-dual number
-  typedef T S;
-  T v, a, b, ab;
-};
-template <typename T> PDDP_DEV HDT<T> hd_(typename HDT<T>::S v) { return HDT<T>{v, 0.f, 0.f, 0.f}; }
-template <typename T> PDDP_DEV HDT<T> operator+(HDT<T> x, HDT<T> y) { return HDT<T>{x.v + y.v, x.a + y.a, x.b + y.b, x.ab + y.ab}; }
-template <typename T> PDDP_DEV HDT<T> operator-(HDT<T> x, HDT<T> y) { return HDT<T>{x.v - y.v, x.a - y.a, x.b - y.b, x.ab - y.ab}; }
-template <typename T> PDDP_DEV HDT<T> operator-(HDT<T> x) { return HDT<T>{-x.v, -x.a, -x.b, -x.ab}; }
-template <typename T> PDDP_DEV HDT<T> operator*(HDT<T> x, HDT<T> y) {
-  return HDT<T>{x.v * y.v, x.a * y.v + x.v * y.a, x.b * y.v + x.v * y.b,
-            x.ab * y.v + x.a * y.b + x.b * y.a + x.v * y.ab};
-}
-template <typename T> PDDP_DEV HDT<T> operator*(typename HDT<T>::S s, HDT<T> x) { return HDT<T>{s * x.v, s * x.a, s * x.b, s * x.ab}; }
-template <typename T> PDDP_DEV HDT<T> operator+(HDT<T> x, typename HDT<T>::S s) { return HDT<T>{x.v + s, x.a, x.b, x.ab}; }
-template <typename T> PDDP_DEV HDT<T> operator-(HDT<T> x, typename HDT<T>::S s) { return HDT<T>{x.v - s, x.a, x.b, x.ab}; }
-template <typename T> PDDP_DEV HDT<T> exp_(HDT<T> x) {
-  const T e = qr_exp(x.v);
-  return HDT<T>{e, e * x.a, e * x.b, e * (x.ab + x.a * x.b)};
-}
-template <typename T> PDDP_DEV void sincos_(HDT<T> x, HDT<T>& s, HDT<T>& c) {
-  T sv, cv;
-  qr_sincos(x.v, sv, cv);
-  s = HDT<T>{sv, cv * x.a, cv * x.b, cv * x.ab - sv * x.a * x.b};
-  c = HDT<T>{cv, -sv * x.a, -sv * x.b, -sv * x.ab - cv * x.a * x.b};
-}
-
 constexpr int kQrMaxAng = 2, kQrMaxM = 2;
-
-// the jittered upper Cholesky only decides which trace the cost sees
-// (encoding.py:536-564: jitter 1e-12, 1e-11, ... <= 10, else the diagonal)
-template <typename T, int NA>
-PDDP_DEV T chol_jitter_of(const T (&C)[NA][NA]) {
-  double jit = 1e-12;
-  while (jit <= 10.0) {
-    T U[NA][NA];
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-#pragma unroll
-      for (int j = i; j < NA; ++j) {
-        T s = C[i][j] + (i == j ? (T)jit : 0.f);
-#pragma unroll
-        for (int q = 0; q < i; ++q) s -= U[q][i] * U[q][j];
-        if (i == j) {
-          // (a failed pivot ends the reference's attempt; what follows here
-          // is computed on garbage and discarded)
-          if (!(s > 0.f)) ok = false;
-          U[i][i] = sqrt_(s);
-        } else {
-          U[i][j] = s / U[i][i];
-        }
-      }
-    }
-    if (ok) return (T)jit;
-    jit *= 10.0;
-  }
-  return -1.f;
-}
 
 // D state dimensions of which NANG are angles: every index below is a compile-
 // time constant (the state is permuted to non-angular | angular as it is
@@ -115,7 +55,7 @@ PDDP_DEV T chol_jitter_of(const T (&C)[NA][NA]) {
 // double cartpole, D = 6; 10 ms for cartpole.)
 template <typename T, int D, int NANG>
 __global__ __launch_bounds__(64) void qr_cost_derivs_kernel(QrCostV<T> s) {
-  using HD = HDT<T>;
+  using HD = HDual<T>;
   auto hd = [](T v) { return HD{v, 0.f, 0.f, 0.f}; };
   constexpr int n = D + D * (D + 1) / 2;
   constexpr int NN = D - NANG;       // non-angular dimensions
@@ -197,84 +137,29 @@ __global__ __launch_bounds__(64) void qr_cost_derivs_kernel(QrCostV<T> s) {
 #pragma unroll
       for (int c = 0; c < a; ++c) C[a][c] = C[c][a];
 
-    T Cav[NA][NA];
-    HD Ma[NA];
-    HD tr = hd(0.f), trd = hd(0.f);  // sum Ca_ij Q_ji; sum Ca_ii Q_ii
-    auto put = [&](int r, int c, HD v) {  // every entry is written once
-      Cav[r][c] = v.v;
-      tr = tr + Qr[c][r] * v;
-      if (r == c) trd = trd + Qr[r][r] * v;
-    };
-#pragma unroll
-    for (int r = 0; r < NN; ++r) {
-      Ma[r] = mu[r];
-#pragma unroll
-      for (int c = 0; c < NN; ++c) put(r, c, C[r][c]);
-    }
-#pragma unroll
-    for (int a1 = 0; a1 < NANG; ++a1) {
-      const int i1 = NN + a1;
-      const HD m1 = mu[i1], v1 = C[i1][i1];
-      const HD damp = exp_(-0.5f * v1);
-      HD s1, c1;
-      sincos_(m1, s1, c1);
-      const HD Es = damp * s1, Ec = damp * c1;
-      const int r = NN + 2 * a1;
-      Ma[r] = Es;
-      Ma[r + 1] = Ec;
-#pragma unroll
-      for (int a2 = 0; a2 < NANG; ++a2) {
-        const int i2 = NN + a2;
-        const HD m2 = mu[i2], v2 = C[i2][i2], cij = C[i1][i2];
-        const HD lq = -0.5f * (v1 + v2), qq = exp_(lq);
-        const HD ep = exp_(lq + cij) - qq, em = exp_(lq - cij) - qq;
-        HD sd, cd, ss, cs;
-        sincos_(m1 - m2, sd, cd);
-        sincos_(m1 + m2, ss, cs);
-        const int cc = NN + 2 * a2;
-        put(r, cc, 0.5f * (ep * cd - em * cs));          // sin, sin
-        put(r + 1, cc + 1, 0.5f * (ep * cd + em * cs));  // cos, cos
-        const HD sc = 0.5f * (ep * sd + em * ss);        // sin_1, cos_2
-        put(r, cc + 1, sc);
-        put(cc + 1, r, sc);
-      }
-#pragma unroll
-      for (int c = 0; c < NN; ++c) {
-        const HD col = C[c][i1];
-        put(c, r, col * Ec);        // Cov(x, sin)
-        put(c, r + 1, -(col * Es));  // Cov(x, cos)
-        put(r, c, col * Ec);
-        put(r + 1, c, -(col * Es));
-      }
-    }
-    if (!have_jit) {  // values only: the same for every pair of this step
-      jit = chol_jitter_of<T, NA>(Cav);
-      have_jit = true;
-    }
-    HD cost = hd(0.f);
-#pragma unroll
-    for (int c = 0; c < NA; ++c) {
-      HD row = hd(0.f);
-#pragma unroll
-      for (int r = 0; r < NA; ++r) row = row + Qr[r][c] * (Ma[r] - goal[r]);
-      cost = cost + row * (Ma[c] - goal[c]);
-    }
-    if (!terminal) {
-      for (int c = 0; c < m; ++c) {
-        HD row = hd(0.f);
-        for (int r = 0; r < m; ++r)
-          row = row + s.R[r * m + c] * (in(n + r, u[r]) - s.u_goal[r]);
-        cost = cost + row * (in(n + c, u[c]) - s.u_goal[c]);
-      }
-    }
-    if (jit >= 0.f) {
-      T trq = 0.f;
-#pragma unroll
-      for (int r = 0; r < NA; ++r) trq += Qr[r][r];
-      cost = cost + tr + jit * trq;  // tr(Q (Ca + jitter I))
-    } else {
-      cost = cost + trd;             // encode()'s diagonal fall-back
-    }
+    using X = HD;
+#define PDDP_COST_ZERO hd(0.f)
+#define PDDP_COST_MU(a) mu[a]
+#define PDDP_COST_COV(a, c) C[a][c]
+#define PDDP_COST_Q(r, c) Qr[r][c]
+#define PDDP_COST_GOAL(r) goal[r]
+    /* values only: the same for every pair of this step */
+#define PDDP_COST_JITTER                  \
+  if (!have_jit) {                        \
+    jit = chol_jitter_of<T, NA>(Cav);     \
+    have_jit = true;                      \
+  }
+#define PDDP_COST_JITTER_TERM(v) (v)
+#define PDDP_COST_ACTION                                                    \
+  if (!terminal) {                                                          \
+    for (int c = 0; c < m; ++c) {                                           \
+      HD row = hd(0.f);                                                     \
+      for (int r = 0; r < m; ++r)                                           \
+        row = row + s.R[r * m + c] * (in(n + r, u[r]) - s.u_goal[r]);       \
+      cost = cost + row * (in(n + c, u[c]) - s.u_goal[c]);                  \
+    }                                                                       \
+  }
+#include "gauss_cost_body.inc"
 
     // ---- scatter: value, gradient (diagonal pairs), Hessian (both triangles)
     const size_t st = (size_t)b * (N + 1) + t;  // state index incl. terminal

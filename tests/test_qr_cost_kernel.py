@@ -10,6 +10,10 @@ regimes of the encoded state:
   (c) the Cholesky part exactly zero
   (d) angle variances in [4, 9], angle means 50 randn
 
+And once on the nominal of an ILQRSolver under the DEFAULT encoding, beside
+the cost blocks of `pddp_derivs_*` (csrc/default_kernels.hip), which evaluates
+the same text (csrc/gauss_cost_body.inc): both against the model, by one rule.
+
 CPU tests: the model against the package's float64 torch path (which the
 goldens pin), the entry point's refusals, and the batch invariance of
 `encode` under UPPER_TRIANGULAR_CHOLESKY.
@@ -467,6 +471,51 @@ def predicted_rungs(D, ang, Z, np_dtype):
     return torch.tensor(r, dtype=torch.float64).reshape(Ca.shape[:-2])
 
 
+def hold_to_model(out, mo, D, ang, m, c, Z, Uc, dtype, first_rung, tag):
+    """The rule of test_kernel_vs_float64_model for one set of blocks `out`
+    (in `dtype`, on the CPU) against the model's `mo` at the same inputs;
+    `first_rung`: the f32 value must sit on rung 1e-12."""
+    for k in BLOCKS:
+        assert torch.isfinite(out[k]).all(), k
+    assert torch.equal(out["L_zz"], out["L_zz"].transpose(-1, -2))
+    assert torch.equal(out["L_uu"], out["L_uu"].transpose(-1, -2))
+    out = {k: v.double() for k, v in out.items()}
+    lad = qm.ladder()
+    if dtype == torch.float64:
+        assert (predicted_rungs(D, ang, Z, np.float64) == lad[0]).all()
+        S = magnitude(D, ang, m, c, Z, Uc)
+        margin = 64 * EPS64 * S / mo["trQ"]
+        measured = (out["L"] - mo["L0"]) / mo["trQ"]
+        print("QRCOST", *tag, "rung", float(measured.min()),
+              float(measured.max()), "margin", float(margin.max()))
+        assert float(margin.max()) < 0.9e-12
+        assert ((measured - lad[0]).abs() <= margin).all(), measured
+        for k in BLOCKS[1:]:
+            e = rel(out[k], mo[k])
+            print("QRCOST", *tag, k, e)
+            assert e <= 1e-10, (k, e)
+        assert rel(out["L"], mo["L0"] + lad[0] * mo["trQ"]) <= 1e-10
+        return
+    ref = torch_path(stub_cost(D, ang, c, m), Z, Uc, torch.float32)
+    rungs = lad[:1] if first_rung else [r for r in lad if r <= 1.0001e-4]
+    ek, chosen = value_error(out["L"], mo, rungs)
+    et, _ = value_error(ref["L"], mo, lad)
+    bar = max(8 * et, 16 * EPS32)
+    # the lowest rung each entry is consistent with, as far as L resolves it
+    fits = torch.stack([(out["L"] - mo["L0"] - r * mo["trQ"]).abs() <=
+                        bar * mo["L0"].abs().max() for r in lad], -1)
+    lowest = torch.tensor(lad)[fits.double().argmax(-1)]
+    pred = predicted_rungs(D, ang, Z, np.float32)
+    print("QRCOST", *tag, "L", ek, et, "rung: lowest consistent",
+          float(lowest.max()), "best fit", float(chosen.max()),
+          "model f32 Cholesky", float(pred.max()))
+    assert ek <= bar, ("L", ek, et)
+    for k in BLOCKS[1:]:
+        ek, et = rel(out[k], mo[k]), rel(ref[k], mo[k])
+        print("QRCOST", *tag, k, ek, et)
+        assert ek <= max(8 * et, 16 * EPS32), (k, ek, et)
+
+
 @pytest.mark.gpu
 @DTYPES
 @pytest.mark.parametrize("regime,m,bounds", CASES, ids=CASE_IDS)
@@ -492,46 +541,9 @@ def test_kernel_vs_float64_model(shape, regime, m, bounds, dtype):
     mo = model_blocks(D, ang, m, regime, dtype, bounds)
     out, guards = launch(D, ang, m, c, Z, U, dtype, bounds)
     for k in BLOCKS:
-        assert torch.isfinite(out[k]).all(), k
         assert torch.isnan(guards[k]).all(), k
-    assert torch.equal(out["L_zz"], out["L_zz"].transpose(-1, -2))
-    assert torch.equal(out["L_uu"], out["L_uu"].transpose(-1, -2))
-    out = {k: v.double() for k, v in out.items()}
-    lad = qm.ladder()
     tag = (str(dtype)[-3:], SHAPE_IDS[SHAPES.index(shape)], m, bounds, regime)
-    if dtype == torch.float64:
-        assert (predicted_rungs(D, ang, Z, np.float64) == lad[0]).all()
-        S = magnitude(D, ang, m, c, Z, Uc)
-        margin = 64 * EPS64 * S / mo["trQ"]
-        measured = (out["L"] - mo["L0"]) / mo["trQ"]
-        print("QRCOST", *tag, "rung", float(measured.min()),
-              float(measured.max()), "margin", float(margin.max()))
-        assert float(margin.max()) < 0.9e-12
-        assert ((measured - lad[0]).abs() <= margin).all(), measured
-        for k in BLOCKS[1:]:
-            e = rel(out[k], mo[k])
-            print("QRCOST", *tag, k, e)
-            assert e <= 1e-10, (k, e)
-        assert rel(out["L"], mo["L0"] + lad[0] * mo["trQ"]) <= 1e-10
-        return
-    ref = torch_path(stub_cost(D, ang, c, m), Z, Uc, torch.float32)
-    rungs = lad[:1] if regime in "ac" else [r for r in lad if r <= 1.0001e-4]
-    ek, chosen = value_error(out["L"], mo, rungs)
-    et, _ = value_error(ref["L"], mo, lad)
-    bar = max(8 * et, 16 * EPS32)
-    # the lowest rung each entry is consistent with, as far as L resolves it
-    fits = torch.stack([(out["L"] - mo["L0"] - r * mo["trQ"]).abs() <=
-                        bar * mo["L0"].abs().max() for r in lad], -1)
-    lowest = torch.tensor(lad)[fits.double().argmax(-1)]
-    pred = predicted_rungs(D, ang, Z, np.float32)
-    print("QRCOST", *tag, "L", ek, et, "rung: lowest consistent",
-          float(lowest.max()), "best fit", float(chosen.max()),
-          "model f32 Cholesky", float(pred.max()))
-    assert ek <= bar, ("L", ek, et)
-    for k in BLOCKS[1:]:
-        ek, et = rel(out[k], mo[k]), rel(ref[k], mo[k])
-        print("QRCOST", *tag, k, ek, et)
-        assert ek <= max(8 * et, 16 * EPS32), (k, ek, et)
+    hold_to_model(out, mo, D, ang, m, c, Z, Uc, dtype, regime in "ac", tag)
 
 
 def _sick_rows(D, ang, count):
@@ -608,3 +620,56 @@ def test_clamp_equals_passing_the_clamped_action(shape, dtype):
         assert torch.equal(a[k], b[k]), k
     free, _ = launch(D, ang, m, c, Z, U, dtype, False)
     assert not torch.equal(a["L_u"], free["L_u"])
+
+
+@pytest.mark.gpu
+@DTYPES
+@pytest.mark.parametrize("name", ["cartpole", "pendulum", "double_cartpole"])
+def test_records_and_cost_kernel_share_the_cost(name, dtype):
+    """The two users of csrc/gauss_cost_body.inc on one nominal: the cost
+    blocks of `pddp_derivs_*` under the DEFAULT encoding (ILQRSolver's
+    records, B = 2, N = 2, the shipped cost, bounded) and the blocks of
+    `pddp_qr_cost_derivs_*` on the same Z, U, Q, Q_term, R and goals, each
+    held to the float64 model by the rule and the bars of
+    test_kernel_vs_float64_model.  The nominal is a rollout from regime-(a)
+    states, whose factors the dynamics turn into diagonals of the same size:
+    rung 1e-12 in both dtypes."""
+    import pddp_amd
+    from pddp_amd.controllers.solver import ILQRSolver
+    cost, mc = _shipped(name)
+    D, m = mc.state_size, mc.action_size
+    ang = tuple(int(i) for i in mc.angular_indices)
+    NA, n = D + len(ang), qm.encoded_size(D)
+    Bq, Nq = 2, 2
+    r = (lambda t: t.float().double()) if dtype == torch.float32 \
+        else (lambda t: t)
+    f64 = lambda t, k: r(torch.as_tensor(t).detach().double().expand(
+        *k).clone())
+    c = dict(Q=f64(cost.Q, (NA, NA)), Q_term=f64(cost.Q_term, (NA, NA)),
+             R=f64(cost.R, (m, m)), x_goal=f64(cost.x_goal, (NA,)),
+             u_goal=f64(cost.u_goal, (m,)),
+             u_min=torch.full((m,), -0.25, dtype=torch.float64),
+             u_max=torch.full((m,), 0.25, dtype=torch.float64))
+    z0 = r(states(D, ang, "a", Bq, 21))
+    g = torch.Generator().manual_seed(22)
+    U = r(torch.rand(Bq, Nq, m, generator=g, dtype=torch.float64) - 0.5)
+    prob = mc(0.05).native_problem(pddp_amd.StateEncoding.DEFAULT, cost)
+    s = ILQRSolver(prob, Bq, Nq, dtype, "cuda:0", c["u_min"], c["u_max"])
+    s.set_nominal(z0.cuda(), U.cuda())
+    s.derivs()
+    torch.cuda.synchronize()
+    Z = s.Z.cpu().double()
+    assert torch.equal(Z[:, 0], z0)
+    Uc = clamped(c, U, True)
+    assert bool((Uc != U).any())
+    _, _, L_z, L_u, L_zz, L_uz, L_uu = s.record_views()
+    records = {k: v.cpu().clone() for k, v in dict(
+        L=s.L, L_z=L_z, L_u=L_u, L_zz=L_zz, L_uz=L_uz, L_uu=L_uu).items()}
+    kernel, guards = launch(D, ang, m, c, Z, U, dtype, True)
+    for k in BLOCKS:
+        assert torch.isnan(guards[k]).all(), k
+    mo = model_on(D, ang, m, c, Z, Uc)
+    for who, out in (("records", records), ("qr_cost", kernel)):
+        assert all(out[k].shape == mo[k].shape for k in BLOCKS[1:]), who
+        hold_to_model(out, mo, D, ang, m, c, Z, Uc, dtype, True,
+                      (str(dtype)[-3:], name, who))
