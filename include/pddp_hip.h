@@ -776,13 +776,15 @@ int pddp_mppi_trial_f64(
     double* ess_log, double* plan_log, void* stream);
 
 /* ---- the sampling planners under the line search's objective: pddp_shoot_*,
- * pddp_mppi_* and pddp_mppi_trial_* above along a reference (a goal per time
- * step, pddp_line_search_track_*) and / or under per-trajectory cost weights
- * (pddp_line_search_weighted_*) (the *_goals_kernel of csrc/shoot.hip,
- * mppi.hip, mppi_trial.hip; the reference has no counterpart).  Nothing changes in how candidates are drawn, clamped,
- * selected, weighted or summed: the three laws above hold word for word.  Only
- * the cost every rollout is summed under changes - the candidates', the
- * winner's second pass in shoot, the weighted sequence's in mppi and the trial:
+ * pddp_mppi_*, pddp_cem_* and pddp_mppi_trial_* above along a reference (a
+ * goal per time step, pddp_line_search_track_*) and / or under per-trajectory
+ * cost weights (pddp_line_search_weighted_*) (the *_goals_kernel of
+ * csrc/shoot.hip, mppi.hip, cem.hip, mppi_trial.hip; the reference has no
+ * counterpart).  Nothing changes in how candidates are drawn, clamped,
+ * selected, ranked, weighted or summed: the four laws above hold word for
+ * word.  Only the cost every rollout is summed under changes - the
+ * candidates', the winner's second pass in shoot, the weighted sequence's in
+ * mppi and the trial, the refitted mean's in cem:
  *
  *   P_b = the shared problem, the parameters of row b of `table` where one is
  *         given (with a reference the table's goal fields are NOT read), then,
@@ -805,6 +807,13 @@ int pddp_mppi_trial_f64(
  *   _track_            (problem, table, ref, ref_len, ref_t0, ...)
  *   _weighted_         (problem, table, weights, ...)
  *   _track_weighted_   (problem, table, ref, ref_len, ref_t0, weights, ...)
+ *
+ * pddp_cem_track_*, pddp_cem_weighted_*, pddp_cem_track_weighted_*:
+ * pddp_cem_*'s word for word, every rollout - the candidates' and the refitted
+ * mean's - costed along the reference and / or under the weights.  The ranks,
+ * the elites and both moments are pddp_cem_*'s on these costs; Um's step t is
+ * costed under row min(ref_t0 + t, ref_len - 1), the terminal term of J_m
+ * under row min(ref_t0 + N, ref_len - 1).
  *
  * pddp_mppi_trial_goals_* takes pddp_mppi_trial_*'s parameters with `ref,
  * ref_len, ref_t0, weights` after `plant`; both additions are nullable, at
@@ -870,6 +879,31 @@ int pddp_mppi_track_weighted_f64(const pddp_problem* problem,
                                  int ref_len, int ref_t0,
                                  const double* weights,
                                  PDDP_MPPI_REST(double));
+#define PDDP_CEM_REST(T)                                                       \
+  int B, int N, int S, int K, const T* z0, const T* U, const T* u_min,         \
+      const T* u_max, const T* sigma, const T* std_min, double smooth,         \
+      double mix, uint64_t seed, uint64_t sample_offset,                       \
+      const uint8_t* active, T* Jc, int32_t* rank, int32_t* best, T* J_best,   \
+      int32_t* n_elite, T* J_m, T* Z_out, T* U_out, T* S_out, void* stream
+int pddp_cem_track_f32(const pddp_problem* problem, const float* table,
+                       const float* ref, int ref_len, int ref_t0,
+                       PDDP_CEM_REST(float));
+int pddp_cem_track_f64(const pddp_problem* problem, const double* table,
+                       const double* ref, int ref_len, int ref_t0,
+                       PDDP_CEM_REST(double));
+int pddp_cem_weighted_f32(const pddp_problem* problem, const float* table,
+                          const float* weights, PDDP_CEM_REST(float));
+int pddp_cem_weighted_f64(const pddp_problem* problem, const double* table,
+                          const double* weights, PDDP_CEM_REST(double));
+int pddp_cem_track_weighted_f32(const pddp_problem* problem,
+                                const float* table, const float* ref,
+                                int ref_len, int ref_t0, const float* weights,
+                                PDDP_CEM_REST(float));
+int pddp_cem_track_weighted_f64(const pddp_problem* problem,
+                                const double* table, const double* ref,
+                                int ref_len, int ref_t0, const double* weights,
+                                PDDP_CEM_REST(double));
+#undef PDDP_CEM_REST
 #undef PDDP_MPPI_REST
 #undef PDDP_SHOOT_REST
 int pddp_mppi_trial_goals_f32(

@@ -128,6 +128,9 @@ _SIGS = {
     "pddp_mppi_track": [_P, _P] + _REF + _MPPI,
     "pddp_mppi_weighted": [_P, _P, _P] + _MPPI,
     "pddp_mppi_track_weighted": [_P, _P] + _REF + [_P] + _MPPI,
+    "pddp_cem_track": [_P, _P] + _REF + _CEM,
+    "pddp_cem_weighted": [_P, _P, _P] + _CEM,
+    "pddp_cem_track_weighted": [_P, _P] + _REF + [_P] + _CEM,
     "pddp_mppi_trial_goals": [_P] * 3 + _REF + [_P] + [c_int] * 7 + [_P] * 8 +
                              [c_double] + [c_uint64] * 3 + [_P] * 3 +
                              [c_uint64, c_int] + [_P] * 3 + [c_int] + [_P] * 9,
@@ -210,6 +213,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_shoot_track", "pddp_shoot_weighted",
           "pddp_shoot_track_weighted", "pddp_mppi_track", "pddp_mppi_weighted",
           "pddp_mppi_track_weighted", "pddp_mppi_trial_goals",
+          "pddp_cem_track", "pddp_cem_weighted", "pddp_cem_track_weighted",
           "pddp_derivs_track", "pddp_line_search_track",
           "pddp_mpc_advance_track",
           "pddp_mpc_advance_noisy", "pddp_mpc_observe",

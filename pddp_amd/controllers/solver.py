@@ -1329,7 +1329,7 @@ class ILQRSolver(object):
     @_on_device
     def cem(self, samples, std, elites, iterations=1, std_min=0.0, mix=0.0,
             smooth=0.0, seed=0, sample_offset=0, active=None, adopt=True,
-            events=None):
+            events=None, objective="shared"):
         """Sampled shooting with a cross-entropy (CEM) refit of the
         distribution the candidates are drawn from (pddp_cem_*, csrc/cem.hip):
         `shoot`'s S = `samples` candidates around the mean - the current `U` -
@@ -1365,11 +1365,15 @@ class ILQRSolver(object):
         incumbent's rows.  `events`: a (start, stop) pair for the dispatch,
         with one iteration only.
 
-        Refused while a reference or per-trajectory cost weights are set: the
-        candidates would be costed under another objective than the line
-        search's."""
+        `objective`: as `shoot` - "shared" refuses while a reference or
+        per-trajectory cost weights are set, "search" costs the candidates
+        and every iteration's mean under the line search's objective
+        (pddp_cem_track_*, _weighted_*, _track_weighted_*): `J_trace[0]` is
+        then the current nominal's cost under it, and the incumbent is never
+        worse than the start under the objective `rounds()` optimises.
+        `ref_start` is read, not moved."""
         self._need_sample_problem("cem")
-        self._one_sampled_objective("cem")
+        goals = self._one_sampled_objective("cem", objective)
         B, N, n, m = self.B, self.N, self.n, self.m
         S, K, iters = int(samples), int(elites), int(iterations)
         if S < 1:
@@ -1403,7 +1407,9 @@ class ILQRSolver(object):
             # (rows without a refit are never selected)
             Zm, Um = self._out(False, B, N + 1, n), self._out(False, B, N, m)
             Sm = self._out(False, B, N, m)
-            self._launch(events, self._problem_call, "pddp_cem", B, N, S, K,
+            self._launch(events,
+                         functools.partial(self._problem_call, goals=goals),
+                         "pddp_cem", B, N, S, K,
                          p(self.z0), p(mean), p(self.u_min), p(self.u_max),
                          p(sigma), p(floor), float(smooth), float(mix),
                          int(seed), int(sample_offset) + k * B * S, p(active),
@@ -1429,12 +1435,12 @@ class ILQRSolver(object):
         return out
 
     def _one_sampled_objective(self, what, objective="shared"):
-        """The `objective` of `shoot`, `mppi` and `mppi_closed_loop`.
+        """The `objective` of `shoot`, `mppi`, `cem` and `mppi_closed_loop`.
         "shared": the refusal while a reference or per-trajectory cost
         weights are set.  "search": True where the candidates are costed
         along the reference and / or under the weights (the entry points of
-        csrc/shoot.hip, mppi.hip), False where neither is set - the call is
-        then the one "shared" makes."""
+        csrc/shoot.hip, mppi.hip, cem.hip), False where neither is set - the
+        call is then the one "shared" makes."""
         if objective == "search":
             return self.reference is not None or \
                 self.batch_weights is not None

@@ -3,8 +3,10 @@
 // component (sigma [B][N][m]) around the mean U, costed by the same law, the K
 // cheapest ("elites") found inside the launch, and the mean AND the width
 // refitted to them; the new mean is rolled out and costed in the same launch
-// (pddp_cem_*, pddp_cem_batch_*, ILQRSolver.cem).  The reference has no
-// counterpart: include/pddp_hip.h states the law, DESIGN.md 3.4s the kernel.
+// (pddp_cem_*, pddp_cem_batch_*, ILQRSolver.cem); the same under the line
+// search's objective (pddp_cem_track_*, _weighted_*, _track_weighted_*;
+// objective="search": shoot.hip's header has the law).  The reference has no
+// counterpart: include/pddp_hip.h states the law, DESIGN.md 3.4s the kernels.
 //
 //   Jc[b][s]      pddp_shoot_*'s, with sigma[b][t][j] in a_std[j]'s place
 //   rank[b][s]    the number of finite (Jc, s') lexicographically below
@@ -17,8 +19,10 @@
 //        sqrt(V) - sigma), std_min);  Zm, J_m: Um's rollout and its cost
 //
 // The candidate rollout is the family's one text (sampled_rollout_body.inc)
-// through its width hook; the sums are sampled_common.hpp's group_sum.  One
-// kernel per model and type (cem_kernel_body.inc), with mppi_kernel's mapping.
+// through its width hook; the sums are sampled_common.hpp's group_sum.  Two
+// kernels per model and type over ONE text (cem_kernel_body.inc), with
+// mppi_kernel's mapping: cem_kernel with its nullable table, cem_goals_kernel
+// with its nullable reference and weights.
 //
 // Three passes over the same ceil(S / G) turns of the lane group:
 //   1. the candidates' rollouts, row t + 1 of sigma[b] requested a step ahead;
@@ -32,7 +36,8 @@
 //      dynamics: at every step t the 2m values (e, e e) are summed over the
 //      group, the turns in their order by ONE lane per trajectory, which in
 //      the last turn has the whole sums, forms Um[b][t] and Sm[b][t] and steps
-//      the mean's rollout.
+//      the mean's rollout - in the goals kernel under row ref_t0 + t of the
+//      reference, its terminal term under row ref_t0 + N.
 // Every shuffle and barrier sits under launch-uniform control flow: the turn
 // count, N and m are uniform, lanes outside the batch, masked or without an
 // elite take part with zeros.  The order of every sum and of the ranking
@@ -65,6 +70,31 @@ struct CemArgs {
   T* S_out;
 };
 
+// The goals kernel's block: CemArgs without `table` (RefArgs carries it) - a
+// type of its own because the kernel's argument layout is.
+template <typename T>
+struct CemGoalsArgs {
+  int B, N, S, G, K;
+  const T* z0;
+  const T* U;
+  const T* u_min;
+  const T* u_max;
+  const T* sigma;
+  const T* std_min;
+  T beta, gamma, step;
+  uint64_t seed, offset;
+  const uint8_t* active;
+  T* Jc;
+  int32_t* rank;
+  int32_t* best;
+  T* J_best;
+  int32_t* n_elite;
+  T* J_m;
+  T* Z_out;
+  T* U_out;
+  T* S_out;
+};
+
 // the width of step t in `sg`, that of step t + 1 requested next to `ur2`
 #define PDDP_SAMPLED_AFTER_E0                                                  \
   T sg[m], sg2[m];                                                             \
@@ -80,11 +110,37 @@ struct CemArgs {
 #define PDDP_PROBLEM_OF_B PDDP_PLAIN_PROBLEM_OF_B
 #define PDDP_ROW_OF_B PDDP_PLAIN_ROW_OF_B
 #define PDDP_GOALS(point)
+#define PDDP_CEM_CUT_J Jcut
+#define PDDP_CEM_FLOOR(r) smin[r]
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kClosedLoopThreads) void cem_kernel(
     ProblemT<T> shared, CemArgs<T> a) {
 #include "cem_kernel_body.inc"
 }
+#undef PDDP_CEM_FLOOR
+#undef PDDP_CEM_CUT_J
+#undef PDDP_GOALS
+#undef PDDP_ROW_OF_B
+#undef PDDP_PROBLEM_OF_B
+
+#define PDDP_PROBLEM_OF_B PDDP_GOALS_PROBLEM_OF_B
+#define PDDP_ROW_OF_B
+#define PDDP_GOALS(point) PDDP_GOALS_##point
+// (The goals every lane carries through pass 3 take the float64 double
+// cartpole and rendezvous past 256 registers; with the cut's cost and the
+// floor held across the passes as well, four vector registers spill.  Here
+// both are read again where pass 3 uses them - the same words: cut_J[] is not
+// written after pass 2's last barrier - and nothing spills.)
+#define PDDP_CEM_CUT_J (ok ? cut_J[group] : Jcut)
+#define PDDP_CEM_FLOOR(r) (a.std_min != nullptr ? a.std_min[r] : smin[r])
+template <typename T, int MODEL>
+__global__ __launch_bounds__(kClosedLoopThreads) void cem_goals_kernel(
+    ProblemT<T> shared, CemGoalsArgs<T> a, RefArgs<T> goals,
+    const T* weights) {
+#include "cem_kernel_body.inc"
+}
+#undef PDDP_CEM_FLOOR
+#undef PDDP_CEM_CUT_J
 #undef PDDP_GOALS
 #undef PDDP_ROW_OF_B
 #undef PDDP_PROBLEM_OF_B
@@ -101,8 +157,16 @@ static int launch_cem(const pddp_problem& p, CemArgs<T> a, hipStream_t st) {
   return launch_sampled<T>(cem_kernel<T, MODEL>, p, a, st);
 }
 
-// One impl and one argument test through the form (goal_form.hpp), as
-// mppi_impl; the plain form and _batch are the ones exported so far.
+template <typename T, int MODEL>
+static int launch_cem_goals(const pddp_problem& p,
+                            With<CemGoalsArgs<T>, FormGoals<T>> w,
+                            hipStream_t st) {
+  return launch_sampled<T>(cem_goals_kernel<T, MODEL>, p, w.a, st, w.x.goals,
+                           w.x.weights);
+}
+
+// One impl and one argument test for the five entry-point families: what a
+// form does not bring is null (goal_form.hpp).
 template <typename T>
 static int cem_impl(const pddp_problem* p, const GoalForm<T>& f,
                     PDDP_CEM_PARAMS(T)) {
@@ -116,12 +180,19 @@ static int cem_impl(const pddp_problem* p, const GoalForm<T>& f,
       !(smooth >= 0.0 && smooth < 1.0) ||  // (NaN fails both)
       !(mix >= 0.0 && mix < 1.0))
     return PDDP_E_BADARG;
-  FormGoals<T> x{};
-  if (!form_goals(f, &x)) return PDDP_E_BADARG;
+  With<CemGoalsArgs<T>, FormGoals<T>> w{};
+  if (!form_goals(f, &w.x)) return PDDP_E_BADARG;
   if (int rc = check_problem(p)) return rc;
-  if (f.goals) return PDDP_E_UNSUPPORTED;  // (no goals kernel yet)
   const T beta = (T)smooth, gamma = (T)std::sqrt(1.0 - smooth * smooth);
   const T step = (T)(1.0 - mix);
+  if (f.goals) {
+    w.a = CemGoalsArgs<T>{B,     N,      S,     0,     K,       z0,
+                          U,     u_min,  u_max, sigma, std_min, beta,
+                          gamma, step,   seed,  sample_offset,  active,
+                          Jc,    rank,   best,  J_best, n_elite, J_m,
+                          Z_out, U_out,  S_out};
+    PDDP_DISPATCH_MODEL(launch_cem_goals, T, p, w, (hipStream_t)stream)
+  }
   const CemArgs<T> a{B,      N,     S,       0,     K,     z0,    U,
                      f.table, u_min, u_max,  sigma, std_min, beta, gamma,
                      step,   seed,  sample_offset, active, Jc,    rank,
@@ -133,21 +204,7 @@ static int cem_impl(const pddp_problem* p, const GoalForm<T>& f,
 
 extern "C" {
 
-#define PDDP_CEM_ENTRY_POINTS(SUF, T)                                          \
-  int pddp_cem_##SUF(const pddp_problem* p, PDDP_CEM_PARAMS(T)) {              \
-    return pddp::cem_impl<T>(                                                  \
-        p, {false, false, false, false, nullptr, nullptr, 0, 0, nullptr},      \
-        PDDP_CEM_ARGS);                                                        \
-  }                                                                            \
-  /* the same with a problem per trajectory: row b of `table` */               \
-  int pddp_cem_batch_##SUF(const pddp_problem* p, const T* table,              \
-                           PDDP_CEM_PARAMS(T)) {                               \
-    return pddp::cem_impl<T>(                                                  \
-        p, {true, false, false, false, table, nullptr, 0, 0, nullptr},         \
-        PDDP_CEM_ARGS);                                                        \
-  }
-PDDP_CEM_ENTRY_POINTS(f32, float)
-PDDP_CEM_ENTRY_POINTS(f64, double)
-#undef PDDP_CEM_ENTRY_POINTS
+PDDP_FORM_ENTRY_POINTS(cem, f32, float, PDDP_CEM_PARAMS, PDDP_CEM_ARGS)
+PDDP_FORM_ENTRY_POINTS(cem, f64, double, PDDP_CEM_PARAMS, PDDP_CEM_ARGS)
 
 }  // extern "C"

@@ -1,6 +1,10 @@
-// cem_kernel_body.inc - the body of cem_kernel (cem.hip): three passes over the
-// same ceil(S / G) turns of the lane group.  The including kernel has `shared`,
-// `a` (CemArgs) and sampled_common.hpp's hooks, as mppi_kernel_body.inc's.
+// cem_kernel_body.inc - the body of cem_kernel and of cem_goals_kernel
+// (cem.hip): three passes over the same ceil(S / G) turns of the lane group.
+// The including kernel has `shared`, `a` (CemArgs or CemGoalsArgs) and
+// sampled_common.hpp's hooks, as mppi_kernel_body.inc's; in the goals kernel
+// the mean's rollout of pass 3 reads the rows the candidates read.  Two words
+// of pass 3 are the kernel's (cem.hip): PDDP_CEM_CUT_J, the cut's cost, and
+// PDDP_CEM_FLOOR(r), std_min[r] - `Jcut` and `smin[r]` in the plain kernel.
   using D = ModelDims<MODEL>;
   constexpr int n = D::n, m = D::m;
   constexpr int kWaves = kClosedLoopThreads / kWave;
@@ -135,7 +139,10 @@
   // step: s1 (e) and s2 (e e, rounded) of the elites s >= 1 over the group, the
   // turns in their order by the owner, who keeps the running sums in U_out (s1)
   // and S_out (s2) between turns, and in the last turn forms Um[b][t], Sm[b][t]
-  // and steps the mean's rollout.
+  // and steps the mean's rollout.  The goal hooks sit where
+  // mppi_update_body.inc has them and enclose no shuffle and no barrier: every
+  // lane takes its trajectory's rows under the launch-uniform `tracked` alone,
+  // TAKE_FIRST in every turn (pass 1 leaves P with the terminal row's goals).
   __shared__ T part_sum[2][2 * m][kWaves];
   T* Zo = a.Z_out + (size_t)b * (N + 1) * n;
   T* Uo = a.U_out + (size_t)b * N * m;
@@ -153,7 +160,8 @@
     bool draw = false;
     if (ok && s >= 1 && s < S) {
       const T Js = a.Jc[bs];
-      draw = is_finite(Js) && (Js < Jcut || (Js == Jcut && s <= scut));
+      draw = is_finite(Js) && (Js < PDDP_CEM_CUT_J ||
+                               (Js == PDDP_CEM_CUT_J && s <= scut));
     }
     // (more than one turn: S > 256, the rows are there)
     const bool carry = owner && turn > 0 && rows;
@@ -169,9 +177,10 @@
 #pragma unroll
     for (int j = 0; j < n; ++j) z[j] = z0[j];
     if (draw) draw_units<T, m>(a.seed, roll, 0, kSampledStream, e);  // e_0
+    PDDP_GOALS(TAKE_FIRST)
     T J = T(0);
     for (int t = 0; t < N; ++t) {
-      // the next step's mean, width and carried sums, ahead of the chain
+      // the next step's mean, width, carried sums and goals, ahead of the chain
       T ur2[m], sg2[m], prev2[2 * m], p[2 * m];
       const int tn = (t + 1 < N) ? t + 1 : t;
 #pragma unroll
@@ -184,6 +193,7 @@
         // (an explicit fma: the square is rounded before it meets a sum)
         p[m + j] = draw ? fma_of(e[j], e[j], T(0)) : T(0);
       }
+      PDDP_GOALS(REQUEST_NEXT)
       if (draw) {
         T xi[m];
         draw_units<T, m>(a.seed, roll, t + 1, kSampledStream, xi);
@@ -216,7 +226,7 @@
             un[r] = bounded ? clamp_nan(v, umin[r], umax[r]) : v;
             const T sd = fma_of(sg[r], sqrt_of(V), T(0));
             const T w = fma_of(a.step, sd - sg[r], sg[r]);
-            sn[r] = w > smin[r] ? w : smin[r];
+            sn[r] = w > PDDP_CEM_FLOOR(r) ? w : PDDP_CEM_FLOOR(r);
           }
           if (rows) {
             PDDP_COPY(n, Zo + (size_t)t * n, z)
@@ -237,6 +247,7 @@
         prev[j] = prev2[j];
         prev[m + j] = prev2[m + j];
       }
+      PDDP_GOALS(TAKE_NEXT)
     }
     if (owner && last) {
       J += cost_value<T, MODEL>(P, z, nullptr, trig_of<T, MODEL>(z), true);

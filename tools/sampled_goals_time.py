@@ -1,20 +1,24 @@
 """What the line search's objective costs the sampling planners: each new form
-(ILQRSolver.shoot / mppi / mppi_closed_loop with objective="search" along a
-reference, under per-trajectory weights, under both - the *_goals_kernel of
-csrc/shoot.hip, csrc/mppi.hip, csrc/mppi_trial.hip) next to its sibling
+(ILQRSolver.shoot / mppi / cem / mppi_closed_loop with objective="search"
+along a reference, under per-trajectory weights, under both - the
+*_goals_kernel of csrc/shoot.hip, csrc/mppi.hip, csrc/cem.hip,
+csrc/mppi_trial.hip) next to its sibling
 without either (the plain kernel of the same unit) ON THE SAME COMMIT: cartpole f32, 4096 trajectories, horizon 100,
 bounded, base actions 0.1 randn, std 3, smooth 0.7, temperature 100,
 S = 16, 64 and 256.  The reference has N + 1 + steps rows around the shared
 goal, the weights are the shared diagonals x U(1, 2).
 
   shoot, mppi: one launch, adopt=False;
+  cem: one launch, adopt=False, S / 4 elites, mix 0.25: the plain form, the
+       _batch form (a table of the shared rows) and _track_weighted; mppi has
+       a _batch row too, so that both ratios "both" / "batch" come from one run;
   trial: mppi_closed_loop(steps = 20, iterations = 3), time per control step.
 
 The protocol of tools/mppi_time.py: one process, the legs alternating launch
 by launch, events on the dispatch itself (pddp_attach_events), WARM warm-up
 launches, median of REPS with [min, max]; the engine clock before and after
 (rocm-smi, read only) printed with the result:
-    python tools/sampled_goals_time.py [B]"""
+    python tools/sampled_goals_time.py [B] [shoot|mppi|cem|trial ...]"""
 import ctypes
 import os
 import subprocess
@@ -30,6 +34,8 @@ from pddp_amd.utils.encoding import StateEncoding
 B = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 4096
 N, WARM, REPS, STD, SMOOTH, LAM = 100, 5, 20, 3.0, 0.7, 100.0
 STEPS, K = 20, 3
+KINDS = [a for a in sys.argv[1:] if not a.isdigit()] or \
+    ["shoot", "mppi", "cem", "trial"]
 td = torch.float32
 lib = _native.lib()
 
@@ -82,6 +88,8 @@ scale = lambda d: d * torch.from_numpy(
 def solver(form):
     s = ILQRSolver(prob, B, N, td, "cuda", *bounds)
     s.set_nominal(z0, U)
+    if form == "batch":
+        s.set_batch_problem()
     if form in ("ref", "both"):
         s.set_reference(x_ref)
     if form in ("weights", "both"):
@@ -91,7 +99,7 @@ def solver(form):
 
 
 FORMS = ("plain", "ref", "weights", "both")
-solvers = {f: solver(f) for f in FORMS}
+solvers = {f: solver(f) for f in FORMS + ("batch",)}
 lam = torch.full((B,), LAM, dtype=td, device="cuda")
 e0, e1 = event(), event()
 
@@ -105,6 +113,8 @@ def leg(kind, form, S):
             s.shoot(S, STD, adopt=False, **kw)
         elif kind == "mppi":
             s.mppi(S, STD, lam, adopt=False, **kw)
+        elif kind == "cem":
+            s.cem(S, STD, S // 4, mix=0.25, adopt=False, **kw)
         else:
             if s.reference is not None:
                 s.set_reference_start(0)
@@ -116,9 +126,10 @@ def leg(kind, form, S):
 
 
 legs = {}
-for kind in ("shoot", "mppi", "trial"):
+for kind in ("shoot", "mppi", "cem", "trial"):
+    forms = {"mppi": FORMS + ("batch",), "cem": ("plain", "batch", "both")}
     for S in (16, 64, 256):
-        for form in FORMS:
+        for form in forms.get(kind, FORMS) if kind in KINDS else ():
             legs[(kind, S, form)] = leg(kind, form, S)
 
 before = clock()
@@ -137,4 +148,6 @@ med = {k: np.median(v) for k, v in times.items()}
 for (kind, S, form), ts in times.items():
     extra = "" if form == "plain" else \
         "; %.2f x plain" % (med[kind, S, form] / med[kind, S, "plain"])
+    if form == "both" and (kind, S, "batch") in med:
+        extra += "; %.2f x batch" % (med[kind, S, form] / med[kind, S, "batch"])
     print("%s, S %d, %s: %s%s" % (kind, S, form, stats(ts), extra), flush=True)
