@@ -775,6 +775,109 @@ int pddp_mppi_trial_f64(
     double* Ulog, double* Jcl, double* Ylog, double* J0_log, double* Jw_log,
     double* ess_log, double* plan_log, void* stream);
 
+/* ---- a receding-horizon CEM trial, every control step inside ONE launch:
+ * plan by I iterations of pddp_cem_*'s law around a mean and a width, apply
+ * the incumbent's first action to the plant, observe, shift the plan and the
+ * width (csrc/cem_trial.hip; the reference has no counterpart).  The plain
+ * objective only: the shared Q, Q_term, R, one goal per trajectory.
+ * Trajectory b is live when active is NULL or active[b] != 0 and carries two
+ * things between control steps, both in/out: the plan U[b] and the width
+ * sigma[b] its next control step starts from.  Control step c runs over
+ * t0 .. t0 + count - 1 of TT, from what the controller sees, y = z0[b]:
+ *
+ *   1. mean = U[b], width = sigma[b], incumbent = U[b].
+ *   2. plan.  For k = 0 .. I-1: pddp_cem_*'s law above, word for word, from
+ *      x_0 = y under the controller's model (the shared problem with row b of
+ *      `table` written over it), with `mean` as U[b] and `width` as sigma[b],
+ *      candidate (b, s) rollout
+ *        r = cand_offset + (c I + k) iter_stride + b S + s          (uint64)
+ *      of stream 2: Jc[b][.], the ranks, Ke, Um, Sm and J_m (+inf without a
+ *      finite cost; Um, Sm are then not written).
+ *        at k = 0: J_inc = Jc[b][0]  (the mean is candidate 0 and, at k = 0,
+ *                  the incumbent);  Jtrace_log[b][c][0] = J_inc
+ *        Jm_log[b][c][k] = J_m;  nelite_log[b][c][k] = Ke
+ *        better = isfinite(J_m) && J_m <= J_inc: incumbent = Um, J_inc = J_m
+ *        moved  = Ke > 0:                        mean = Um, width = Sm
+ *        Jtrace_log[b][c][k+1] = J_inc
+ *      - the selects ILQRSolver.cem makes on the host between its launches.
+ *   3. apply, observe.  plan_log[b][c] = incumbent; std_log[b][c] = width (the
+ *      one after the last iteration, before step 5); u = clamp(incumbent[0]);
+ *      then pddp_mppi_trial_*'s steps 2 and 3 word for word: Xlog, Ulog, Jcl,
+ *      the disturbance, w and v of streams 0 / 1 at (seed, rollout_offset + b,
+ *      step_offset + c [+ 1]), the terminal cost at c == TT-1, x_true, Ylog,
+ *      z0[b].
+ *   4. U[b][i] = incumbent[i+1], the last row repeated: plain copies of
+ *      unclamped words.
+ *   5. sigma[b] = sigma0[b] where sigma0 is given: every control step restarts
+ *      from the caller's width.  Else sigma[b][i] = width[i+1], the last row
+ *      repeated: the refitted width is carried; it is >= std_min.
+ *
+ * After the last control step of the launch Z[b] is the rollout of the shifted
+ * U[b], clamped, from z0[b] under the controller's model.  The trial keeps no
+ * rank array: the ranks follow exactly from the logged costs.
+ *
+ * iter_stride, a run of trajectories b0.. alone and count control steps in one
+ * launch or in several: as pddp_mppi_trial_* (z0, U, sigma, x_true, Jcl
+ * carried; the work buffers carry nothing between launches).
+ *
+ * Arguments, in this order:
+ *   problem, table, plant     pddp_mppi_trial_*'s
+ *   B, N, S, K, I, TT, t0, count      K: the elites, 1 <= K <= S; I >= 1
+ *   z0 [B][n], U [B][N][m], Z [B][N+1][n]       pddp_mppi_trial_*'s
+ *   mean, width, Um, Sm       [B][N][m] each, workspace: the distribution
+ *                             inside a control step and an iteration's refit
+ *                             (S > 256: Um, Sm also hold the running sums of a
+ *                             lane's turns - the rows always exist here)
+ *   u_min, u_max              pddp_cem_*'s
+ *   sigma [B][N][m]           in: the width control step t0 starts from; out:
+ *                             the one step t0 + count would start from
+ *   sigma0 [B][N][m]          nullable, const
+ *   std_min [m]               nullable: zeros
+ *   smooth, mix               pddp_cem_*'s
+ *   seed, cand_offset, iter_stride, disturbance, w_std, v_std,
+ *   rollout_offset, step_offset, x_true, active
+ *                             pddp_mppi_trial_*'s
+ *   Jc, log_costs             Jc workspace [B][S]; log_costs != 0:
+ *                             [B][TT][I][S], every iteration's costs kept
+ *   Xlog, Ulog, Jcl, Ylog     pddp_mppi_trial_*'s
+ *   Jtrace_log [B][TT][I+1], Jm_log [B][TT][I], nelite_log [B][TT][I] int32,
+ *   plan_log [B][TT][N][m], std_log [B][TT][N][m]       nullable each
+ *   stream
+ *
+ * Domain: the four sample models under PDDP_ENC_IGNORE_UNCERTAINTY.
+ * PDDP_E_BADARG: what pddp_mppi_trial_* refuses (a null problem, z0, U or Jc;
+ * non-positive B, N or S; B S > 0x7fffffff; smooth outside [0, 1) or NaN;
+ * TT < 1, t0 < 0, count < 1, t0 + count > TT; a null Z, Xlog, Ulog or Jcl;
+ * v_std without x_true; step_offset < 0 or step_offset + TT beyond an int);
+ * K < 1 or K > S; I < 1; mix outside [0, 1) or NaN; a null sigma; a work
+ * buffer (mean, width, Um, Sm) that is null or is another buffer of the call.
+ * PDDP_E_UNSUPPORTED: any other encoding.  All before any HIP call. */
+int pddp_cem_trial_f32(
+    const pddp_problem* problem, const float* table, const float* plant, int B,
+    int N, int S, int K, int I, int TT, int t0, int count, float* z0, float* U,
+    float* Z, float* mean, float* width, float* Um, float* Sm,
+    const float* u_min, const float* u_max, float* sigma, const float* sigma0,
+    const float* std_min, double smooth, double mix, uint64_t seed,
+    uint64_t cand_offset, uint64_t iter_stride, const float* disturbance,
+    const float* w_std, const float* v_std, uint64_t rollout_offset,
+    int step_offset, float* x_true, const uint8_t* active, float* Jc,
+    int log_costs, float* Xlog, float* Ulog, float* Jcl, float* Ylog,
+    float* Jtrace_log, float* Jm_log, int32_t* nelite_log, float* plan_log,
+    float* std_log, void* stream);
+int pddp_cem_trial_f64(
+    const pddp_problem* problem, const double* table, const double* plant,
+    int B, int N, int S, int K, int I, int TT, int t0, int count, double* z0,
+    double* U, double* Z, double* mean, double* width, double* Um, double* Sm,
+    const double* u_min, const double* u_max, double* sigma,
+    const double* sigma0, const double* std_min, double smooth, double mix,
+    uint64_t seed, uint64_t cand_offset, uint64_t iter_stride,
+    const double* disturbance, const double* w_std, const double* v_std,
+    uint64_t rollout_offset, int step_offset, double* x_true,
+    const uint8_t* active, double* Jc, int log_costs, double* Xlog,
+    double* Ulog, double* Jcl, double* Ylog, double* Jtrace_log,
+    double* Jm_log, int32_t* nelite_log, double* plan_log, double* std_log,
+    void* stream);
+
 /* ---- the sampling planners under the line search's objective: pddp_shoot_*,
  * pddp_mppi_*, pddp_cem_* and pddp_mppi_trial_* above along a reference (a
  * goal per time step, pddp_line_search_track_*) and / or under per-trajectory

@@ -119,6 +119,13 @@ _SIGS = {
     "pddp_mppi_trial": [_P] * 3 + [c_int] * 7 + [_P] * 8 +
                        [c_double] + [c_uint64] * 3 + [_P] * 3 +
                        [c_uint64, c_int] + [_P] * 3 + [c_int] + [_P] * 9,
+    # (a whole CEM trial: problem, table, plant; B N S K I TT t0 count; z0, U,
+    # Z, mean, width, Um, Sm, u_min, u_max, sigma, sigma0, std_min; smooth,
+    # mix; seed, cand_offset, iter_stride; then as the MPPI trial, with the
+    # logs Xlog, Ulog, Jcl, Ylog, Jtrace, Jm, nelite, plan, std)
+    "pddp_cem_trial": [_P] * 3 + [c_int] * 8 + [_P] * 12 +
+                      [c_double] * 2 + [c_uint64] * 3 + [_P] * 3 +
+                      [c_uint64, c_int] + [_P] * 3 + [c_int] + [_P] * 10,
     # (the planners under the line search's objective: problem, table, then
     # the window and / or the weights, then the sibling's list; the trial
     # takes both, nullable each, after the plant)
@@ -209,7 +216,7 @@ _TYPED = ("pddp_riccati_backward", "pddp_riccati_backward_variant",
           "pddp_closed_loop_track",
           "pddp_shoot", "pddp_shoot_batch", "pddp_shoot_draws",
           "pddp_mppi", "pddp_mppi_batch", "pddp_mppi_trial",
-          "pddp_cem", "pddp_cem_batch",
+          "pddp_cem", "pddp_cem_batch", "pddp_cem_trial",
           "pddp_shoot_track", "pddp_shoot_weighted",
           "pddp_shoot_track_weighted", "pddp_mppi_track", "pddp_mppi_weighted",
           "pddp_mppi_track_weighted", "pddp_mppi_trial_goals",

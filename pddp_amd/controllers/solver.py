@@ -1435,7 +1435,8 @@ class ILQRSolver(object):
         return out
 
     def _one_sampled_objective(self, what, objective="shared"):
-        """The `objective` of `shoot`, `mppi`, `cem` and `mppi_closed_loop`.
+        """The `objective` of `shoot`, `mppi`, `cem`, `mppi_closed_loop` and
+        `cem_closed_loop` (which has no entry point for True yet and refuses).
         "shared": the refusal while a reference or per-trajectory cost
         weights are set.  "search": True where the candidates are costed
         along the reference and / or under the weights (the entry points of
@@ -1588,6 +1589,110 @@ class ILQRSolver(object):
         if tracking:  # the next call's window, as mpc_closed_loop leaves it
             self.ref_start += T
             self._graph = None  # (captured under another window)
+        return out
+
+    @_on_device
+    def cem_closed_loop(self, steps, samples, std, elites, iterations=1,
+                        std_min=0.0, mix=0.0, keep_std=False, smooth=0.0,
+                        seed=0, candidate_offset=0, z0=None, params=None,
+                        x_goal=None, u_goal=None, disturbance=None,
+                        process_std=None, obs_std=None, sample_offset=0,
+                        step_offset=0, active=None, log_costs=False,
+                        events=None, objective="shared"):
+        """A receding-horizon CEM trial of every trajectory on its own plant,
+        all `steps` control steps in ONE launch (pddp_cem_trial_*,
+        csrc/cem_trial.hip): per control step `iterations` iterations of
+        `cem`'s law from what the controller sees, around a mean that starts
+        as the plan `U` and a width - with `cem`'s selects between them: the
+        incumbent (the plan at the step's start) is replaced by an iteration's
+        mean where isfinite(J_m) & (J_m <= the carried cost), the distribution
+        moves where the iteration had an elite - then clamp(incumbent[0]) is
+        applied to plant b, the trial is logged, the next state observed and
+        the plan shifted by one (the last row repeated).  `samples`, `std`,
+        `elites`, `std_min`, `mix`, `smooth`: as `cem`.  Iteration k of control
+        step c draws its candidates as `cem(seed=, sample_offset=
+        candidate_offset + (c iterations + k) B samples)` does.
+
+        `keep_std=False`: every control step starts from the width given, the
+        usual CEM-MPC.  `keep_std=True`: a control step starts from the shift
+        of the width the step before refitted (never below `std_min`).
+
+        The plant, `disturbance`, the noise, the start, continuation with
+        `z0=None` and `active` are `mppi_closed_loop`'s, word for word: the
+        three controllers run under the same normals with the same `seed`,
+        `sample_offset` and `step_offset`.
+
+        Returns an object with `X`, `U`, `J`, `Y` as `mppi_closed_loop`;
+        `J_trace` [B][steps][iterations+1]: the incumbent's cost before
+        iteration 0 and after each; `J_m` [B][steps][iterations] and `n_elite`
+        (int32) of every iteration; `plans` [B][steps][N][m]; `std_steps`
+        [B][steps][N][m]: the width after each step's last iteration; `std`
+        [B][N][m]: the width the next control step would start from - a
+        continued call passes it back as `std`; with `log_costs` `Jc`
+        [B][steps][iterations][samples], else None.  Of a masked trajectory
+        NaN / 0 (`std`: the width given).  No host synchronisation; `events`:
+        a (start, stop) pair attached to the one launch.
+
+        Afterwards `z0`, `U` and `Z` are updated in place, the controller
+        state is re-armed and records are due, as after `mppi_closed_loop`.
+
+        `objective`: "search" with neither a reference nor per-trajectory
+        weights set is the call "shared" makes; with either set both refuse -
+        the tracked / weighted trial is not built yet."""
+        what = "cem_closed_loop"
+        self._need_sample_problem(what)
+        if self._one_sampled_objective(what, objective):
+            raise _native.NativeError(
+                '%s: objective="search" along a reference or under '
+                "per-trajectory weights: the tracked / weighted trial is not "
+                "built yet" % what)
+        B, N, n, m = self.B, self.N, self.n, self.m
+        T, S, K, I = int(steps), int(samples), int(elites), int(iterations)
+        if S < 1:
+            raise _native.NativeError("%s: %d samples" % (what, S))
+        if not 1 <= K <= S:
+            raise _native.NativeError(
+                "%s: %d elites of %d samples" % (what, K, S))
+        if I < 1:
+            raise _native.NativeError("%s: %d iterations" % (what, I))
+        if T < 1:
+            raise _native.NativeError("%s: %d steps" % (what, T))
+        sigma = self._width(what, std)
+        sigma0 = None if keep_std else sigma.clone()
+        floor = self._action_std(std_min, what)
+        step_offset, w_std, v_std, z0, disturbance = self._trial_inputs(
+            what, T, z0, disturbance, process_std, obs_std, step_offset,
+            active)
+        plant = self._plant_table(what, params, x_goal, u_goal)
+        masked = active is not None
+        out = types.SimpleNamespace(
+            X=self._out(masked, B, T + 1, n), U=self._out(masked, B, T, m),
+            J=self._out(masked, B), Y=None,
+            J_trace=self._out(masked, B, T, I + 1),
+            J_m=self._out(masked, B, T, I),
+            n_elite=self._out(masked, B, T, I, dtype=torch.int32, fill=0),
+            plans=self._out(masked, B, T, N, m),
+            std_steps=self._out(masked, B, T, N, m), std=sigma,
+            Jc=self._out(masked, B, T, I, S) if log_costs else None)
+        x_true = self._trial_start(T, z0, v_std, seed, sample_offset,
+                                   step_offset, active, out)
+        work = [self._out(False, B, N, m) for _ in range(4)]
+        Jc = out.Jc if log_costs else self._out(False, B, S)
+        p = _native.ptr
+        self._launch(
+            events, _native.call, "pddp_cem_trial", self.dtype, self._pp,
+            p(self.batch_table), p(plant), B, N, S, K, I, T, 0, T, p(self.z0),
+            p(self.U), p(self.Z), *[p(w) for w in work], p(self.u_min),
+            p(self.u_max), p(sigma), p(sigma0), p(floor), float(smooth),
+            float(mix), int(seed), int(candidate_offset), B * S,
+            p(disturbance), p(w_std), p(v_std), int(sample_offset),
+            step_offset, p(x_true), p(active), p(Jc), int(bool(log_costs)),
+            p(out.X), p(out.U), p(out.J), p(out.Y), p(out.J_trace),
+            p(out.J_m), p(out.n_elite), p(out.plans), p(out.std_steps),
+            self._s())
+        # (the plan is a new nominal: records at the next round's start)
+        self.reset_controller_state()
+        self._derivs_due = True
         return out
 
     def _plant_table(self, what, params, x_goal, u_goal):

@@ -95,15 +95,9 @@ struct CemGoalsArgs {
   T* S_out;
 };
 
-// the width of step t in `sg`, that of step t + 1 requested next to `ur2`
-#define PDDP_SAMPLED_AFTER_E0                                                  \
-  T sg[m], sg2[m];                                                             \
-  PDDP_COPY(m, sg2, Sb)
-#define PDDP_SAMPLED_WIDTH_REQUEST                                             \
-  _Pragma("unroll") for (int j = 0; j < m; ++j) {                              \
-    sg[j] = sg2[j];                                                            \
-    sg2[j] = Sb[tn * m + j];                                                   \
-  }
+// (the width per step: sampled_common.hpp's PDDP_WIDTH_ROWS_* over `Sb`)
+#define PDDP_SAMPLED_AFTER_E0 PDDP_WIDTH_ROWS_AFTER_E0
+#define PDDP_SAMPLED_WIDTH_REQUEST PDDP_WIDTH_ROWS_REQUEST
 #define PDDP_SAMPLED_WIDTH(r) sg[r]
 #define PDDP_SAMPLED_KEEP_ROW
 

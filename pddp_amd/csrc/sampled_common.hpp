@@ -1,5 +1,6 @@
 // sampled_common.hpp - what the sampling planners share (shoot.hip, mppi.hip,
-// mppi_trial.hip, cem.hip): the draws' stream, the order
+// mppi_trial.hip, cem.hip, cem_trial.hip): the
+// draws' stream, the order
 // of an argmin and of a ranking, the softmin weight, the sum over a lane
 // group, the hand-over inside a launch,
 // the hooks through which a family's ONE kernel text (*_kernel_body.inc)
@@ -149,6 +150,19 @@ PDDP_DEV void hand_over() {
 #define PDDP_GOALS_TAKE_NEXT                                                   \
   PDDP_COPY(m, P.ugoal, ug2)                                                   \
   PDDP_COPY(D::na, P.goal, xg2)
+
+// sampled_rollout_body.inc's width hooks for a width per time step (cem.hip,
+// cem_trial.hip): `Sb` is the trajectory's [N][m] rows; the width of step t in
+// `sg`, that of step t + 1 requested next to `ur2`.  With them a kernel defines
+// PDDP_SAMPLED_WIDTH(r) as sg[r].
+#define PDDP_WIDTH_ROWS_AFTER_E0                                               \
+  T sg[m], sg2[m];                                                             \
+  PDDP_COPY(m, sg2, Sb)
+#define PDDP_WIDTH_ROWS_REQUEST                                                \
+  _Pragma("unroll") for (int j = 0; j < m; ++j) {                              \
+    sg[j] = sg2[j];                                                            \
+    sg2[j] = Sb[tn * m + j];                                                   \
+  }
 
 // ---- host path -----------------------------------------------------------------
 
