@@ -62,6 +62,7 @@ pddp_*_track_weighted_* entry points (csrc/goal_kernels.hpp), with the table's
 address or NULL, the reference window and the weights; every round is
 records+separate.  Without the keyword the second setter refuses.
 """
+import contextlib
 import ctypes
 import functools
 import numbers
@@ -1541,51 +1542,33 @@ class ILQRSolver(object):
             raise _native.NativeError(
                 "%s: with a reference the trial's cost is evaluated along "
                 "it; the plant's x_goal / u_goal would not be read" % what)
-        B, N, n, m = self.B, self.N, self.n, self.m
-        T, S, K = int(steps), int(samples), int(iterations)
-        if S < 1:
-            raise _native.NativeError("%s: %d samples" % (what, S))
-        if K < 1:
-            raise _native.NativeError("%s: %d iterations" % (what, K))
-        if T < 1:
-            raise _native.NativeError("%s: %d steps" % (what, T))
+        B, N, m = self.B, self.N, self.m
         a_std = self._action_std(std, what)
         lam = self._temperature(what, temperature)
-        step_offset, w_std, v_std, z0, disturbance = self._trial_inputs(
-            what, T, z0, disturbance, process_std, obs_std, step_offset,
-            active)
-        plant = self._plant_table(what, params, x_goal, u_goal)
         masked = active is not None
-        out = types.SimpleNamespace(
-            X=self._out(masked, B, T + 1, n), U=self._out(masked, B, T, m),
-            J=self._out(masked, B), Y=None, J0=self._out(masked, B, T, K),
-            J_w=self._out(masked, B, T, K), ess=self._out(masked, B, T),
-            plans=self._out(masked, B, T, N, m),
-            Jc=self._out(masked, B, T, K, S) if log_costs else None)
-        x_true = self._trial_start(T, z0, v_std, seed, sample_offset,
-                                   step_offset, active, out)
-        U_work = self._out(False, B, N, m)
-        Jc = out.Jc if log_costs else self._out(False, B, S)
         p = _native.ptr
-        name, lead = "pddp_mppi_trial", ()
-        if goals:  # (the window and the weights, nullable each, not both)
-            name = "pddp_mppi_trial_goals"
-            lead = (self._ref_window() if tracking else (None, 0, 0)) + \
-                (p(self.batch_weights),)
-        self._launch(
-            events, _native.call, name, self.dtype, self._pp,
-            p(self.batch_table), p(plant), *lead, B, N, S, K, T, 0, T,
-            p(self.z0),
-            p(self.U), p(self.Z), p(U_work), p(self.u_min), p(self.u_max),
-            p(a_std), p(lam), float(smooth), int(seed), int(candidate_offset),
-            B * S, p(disturbance), p(w_std), p(v_std), int(sample_offset),
-            step_offset, p(x_true), p(active), p(Jc), int(bool(log_costs)),
-            p(out.X), p(out.U), p(out.J), p(out.Y), p(out.J0), p(out.J_w),
-            p(out.ess), p(out.plans), self._s())
+        with self._sampled_trial(
+                what, steps, samples, iterations, None, z0, params, x_goal,
+                u_goal, disturbance, process_std, obs_std, seed, sample_offset,
+                step_offset, active, log_costs) as (T, S, K, out, plant, tail):
+            out.J0, out.J_w = self._out(masked, B, T, K), \
+                self._out(masked, B, T, K)
+            out.ess = self._out(masked, B, T)
+            out.plans = self._out(masked, B, T, N, m)
+            U_work = self._out(False, B, N, m)
+            name, lead = "pddp_mppi_trial", ()
+            if goals:  # (the window and the weights, nullable each, not both)
+                name = "pddp_mppi_trial_goals"
+                lead = (self._ref_window() if tracking else (None, 0, 0)) + \
+                    (p(self.batch_weights),)
+            self._launch(
+                events, _native.call, name, self.dtype, self._pp,
+                p(self.batch_table), p(plant), *lead, B, N, S, K, T, 0, T,
+                p(self.z0), p(self.U), p(self.Z), p(U_work), p(self.u_min),
+                p(self.u_max), p(a_std), p(lam), float(smooth), int(seed),
+                int(candidate_offset), B * S, *tail, p(out.J0), p(out.J_w),
+                p(out.ess), p(out.plans), self._s())
         out.took = torch.isfinite(out.J_w) & (out.J_w <= out.J0)
-        # (the plan is a new nominal: records at the next round's start)
-        self.reset_controller_state()
-        self._derivs_due = True
         if tracking:  # the next call's window, as mpc_closed_loop leaves it
             self.ref_start += T
             self._graph = None  # (captured under another window)
@@ -1646,20 +1629,58 @@ class ILQRSolver(object):
                 '%s: objective="search" along a reference or under '
                 "per-trajectory weights: the tracked / weighted trial is not "
                 "built yet" % what)
-        B, N, n, m = self.B, self.N, self.n, self.m
-        T, S, K, I = int(steps), int(samples), int(elites), int(iterations)
+        B, N, m = self.B, self.N, self.m
+        sigma = self._width(what, std)
+        sigma0 = None if keep_std else sigma.clone()
+        floor = self._action_std(std_min, what)
+        masked = active is not None
+        p = _native.ptr
+        with self._sampled_trial(
+                what, steps, samples, iterations, elites, z0, params, x_goal,
+                u_goal, disturbance, process_std, obs_std, seed, sample_offset,
+                step_offset, active, log_costs) as (T, S, I, out, plant, tail):
+            out.J_trace = self._out(masked, B, T, I + 1)
+            out.J_m = self._out(masked, B, T, I)
+            out.n_elite = self._out(masked, B, T, I, dtype=torch.int32,
+                                    fill=0)
+            out.plans = self._out(masked, B, T, N, m)
+            out.std_steps, out.std = self._out(masked, B, T, N, m), sigma
+            work = [self._out(False, B, N, m) for _ in range(4)]
+            self._launch(
+                events, _native.call, "pddp_cem_trial", self.dtype, self._pp,
+                p(self.batch_table), p(plant), B, N, S, int(elites), I, T, 0,
+                T, p(self.z0), p(self.U), p(self.Z), *[p(w) for w in work],
+                p(self.u_min), p(self.u_max), p(sigma), p(sigma0), p(floor),
+                float(smooth), float(mix), int(seed), int(candidate_offset),
+                B * S, *tail, p(out.J_trace), p(out.J_m), p(out.n_elite),
+                p(out.plans), p(out.std_steps), self._s())
+        return out
+
+    @contextlib.contextmanager
+    def _sampled_trial(self, what, steps, samples, iterations, elites, z0,
+                       params, x_goal, u_goal, disturbance, process_std,
+                       obs_std, seed, sample_offset, step_offset, active,
+                       log_costs):
+        """What `mppi_closed_loop` and `cem_closed_loop` do around their one
+        launch.  Before it: the checks of the counts (`elites`: cem's, else
+        None) and of `_trial_inputs`, the plant table, the outputs both have
+        (`X`, `U`, `J`, `Y`, with `log_costs` `Jc`) and the trial's start.
+        Yields (steps, samples, iterations, out, plant, tail); `tail`: the
+        native call's arguments from `disturbance` to `Ylog`, the costs'
+        buffer - `out.Jc`, or one launch's [B][samples] - among them.  After
+        it the plan is a new nominal: the controller state is re-armed and
+        records are due at the next round's start."""
+        B, n, m = self.B, self.n, self.m
+        T, S, I = int(steps), int(samples), int(iterations)
         if S < 1:
             raise _native.NativeError("%s: %d samples" % (what, S))
-        if not 1 <= K <= S:
+        if elites is not None and not 1 <= int(elites) <= S:
             raise _native.NativeError(
-                "%s: %d elites of %d samples" % (what, K, S))
+                "%s: %d elites of %d samples" % (what, int(elites), S))
         if I < 1:
             raise _native.NativeError("%s: %d iterations" % (what, I))
         if T < 1:
             raise _native.NativeError("%s: %d steps" % (what, T))
-        sigma = self._width(what, std)
-        sigma0 = None if keep_std else sigma.clone()
-        floor = self._action_std(std_min, what)
         step_offset, w_std, v_std, z0, disturbance = self._trial_inputs(
             what, T, z0, disturbance, process_std, obs_std, step_offset,
             active)
@@ -1668,32 +1689,17 @@ class ILQRSolver(object):
         out = types.SimpleNamespace(
             X=self._out(masked, B, T + 1, n), U=self._out(masked, B, T, m),
             J=self._out(masked, B), Y=None,
-            J_trace=self._out(masked, B, T, I + 1),
-            J_m=self._out(masked, B, T, I),
-            n_elite=self._out(masked, B, T, I, dtype=torch.int32, fill=0),
-            plans=self._out(masked, B, T, N, m),
-            std_steps=self._out(masked, B, T, N, m), std=sigma,
             Jc=self._out(masked, B, T, I, S) if log_costs else None)
         x_true = self._trial_start(T, z0, v_std, seed, sample_offset,
                                    step_offset, active, out)
-        work = [self._out(False, B, N, m) for _ in range(4)]
         Jc = out.Jc if log_costs else self._out(False, B, S)
         p = _native.ptr
-        self._launch(
-            events, _native.call, "pddp_cem_trial", self.dtype, self._pp,
-            p(self.batch_table), p(plant), B, N, S, K, I, T, 0, T, p(self.z0),
-            p(self.U), p(self.Z), *[p(w) for w in work], p(self.u_min),
-            p(self.u_max), p(sigma), p(sigma0), p(floor), float(smooth),
-            float(mix), int(seed), int(candidate_offset), B * S,
+        yield T, S, I, out, plant, (
             p(disturbance), p(w_std), p(v_std), int(sample_offset),
             step_offset, p(x_true), p(active), p(Jc), int(bool(log_costs)),
-            p(out.X), p(out.U), p(out.J), p(out.Y), p(out.J_trace),
-            p(out.J_m), p(out.n_elite), p(out.plans), p(out.std_steps),
-            self._s())
-        # (the plan is a new nominal: records at the next round's start)
+            p(out.X), p(out.U), p(out.J), p(out.Y))
         self.reset_controller_state()
         self._derivs_due = True
-        return out
 
     def _plant_table(self, what, params, x_goal, u_goal):
         """[B][BATCH_ROW] plant rows of a trial whose fields are [B][.]: a

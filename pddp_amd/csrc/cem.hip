@@ -22,7 +22,9 @@
 // through its width hook; the sums are sampled_common.hpp's group_sum.  Two
 // kernels per model and type over ONE text (cem_kernel_body.inc), with
 // mppi_kernel's mapping: cem_kernel with its nullable table, cem_goals_kernel
-// with its nullable reference and weights.
+// with its nullable reference and weights.  Passes 2 and 3 are texts of their
+// own, which the trial's kernel includes too (cem_rank_body.inc,
+// cem_refit_body.inc; cem_trial.hip).
 //
 // Three passes over the same ceil(S / G) turns of the lane group:
 //   1. the candidates' rollouts, row t + 1 of sigma[b] requested a step ahead;

@@ -8,9 +8,11 @@
 // include/pddp_hip.h states the law, DESIGN.md 3.4t the kernel.
 //
 // The candidate rollout is the family's one text (sampled_rollout_body.inc)
-// through the width-per-step hooks cem.hip uses; the ranking and the refit
-// follow cem_kernel_body.inc's passes 2 and 3; the plant section is
-// mppi_trial_kernel_body.inc's.  One kernel per model and type
+// through the width-per-step hooks cem.hip uses; the ranking and the refit are
+// cem.hip's texts (cem_rank_body.inc, cem_refit_body.inc); the first
+// statements, the plant section and the closing rollout are the MPPI trial's
+// (trial_prologue.inc, trial_plant_body.inc, trial_final_rollout.inc;
+// DESIGN.md 3.4u).  One kernel per model and type
 // (cem_trial_kernel_body.inc).
 //
 // Mapping: mppi_trial_kernel's - a trajectory owns a lane group of G lanes and
@@ -76,11 +78,15 @@ struct CemTrialArgs {
 #define PDDP_SAMPLED_WIDTH(r) sg[r]
 #define PDDP_SAMPLED_KEEP_ROW
 #define PDDP_GOALS(point)
+#define PDDP_TRIAL_PLANT_PROBLEM PDDP_PLAIN_TRIAL_PLANT_PROBLEM
+#define PDDP_TRIAL_TERMINAL_GOAL PDDP_PLAIN_TRIAL_TERMINAL_GOAL
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kClosedLoopThreads) void cem_trial_kernel(
     ProblemT<T> shared, CemTrialArgs<T> a) {
 #include "cem_trial_kernel_body.inc"
 }
+#undef PDDP_TRIAL_TERMINAL_GOAL
+#undef PDDP_TRIAL_PLANT_PROBLEM
 #undef PDDP_GOALS
 #undef PDDP_SAMPLED_KEEP_ROW
 #undef PDDP_SAMPLED_WIDTH
@@ -98,16 +104,9 @@ static int launch_cem_trial(const pddp_problem& p, CemTrialArgs<T> a,
 template <typename T>
 static int cem_trial_impl(const pddp_problem* p, CemTrialArgs<T> a,
                           double smooth, double mix, void* stream) {
-  if (a.B <= 0 || a.N <= 0 || a.S <= 0 ||
-      (long long)a.B * a.S > 0x7fffffffLL || !a.z0 || !a.U || !a.sigma ||
-      !a.Jc || !(smooth >= 0.0 && smooth < 1.0) ||  // (NaN fails both)
-      !(mix >= 0.0 && mix < 1.0) || a.K < 1 || a.K > a.S || a.I < 1)
-    return PDDP_E_BADARG;
-  if (a.TT < 1 || a.t0 < 0 || a.count < 1 ||
-      (long long)a.t0 + a.count > a.TT || !a.Z || !a.Xlog || !a.Ulog ||
-      !a.Jcl || (a.v_std != nullptr && a.x_true == nullptr) ||
-      // (step_offset + c + 1 is a counter word of the draws: an int)
-      a.step_offset < 0 || a.step_offset > INT_MAX - a.TT)
+  if (!check_trial_args(a, smooth) || !a.sigma ||
+      !(mix >= 0.0 && mix < 1.0) ||  // (NaN fails both)
+      a.K < 1 || a.K > a.S || a.I < 1)
     return PDDP_E_BADARG;
   // a work buffer is there and is no other buffer of the call
   const void* work[] = {a.mean, a.width, a.Um, a.Sm};
@@ -125,10 +124,8 @@ static int cem_trial_impl(const pddp_problem* p, CemTrialArgs<T> a,
       if (work[i] == o) return PDDP_E_BADARG;
   }
   if (int rc = check_problem(p)) return rc;
-  a.beta = (T)smooth;
-  a.gamma = (T)std::sqrt(1.0 - smooth * smooth);
+  set_trial_noise<T>(a, smooth);
   a.step = (T)(1.0 - mix);
-  if (a.v_std == nullptr) a.x_true = a.Ylog = nullptr;
   PDDP_DISPATCH_MODEL(launch_cem_trial, T, p, a, (hipStream_t)stream)
 }
 

@@ -11,7 +11,10 @@
 // sums are shoot.hip's and mppi.hip's: one text each
 // (sampled_rollout_body.inc, sampled_argmin.inc, mppi_update_body.inc,
 // sampled_common.hpp; included texts, not device functions - the Makefile's
-// note on contraction).  Two kernels per model and type over ONE text
+// note on contraction).  The first statements, the plant section and the
+// closing rollout are texts the CEM trial includes too (trial_prologue.inc,
+// trial_plant_body.inc, trial_final_rollout.inc).  Two
+// kernels per model and type over ONE text
 // (mppi_trial_kernel_body.inc): mppi_trial_kernel with its nullable table,
 // mppi_trial_goals_kernel with its nullable reference and weights.
 //
@@ -103,11 +106,8 @@ struct MppiTrialGoalsArgs {
     write_params_and_goals<T, MODEL>(P, a.table + (size_t)b * PDDP_BATCH_ROW);
 #define PDDP_GOALS(point)
 #define PDDP_TRIAL_WINDOW_OF_C
-#define PDDP_TRIAL_PLANT_PROBLEM                                               \
-  ProblemT<T> Pl = P;                                                          \
-  if (a.plant != nullptr)                                                      \
-    write_params_and_goals<T, MODEL>(Pl, a.plant + (size_t)b * PDDP_BATCH_ROW);
-#define PDDP_TRIAL_TERMINAL_GOAL
+#define PDDP_TRIAL_PLANT_PROBLEM PDDP_PLAIN_TRIAL_PLANT_PROBLEM
+#define PDDP_TRIAL_TERMINAL_GOAL PDDP_PLAIN_TRIAL_TERMINAL_GOAL
 template <typename T, int MODEL>
 __global__ __launch_bounds__(kClosedLoopThreads) void mppi_trial_kernel(
     ProblemT<T> shared, MppiTrialArgs<T> a) {
@@ -208,16 +208,8 @@ static int mppi_trial_impl(const pddp_problem* p, Launch l, bool with_goals,
                            const FormGoals<T>& x, double smooth,
                            void* stream) {
   auto& a = block_of(l);
-  if (a.B <= 0 || a.N <= 0 || a.S <= 0 ||
-      (long long)a.B * a.S > 0x7fffffffLL || !a.z0 || !a.U || !a.a_std ||
-      !a.lam || !a.Jc || !(smooth >= 0.0 && smooth < 1.0))  // (NaN fails both)
-    return PDDP_E_BADARG;
-  if (a.K < 1 || a.TT < 1 || a.t0 < 0 || a.count < 1 ||
-      (long long)a.t0 + a.count > a.TT || !a.Z || !a.U_work || !a.Xlog ||
-      !a.Ulog || !a.Jcl || a.U_work == a.U ||
-      (a.v_std != nullptr && a.x_true == nullptr) ||
-      // (step_offset + c + 1 is a counter word of the draws: an int)
-      a.step_offset < 0 || a.step_offset > INT_MAX - a.TT)
+  if (!check_trial_args(a, smooth) || !a.a_std || !a.lam || a.K < 1 ||
+      !a.U_work || a.U_work == a.U)
     return PDDP_E_BADARG;
   if (with_goals) {
     const RefArgs<T>& r = x.goals;
@@ -227,9 +219,7 @@ static int mppi_trial_impl(const pddp_problem* p, Launch l, bool with_goals,
       return PDDP_E_BADARG;
   }
   if (int rc = check_problem(p)) return rc;
-  a.beta = (T)smooth;
-  a.gamma = (T)std::sqrt(1.0 - smooth * smooth);
-  if (a.v_std == nullptr) a.x_true = a.Ylog = nullptr;
+  set_trial_noise<T>(a, smooth);
   PDDP_DISPATCH_MODEL(launch_mppi_trial, T, p, l, (hipStream_t)stream)
 }
 

@@ -3,27 +3,19 @@
 // iterations of mppi's three passes, the head's decision, the plant step and
 // the shift, then the rollout of the shifted plan.  The including kernel has
 // `shared`, `a` (MppiTrialArgs or MppiTrialGoalsArgs), sampled_common.hpp's
-// hooks and defines
+// hooks and defines, for this text and for trial_plant_body.inc,
 //   PDDP_TRIAL_WINDOW_OF_C     first statement of control step c: the goals
 //                              kernel moves its reference window, else empty
 //   PDDP_TRIAL_PLANT_PROBLEM   `Pl`, the problem the applied step is logged
 //                              under
 //   PDDP_TRIAL_TERMINAL_GOAL   ahead of the trial's terminal cost: the goals
 //                              kernel's row, else empty
-  using D = ModelDims<MODEL>;
-  constexpr int n = D::n, m = D::m;
-  constexpr int kWaves = kClosedLoopThreads / kWave;
-  const int tid = threadIdx.x, G = a.G, N = a.N, S = a.S, K = a.K, TT = a.TT;
-  const int group = tid / G, lane = tid - group * G;
-  const long long bl = (long long)blockIdx.x * (blockDim.x / G) + group;
-  const bool in_batch = bl < a.B;
-  const int b = in_batch ? (int)bl : 0;
-  // (nothing of a skipped trajectory is read or written)
-  const bool live = in_batch && (a.active == nullptr || a.active[b] != 0);
-  const bool head = live && lane == 0;  // ONE lane per trajectory
-  const bool bounded = a.u_min != nullptr && a.u_max != nullptr;
-  const bool multi = blockDim.x > kWave;  // one trajectory, several wavefronts
-  const int span = G < kWave ? G : kWave;
+// The first statements, the plant section and the closing rollout are the CEM
+// trial's too (trial_prologue.inc, trial_plant_body.inc,
+// trial_final_rollout.inc).
+#define PDDP_TRIAL_ITERATIONS K = a.K
+#include "trial_prologue.inc"
+#undef PDDP_TRIAL_ITERATIONS
 
   // the controller's model of trajectory b, as mppi's kernels hold it
   PDDP_PROBLEM_OF_B
@@ -171,88 +163,14 @@
             }
           }
 
-          // apply u to the plant of row b, log the trial (the hand-over's
-          // steps 2 - 4 with its noise hooks) under `Pl`
-          T x[n], xn[n];
-#pragma unroll
-          for (int j = 0; j < n; ++j)
-            x[j] = a.v_std != nullptr ? a.x_true[(size_t)b * n + j] : z0[j];
-          const uint64_t roll = a.rollout_offset + (uint64_t)b;
-          const int step = a.step_offset + c;
-          {
-            PDDP_TRIAL_PLANT_PROBLEM
-#pragma unroll
-            for (int j = 0; j < n; ++j)
-              a.Xlog[((size_t)b * (TT + 1) + c) * n + j] = x[j];
-#pragma unroll
-            for (int j = 0; j < m; ++j) a.Ulog[bc * m + j] = u[j];
-            const Trig<T, MODEL> tr = trig_of<T, MODEL>(x);
-            Jcl += cost_value<T, MODEL>(Pl, x, u, tr, false);
-            dynamics<T, MODEL, false>(Pl, x, u, tr, xn, nullptr, nullptr);
-            if (a.disturbance != nullptr) {
-#pragma unroll
-              for (int j = 0; j < n; ++j)
-                xn[j] = xn[j] + a.disturbance[bc * n + j];
-            }
-            if (a.w_std != nullptr) {
-              T wn[n];
-              draw_units<T, n>(a.seed, roll, step, 0, wn);
-              add_scaled<T, n>(a.w_std, wn, xn);
-            }
-            if (c == TT - 1) {
-#pragma unroll
-              for (int j = 0; j < n; ++j)
-                a.Xlog[((size_t)b * (TT + 1) + TT) * n + j] = xn[j];
-              PDDP_TRIAL_TERMINAL_GOAL
-              Jcl += cost_value<T, MODEL>(Pl, xn, nullptr,
-                                          trig_of<T, MODEL>(xn), true);
-            }
-            a.Jcl[b] = Jcl;
-          }
-          // observe: x' stays the plant's, the controller gets y'
-          if (a.v_std != nullptr) {
-            T vn[n];
-#pragma unroll
-            for (int j = 0; j < n; ++j) a.x_true[(size_t)b * n + j] = xn[j];
-            draw_units<T, n>(a.seed, roll, step + 1, 1, vn);
-            add_scaled<T, n>(a.v_std, vn, xn);
-            if (a.Ylog != nullptr) {
-#pragma unroll
-              for (int j = 0; j < n; ++j)
-                a.Ylog[((size_t)b * (TT + 1) + c + 1) * n + j] = xn[j];
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < n; ++j) a.z0[(size_t)b * n + j] = xn[j];
+          // apply u to the plant of row b, log the trial, observe
+#include "trial_plant_body.inc"
         }
       }
       hand_over();
     }
   }
 
-  // the rollout of the shifted plan, clamped, from what the controller sees
-  // now, under the controller's model (the head re-reads its own stores); it
-  // reads no goal and no weight
-  if (head) {
-    T* Zb = a.Z + (size_t)b * (N + 1) * n;
-    T z[n], zn[n], u[m];
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      z[j] = a.z0[(size_t)b * n + j];
-      Zb[j] = z[j];
-    }
-    for (int i = 0; i < N; ++i) {
-#pragma unroll
-      for (int j = 0; j < m; ++j) {
-        u[j] = Ub[i * m + j];
-        if (bounded) u[j] = clamp1(u[j], umin[j], umax[j]);
-      }
-      const Trig<T, MODEL> tr = trig_of<T, MODEL>(z);
-      dynamics<T, MODEL, false>(P, z, u, tr, zn, nullptr, nullptr);
-#pragma unroll
-      for (int j = 0; j < n; ++j) {
-        z[j] = zn[j];
-        Zb[(i + 1) * n + j] = z[j];
-      }
-    }
-  }
+#define PDDP_TRIAL_PLAN Ub
+#include "trial_final_rollout.inc"
+#undef PDDP_TRIAL_PLAN

@@ -1,11 +1,11 @@
 // sampled_common.hpp - what the sampling planners share (shoot.hip, mppi.hip,
-// mppi_trial.hip, cem.hip, cem_trial.hip): the
-// draws' stream, the order
-// of an argmin and of a ranking, the softmin weight, the sum over a lane
-// group, the hand-over inside a launch,
-// the hooks through which a family's ONE kernel text (*_kernel_body.inc)
-// reaches the problem of trajectory b - the plain kernel's table row, or the
-// goals kernel's reference and weights - and the host path's common pieces.
+// mppi_trial.hip, cem.hip, cem_trial.hip):
+// the draws' stream, the order of an argmin and of a ranking, the softmin
+// weight, the sum over a lane group, the hand-over inside a launch, the hooks
+// through which a family's ONE kernel text (*_kernel_body.inc) reaches the
+// problem of trajectory b - the plain kernel's table row, or the goals kernel's
+// reference and weights -, a plain trial's plant hooks, and the host path's
+// common pieces, the trials' argument test among them.
 #pragma once
 
 #include <climits>
@@ -164,6 +164,16 @@ PDDP_DEV void hand_over() {
     sg2[j] = Sb[tn * m + j];                                                   \
   }
 
+// trial_plant_body.inc's hooks in a plain trial kernel (mppi_trial_kernel,
+// cem_trial_kernel): the applied step is logged under the controller's model
+// with row b of the plant table written over it, goals included, and the
+// terminal cost under the same goals.
+#define PDDP_PLAIN_TRIAL_PLANT_PROBLEM                                         \
+  ProblemT<T> Pl = P;                                                          \
+  if (a.plant != nullptr)                                                      \
+    write_params_and_goals<T, MODEL>(Pl, a.plant + (size_t)b * PDDP_BATCH_ROW);
+#define PDDP_PLAIN_TRIAL_TERMINAL_GOAL
+
 // ---- host path -----------------------------------------------------------------
 
 // (GoalForm, FormGoals, form_goals: goal_form.hpp)
@@ -191,6 +201,30 @@ static int launch_sampled(void (*kernel)(ProblemT<T>, Args, Extra...),
   const dim3 blocks = sampled_geometry(a, &threads);
   PDDP_LAUNCH(kernel, blocks, dim3(threads), 0, st, P, a, extra...);
   return launch_status();
+}
+
+// What the blocks of the two trials (MppiTrialArgs, MppiTrialGoalsArgs,
+// CemTrialArgs) share: false where a shared field refuses the call.  What is a
+// trial's own - K, its work buffers, its widths - its impl tests itself.
+template <typename Args>
+static bool check_trial_args(const Args& a, double smooth) {
+  return a.B > 0 && a.N > 0 && a.S > 0 &&
+         (long long)a.B * a.S <= 0x7fffffffLL && a.z0 && a.U && a.Jc &&
+         smooth >= 0.0 && smooth < 1.0 &&  // (NaN fails both)
+         a.TT >= 1 && a.t0 >= 0 && a.count >= 1 &&
+         (long long)a.t0 + a.count <= a.TT && a.Z && a.Xlog && a.Ulog &&
+         a.Jcl && (a.v_std == nullptr || a.x_true != nullptr) &&
+         // (step_offset + c + 1 is a counter word of the draws: an int)
+         a.step_offset >= 0 && a.step_offset <= INT_MAX - a.TT;
+}
+
+// The AR(1) of the draws; without measurement noise the plant's state is the
+// controller's and there is nothing to observe.
+template <typename T, typename Args>
+static void set_trial_noise(Args& a, double smooth) {
+  a.beta = (T)smooth;
+  a.gamma = (T)std::sqrt(1.0 - smooth * smooth);
+  if (a.v_std == nullptr) a.x_true = a.Ylog = nullptr;
 }
 
 }  // namespace pddp
